@@ -19,6 +19,9 @@ identical update.  Rank 0 prints ONE JSON line:
   * `roofline_kernels` micro-benchmarks through the single-op C ABI of the heaviest forward conv and the heaviest weight gradient;
   * `cpu_baseline`    the ATen-CPU executor of oracle/aten_ref.py (the reference's CPU path = libtorch CPU kernels in unet.cpp
                       order) on a bounded sample, rank 0, N=1 only.
+
+--dump-outputs DIR: rank 0 writes what the last timed step handed its caller as DIR/<name>.npy (see step_outputs), so that two
+builds can be compared output for output: model, samples and step sequence are seeded, the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -160,6 +163,24 @@ def cpu_baseline(size, budget_steps=3):   # ~3 s per 128^3 step on 16 cores: 1 w
                       "(oracle/aten_ref.py), torch %s; %d threads = the job's CPU share on a one-GPU box (16 cores; %d visible to the process)"
                       % (budget_steps, size, torch.__version__, cores, avail),
             "ms_per_step": dt * 1e3}
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def step_outputs(trainer, model):
+    """What the caller of Trainer.step() holds after it: `loss_stats` {total, ce, dice, mse} summed over the step's samples (the
+    step's return value), `params` the updated fp32 master weights and `grad_norm` ||g|| before clipping (the update zeroes the
+    gradients).  The default network's 15.0 M weights (60.1 MB) are written whole; a set over DUMP_BYTES keeps a fixed seeded
+    sample of the weights."""
+    import numpy as np
+    out = {"loss_stats": trainer._stats.cpu().numpy(), "grad_norm": model.optimizer.last_grad_norm.cpu().numpy()}
+    w = model.flat_params.cpu().numpy()
+    room = (DUMP_BYTES - sum(v.nbytes for v in out.values())) // w.itemsize
+    if w.size > room:
+        w = w[np.sort(np.random.default_rng(0).choice(w.size, room, replace=False))]
+    out["params"] = w
+    return out
 
 
 def op_flops(o):
@@ -348,7 +369,10 @@ def main():
     ap.add_argument("--in-channels", type=int, default=1)
     ap.add_argument("--augment", action="store_true", help="augment every sample on the GPU inside the timed step (unet_augment_run)")
     ap.add_argument("--prefetch", action="store_true", help="with --augment: sample ring, sample i+1 is augmented on a side stream during step i")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (rank 0, at most 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         spawn_ranks(a.gpus)
@@ -414,6 +438,11 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
+    if a.dump_outputs and rank == 0:   # read now: the batch and profile legs below step the model again
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in step_outputs(trainer, model).items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     if step_ev:   # diagnostic: where inside the timed region the time went (GPU-side interval between consecutive steps' last kernels)
         iv = [step_ev[k].elapsed_time(step_ev[k + 1]) for k in range(a.steps)]
         order = sorted(range(a.steps), key=lambda k: -iv[k])[:3]
