@@ -1815,4 +1815,33 @@ int unet_simulate_modality_run(const UnetSimulateRecipe* recipe, float* t1w, con
     })
 }
 
+// ---- quality control counts (include/unet_qc.h) ----
+static const char* qc_args_error(int out_c, int64_t voxels, int collapse_before) {
+    if (out_c < 1) return "unet_qc: out_c must be positive";
+    if (collapse_before < 0 || collapse_before >= out_c) return "invalid collapse_before";   // qc.cpp:73-74
+    if (voxels <= 0) return "unet_qc: voxels must be positive";
+    if (voxels > ((int64_t)1 << 40)) return "unet_qc: too many voxels";   // the per-block partial counts are 32-bit
+    return nullptr;
+}
+int unet_qc_scratch_bytes(int out_c, int64_t voxels, int collapse_before, size_t* bytes) {
+    if (const char* e = qc_args_error(out_c, voxels, collapse_before)) return fail(e);
+    if (!bytes) return fail("unet_qc_scratch_bytes: null output");
+    *bytes = qc_scratch_bytes(out_c, voxels, collapse_before);
+    return 0;
+}
+int unet_qc_counts(const float* logits, const float* label, const float* image0, int out_c, int64_t voxels, int collapse_before,
+                   int shift_by, uint64_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
+    if (const char* e = qc_args_error(out_c, voxels, collapse_before)) return fail(e);
+    if (!logits || !label || !counts || !scratch) return fail("unet_qc_counts: null device pointer");
+    if (shift_by < 0) return fail("unet_qc_counts: shift_by must not be negative");
+    if (shift_by > 0 && !image0) return fail("unet_qc_counts: shift_by > 0 needs image0");
+    if (scratch_bytes < qc_scratch_bytes(out_c, voxels, collapse_before)) return fail("unet_qc_counts: scratch too small (see unet_qc_scratch_bytes)");
+    OP_TRY({
+        hipPointerAttribute_t at;
+        HIP_OK(hipPointerGetAttributes(&at, logits));
+        DeviceGuard guard(at.device);
+        launch_qc_counts(logits, label, image0, out_c, voxels, collapse_before, shift_by, counts, scratch, (hipStream_t)stream);
+    })
+}
+
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include "../../include/unet_augment.h"
 #include "../../include/unet_hip.h"
+#include "../../include/unet_qc.h"
 
 namespace unet {
 
@@ -308,5 +309,10 @@ size_t augment_scratch_bytes(const UnetAugmentRecipe& r);
 void launch_augment(const UnetAugmentRecipe& r, float* image, float* label, void* scratch, hipStream_t st);
 size_t simulate_scratch_bytes(const UnetSimulateRecipe& r);
 void launch_simulate_modality(const UnetSimulateRecipe& r, float* t1w, const float* label, void* scratch, hipStream_t st);
+
+// kernels_qc.hip: per-class voxel / wrong counts of quality control (include/unet_qc.h)
+size_t qc_scratch_bytes(int out_c, int64_t S, int collapse);
+void launch_qc_counts(const float* logits, const float* label, const float* image0, int out_c, int64_t S, int collapse, int shift,
+                      uint64_t* counts, void* scratch, hipStream_t s);
 
 }  // namespace unet

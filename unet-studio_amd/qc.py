@@ -1,0 +1,269 @@
+"""Quality control of the reference (qc.cpp) over the engine: per case, the share of voxels of every class whose argmax disagrees
+with the label, written to `<model stem>.error_report.tsv` beside the model.
+
+calculate_qc is qc.cpp:55-160: an eval forward that asks the engine for the full-resolution logits only, then ONE kernel
+(include/unet_qc.h) for the subject-label shift (train.cpp:248-256), cast, collapse, argmax and the two per-class histograms.
+run_qc / qc are qc.cpp:164-376.  Reading NIfTI / BIDS and resampling to model.dim are TIPL and out of scope (as in evaluate.py):
+a case is (image_name, label_name, image, label, is_template) with image {in_count, D, H, W} and label {D, H, W} arrays (numpy or
+fp32 device tensors) already at model.dim = (W, H, D).
+
+The host rules (label information, shift predicate, bin mapping, report bytes) are plain functions that need no device."""
+import ctypes as C
+import os
+import threading
+import warnings
+
+import numpy as np
+import torch
+
+from . import engine as E
+from . import nz
+from .engine import UNetError
+
+E._sig("unet_qc_scratch_bytes", C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_size_t))
+E._sig("unet_qc_counts", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+       C.c_size_t, C.c_void_p)
+# every symbol include/unet_qc.h declares
+EXPORTS = ["unet_qc_scratch_bytes", "unet_qc_counts"]
+
+DEFAULT_MAX_TEMPLATE_LABEL = 5   # qc.cpp:231-235
+
+
+class QcStat:
+    """qc_stat (qc.cpp:14-28)"""
+
+    def __init__(self, voxels=0, wrong=0):
+        self.voxels, self.wrong = int(voxels), int(wrong)
+
+    def __iadd__(self, r):
+        self.voxels += r.voxels
+        self.wrong += r.wrong
+        return self
+
+    def ratio(self):
+        return self.wrong / self.voxels if self.voxels else 0.0
+
+    def __eq__(self, r):
+        return isinstance(r, QcStat) and (self.voxels, self.wrong) == (r.voxels, r.wrong)
+
+    def __repr__(self):
+        return "QcStat(%d, %d)" % (self.voxels, self.wrong)
+
+
+# ---- the device half ----------------------------------------------------------------------------------------------------------
+def qc_scratch_bytes(out_c, voxels, collapse_before=0):
+    n = C.c_size_t()
+    E.check(E.lib.unet_qc_scratch_bytes(int(out_c), int(voxels), int(collapse_before), C.byref(n)))
+    return n.value
+
+
+def _device_f32(a, name, device=None):
+    if not (torch.is_tensor(a) and a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()):
+        raise UNetError("qc_counts: %s must be a contiguous float32 device tensor" % name)
+    if device is not None and a.device != device:
+        raise UNetError("qc_counts: %s is on %s, the logits on %s" % (name, a.device, device))
+    return a
+
+
+def qc_counts(logits, label, collapse_before=0, image0=None, shift_by=0, scratch=None):
+    """unet_qc_counts on the current stream.  logits: {1, C, D, H, W} or {C, ...} fp32 device tensor; label: fp32, one value per voxel;
+    image0: input channel 0 (needed when shift_by > 0).  Returns the uint64 device tensor [voxels[0..C'), wrong[0..C')]."""
+    _device_f32(logits, "logits")
+    dev = logits.device
+    _device_f32(label, "label", dev)
+    out_c = int(logits.shape[1] if logits.dim() == 5 else logits.shape[0])
+    S = label.numel()
+    if logits.numel() != out_c * S:
+        raise UNetError("qc_counts: logits hold %d values, not %d classes x %d voxels" % (logits.numel(), out_c, S))
+    if image0 is not None:
+        _device_f32(image0, "image0", dev)
+        if image0.numel() < S:
+            raise UNetError("qc_counts: image0 holds fewer than %d voxels" % S)
+    need = qc_scratch_bytes(out_c, S, collapse_before)
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    cp = out_c - collapse_before + 1 if collapse_before else out_c
+    counts = torch.empty(2 * cp, dtype=torch.uint64, device=dev)
+    E.check(E.lib.unet_qc_counts(logits.data_ptr(), label.data_ptr(), image0.data_ptr() if image0 is not None else None, out_c, S,
+                                 int(collapse_before), int(shift_by), counts.data_ptr(), scratch.data_ptr(),
+                                 scratch.numel() * scratch.element_size(), torch.cuda.current_stream(dev).cuda_stream))
+    return counts
+
+
+def stats_from_counts(counts, out_count, collapse_before=0):
+    """qc.cpp:137-155: the kernel's bins -> (stats[out_count], overall).  With collapse, bin 0 (the merged classes 0..k-1) goes into
+    overall only and stats[0..k) stay empty."""
+    counts = [int(v) for v in counts]
+    cp = out_count - collapse_before + 1 if collapse_before else out_count
+    if len(counts) != 2 * cp:
+        raise UNetError("qc: %d counts, expected %d" % (len(counts), 2 * cp))
+    stats, overall = [QcStat() for _ in range(out_count)], QcStat()
+    for c in range(cp):
+        s = QcStat(counts[c], counts[cp + c])
+        overall += s
+        if not collapse_before:
+            stats[c] = s
+        elif c:
+            stats[collapse_before + c - 1] = s
+    return stats, overall
+
+
+def _to_device(a, device):
+    if torch.is_tensor(a):
+        return a.to(device=device, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+def calculate_qc(model, image, label, collapse_before=0, shift_by=0, scratch=None):
+    """qc.cpp:55-160 (with shift_subject_label applied to the label on the device when shift_by > 0) -> (stats[out_count], overall).
+    Raises UNetError with the reference's messages."""
+    W, H, D = (int(v) for v in model.dim)
+    S = D * H * W
+    if int(np.prod(image.shape)) != S * model.in_count or int(np.prod(label.shape)) != S:
+        raise UNetError("training data dimension mismatch")
+    if not 0 <= collapse_before < model.out_count:
+        raise UNetError("invalid collapse_before")
+    dev = model.device()
+    x = _to_device(image, dev).view(1, model.in_count, D, H, W)
+    t = _to_device(label, dev).view(-1)
+    with torch.no_grad():
+        logits = model._forward_level0(x)
+    if logits is None or tuple(logits.shape) != (1, model.out_count, D, H, W):
+        raise UNetError("model output dimension mismatch")
+    counts = qc_counts(logits, t, collapse_before, x.view(-1)[:S] if shift_by > 0 else None, shift_by, scratch)
+    return stats_from_counts(counts.cpu().tolist(), model.out_count, collapse_before)
+
+
+# ---- the host half --------------------------------------------------------------------------------------------------------
+def max_label_of(label):
+    """max value of the label read as int (read_label_info, train.cpp:229-246: tipl::image<3,int>, truncation toward zero)"""
+    if torch.is_tensor(label):
+        return int(torch.trunc(label.to(torch.float32)).max())
+    return int(np.trunc(np.asarray(label, dtype=np.float32)).max())
+
+
+def label_plan(cases, out_count, warn=True):
+    """qc.cpp:200-253 -> (max_template_label, shift flag per case).  The label information is read once per distinct label name."""
+    info = {}
+    mtl = 0
+    for case in cases:
+        name, is_template = case[1], bool(case[4])
+        if name not in info:
+            info[name] = (is_template, max_label_of(case[3]))
+        if info[name][0]:
+            mtl = max(mtl, info[name][1])
+    if not mtl:
+        if warn:
+            warnings.warn("no template label found; use default %d" % DEFAULT_MAX_TEMPLATE_LABEL)
+        mtl = DEFAULT_MAX_TEMPLATE_LABEL
+    shift = []
+    for case in cases:
+        is_template, max_label = info[case[1]]
+        shift.append(not is_template and max_label < mtl and max_label + mtl < out_count)
+    return mtl, shift
+
+
+def case_settings(shifted, max_template_label):
+    """(collapse_before, shift_by) of one case (qc.cpp:268,297)"""
+    return (max_template_label + 1, max_template_label) if shifted else (0, 0)
+
+
+def report_path(model_path):
+    d, f = os.path.split(model_path)
+    return os.path.join(d, os.path.splitext(f)[0] + ".error_report.tsv")
+
+
+def format_report(out_count, rows):
+    """the report text (qc.cpp:35-52,341-360, std::setprecision(9)); rows: (image, label, stats, overall, unavailable_before)"""
+    lines = ["image\tground_truth\twrong_ratio" + "".join("\twrong_ratio%d" % c for c in range(out_count))]
+    for image, label, stats, overall, unavailable in rows:
+        cols = [os.path.basename(image), os.path.basename(label), "%.9g" % overall.ratio()]
+        cols += ["N/A" if c < unavailable else "%.9g" % s.ratio() for c, s in enumerate(stats)]
+        lines.append("\t".join(cols))
+    return "\n".join(lines) + "\n"
+
+
+def write_report(model_path, out_count, rows):
+    """through <report>.tmp, then the old report removed and the new one renamed into place (qc.cpp:334-372) -> (0, report) or
+    (1, message)"""
+    report = report_path(model_path)
+    tmp = report + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(format_report(out_count, rows).encode())
+    except OSError as e:
+        return 1, "failed writing %s: %s" % (tmp, e)
+    try:
+        if os.path.lexists(report):
+            os.remove(report)
+        os.rename(tmp, report)
+    except OSError as e:
+        return 1, "cannot create %s: %s" % (report, e)
+    return 0, report
+
+
+def run_qc(model, model_path, cases, thread_count=4):
+    """qc.cpp:200-376 on a loaded, prepared model -> (0, report path) or (1, message).  Up to 4 worker threads share the model;
+    each has its own stream, QC scratch and (unet3d.py:_workspace, per host thread) workspace.  The first failure stops the others
+    and no report is written."""
+    cases = list(cases)
+    if not cases:
+        return 1, "no image/label pairs found"
+    mtl, shift = label_plan(cases, model.out_count)
+    W, H, D = (int(v) for v in model.dim)
+    dev = model.device()
+    model.plan_for((D, H, W))                     # made here: the workers only look it up
+    n_workers = min(4, max(1, int(thread_count)), len(cases))
+    stats, errors = [None] * len(cases), [""] * len(cases)
+    lock, failed, nxt = threading.Lock(), threading.Event(), [0]
+
+    def worker():
+        with torch.cuda.device(dev), torch.no_grad():
+            stream = torch.cuda.Stream(dev)
+            with torch.cuda.stream(stream):
+                scratch = torch.empty(qc_scratch_bytes(model.out_count, D * H * W), dtype=torch.uint8, device=dev)
+                while not failed.is_set():
+                    with lock:
+                        i = nxt[0]
+                        nxt[0] += 1
+                    if i >= len(cases):
+                        break
+                    try:
+                        collapse, shift_by = case_settings(shift[i], mtl)
+                        stats[i] = calculate_qc(model, cases[i][2], cases[i][3], collapse, shift_by, scratch)
+                        continue
+                    except Exception as e:   # qc.cpp:300-309
+                        errors[i] = str(e) or "unknown QC error"
+                    failed.set()
+                    break
+
+    if n_workers == 1:
+        worker()
+    else:
+        threads = [threading.Thread(target=worker) for _ in range(n_workers)]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join()
+    if failed.is_set():
+        for i, e in enumerate(errors):
+            if e:
+                return 1, "%s: %s" % (cases[i][0], e)
+        return 1, "QC failed"
+    rows = [(c[0], c[1], s[0], s[1], case_settings(sh, mtl)[0]) for c, s, sh in zip(cases, stats, shift)]
+    return write_report(model_path, model.out_count, rows)
+
+
+def qc(model_path, cases, device="cuda:0", dtype="bf16", thread_count=4):
+    """int qc(void) (qc.cpp:164-376) for cases already read -> (0, report path) or (1, message)"""
+    from .unet3d import UNet3d
+    if not os.path.exists(model_path):
+        return 1, "cannot find model %s" % model_path
+    try:
+        model = nz.load_from_file(model_path, lambda i, o, a: UNet3d(i, o, a, device=device, dtype=dtype))
+    except (nz.NzError, UNetError) as e:
+        return 1, "cannot load model %s: %s" % (model_path, e)
+    if model.out_count < 2:
+        return 1, "QC requires a categorical model"
+    model.prepare_for_inference(device)
+    return run_qc(model, model_path, cases, thread_count)

@@ -389,6 +389,23 @@ class UNet3d:
 
     __call__ = forward
 
+    def _forward_level0(self, x):
+        """forward()[0] alone, without autograd: the coarse levels' outs are NULL, so the engine skips their heads (quality control,
+        qc.cpp:87-94, reads nothing else).  Runs on this thread's workspace and the current stream; None when level 0 has no head."""
+        x = self._check_input(x)
+        plan = self.plan_for(x.shape[2:])
+        ws = self._workspace(plan)
+        shape = plan.output_shapes[0]
+        if shape[1] == 0:
+            return None
+        out = torch.empty(shape, dtype=torch.float32, device=self._device)
+        op = E.ptr_array([out.data_ptr()] + [None] * (len(plan.output_shapes) - 1))
+        mode = 1 if self._training else 0
+        E.check(E.lib.unet_forward(plan.handle, self._pp, self._bp, x.data_ptr(), op, ws.data_ptr(), mode, _stream_ptr(self._device)))
+        if mode and self._buffers:
+            self.num_batches_tracked += 1
+        return out
+
     # ---- fused train micro-step (train.cpp:615-706 for one sample) ----
     def forward_backward(self, x, target, cost_ce=True, cost_dice=True, cost_mse=True, collapse_before=0, packs_current=False, losses_out=None):
         """forward + calc_losses over all deep-supervision levels + backward, all in the engine.
