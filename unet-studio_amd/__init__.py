@@ -14,6 +14,8 @@ from . import nz  # noqa: F401
 from .nz import NzError  # noqa: F401
 from . import qc  # noqa: F401  (the module: qc.qc() is the reference's qc(), qc.EXPORTS the symbols of include/unet_qc.h)
 from .qc import QcStat, calculate_qc, qc_counts, run_qc  # noqa: F401
+from . import feed  # noqa: F401  (the module: feed.EXPORTS the symbols of include/unet_feed.h)
+from .feed import TrainingFeed  # noqa: F401
 
 
 def save_to_file(model, file_name):

@@ -301,6 +301,9 @@ class PrefetchedVolumes:
         self.source, self.stride = source, int(stride)
         self.stream = torch.cuda.Stream(device=device, priority=0)
         self._ready = {}
+        if hasattr(source, "sample_info"):   # the template/subject feed (feed.py): what the trainer asks about a sample passes through
+            self.sample_info = source.sample_info
+            self.max_template_label, self.has_subject_data = source.max_template_label, source.has_subject_data
 
     def _produce(self, index):
         import torch

@@ -12,6 +12,7 @@
 #include <stdexcept>
 #include <string>
 #include <mutex>
+#include <random>
 #include <unordered_map>
 #include <vector>
 
@@ -1842,6 +1843,64 @@ int unet_qc_counts(const float* logits, const float* label, const float* image0,
         DeviceGuard guard(at.device);
         launch_qc_counts(logits, label, image0, out_c, voxels, collapse_before, shift_by, counts, scratch, (hipStream_t)stream);
     })
+}
+
+// ---- template/subject training feed (include/unet_feed.h) ----
+static const char* feed_args_error(const void* label, int64_t voxels, const void* scratch, size_t scratch_bytes) {
+    if (voxels <= 0) return "unet_feed: voxels must be positive";
+    if (!label || !scratch) return "unet_feed: null device pointer";
+    if (scratch_bytes < feed_scratch_bytes(voxels)) return "unet_feed: scratch too small (see unet_feed_scratch_bytes)";
+    return nullptr;
+}
+#define FEED_ON_DEVICE_OF(ptr, ...)                \
+    OP_TRY({                                       \
+        hipPointerAttribute_t at;                  \
+        HIP_OK(hipPointerGetAttributes(&at, ptr)); \
+        DeviceGuard guard(at.device);              \
+        __VA_ARGS__;                               \
+    })
+int unet_feed_scratch_bytes(int64_t voxels, size_t* bytes) {
+    if (voxels <= 0) return fail("unet_feed: voxels must be positive");
+    if (!bytes) return fail("unet_feed_scratch_bytes: null output");
+    *bytes = feed_scratch_bytes(voxels);
+    return 0;
+}
+int unet_feed_label_max(const float* label, int64_t voxels, int32_t* out_max, void* scratch, size_t scratch_bytes, void* stream) {
+    if (const char* e = feed_args_error(label, voxels, scratch, scratch_bytes)) return fail(e);
+    if (!out_max) return fail("unet_feed_label_max: null output");
+    FEED_ON_DEVICE_OF(label, launch_feed_label_max(label, voxels, (int*)out_max, scratch, (hipStream_t)stream));
+}
+int unet_feed_prepare(const float* image0, float* label, int64_t voxels, int normalize, int shift_by, int32_t* label_max,
+                      void* scratch, size_t scratch_bytes, void* stream) {
+    if (const char* e = feed_args_error(label, voxels, scratch, scratch_bytes)) return fail(e);
+    if (shift_by < 0) return fail("unet_feed_prepare: shift_by must not be negative");
+    if (shift_by > 0 && !image0) return fail("unet_feed_prepare: shift_by > 0 needs image0");
+    FEED_ON_DEVICE_OF(label, launch_feed_prepare(image0, label, voxels, normalize, shift_by, (int*)label_max, scratch, (hipStream_t)stream));
+}
+int unet_feed_target(const float* label, int64_t voxels, int normalize, int64_t* target, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+    if (const char* e = feed_args_error(label, voxels, scratch, scratch_bytes)) return fail(e);
+    if (!target) return fail("unet_feed_target: null device pointer");
+    FEED_ON_DEVICE_OF(label, launch_feed_target(label, voxels, normalize, target, scratch, (hipStream_t)stream));
+}
+int unet_feed_schedule(uint64_t seed, int batch_size, int n_template, int n_subject, int64_t first, int64_t count, int32_t* out_case,
+                       int32_t* out_is_template) {
+    if (batch_size < 1) return fail("unet_feed_schedule: batch_size must be positive");
+    if (n_template < 0 || n_subject < 0 || n_template + n_subject == 0) return fail("unet_feed_schedule: no cases");
+    if (first < 0 || count < 0) return fail("unet_feed_schedule: first and count must not be negative");
+    if (count && (!out_case || !out_is_template)) return fail("unet_feed_schedule: null output");
+    // train.cpp:391-401, with the library's own engine and distributions: the draws are the reference's for a given seed
+    std::uniform_int_distribution<int> template_gen(0, std::max<int>(1, n_template) - 1);
+    std::uniform_int_distribution<int> non_template_gen(0, std::max<int>(1, n_subject) - 1);
+    std::mt19937 gen(seed);
+    for (int64_t seed_id = 0; seed_id < first + count; ++seed_id) {
+        const bool use_template = n_subject == 0 || seed_id % batch_size < n_template;
+        const int c = use_template ? template_gen(gen) : non_template_gen(gen);
+        if (seed_id < first) continue;
+        out_case[seed_id - first] = c;
+        out_is_template[seed_id - first] = use_template ? 1 : 0;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/unet_augment.h"
+#include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
 #include "../../include/unet_qc.h"
 
@@ -314,5 +315,12 @@ void launch_simulate_modality(const UnetSimulateRecipe& r, float* t1w, const flo
 size_t qc_scratch_bytes(int out_c, int64_t S, int collapse);
 void launch_qc_counts(const float* logits, const float* label, const float* image0, int out_c, int64_t S, int collapse, int shift,
                       uint64_t* counts, void* scratch, hipStream_t s);
+
+// kernels_feed.hip: label max / normalize / subject shift / int64 target of the training feed (include/unet_feed.h)
+size_t feed_scratch_bytes(int64_t S);
+void launch_feed_label_max(const float* label, int64_t S, int* out_max, void* scratch, hipStream_t s);
+void launch_feed_prepare(const float* image0, float* label, int64_t S, int normalize, int shift, int* label_max, void* scratch,
+                         hipStream_t s);
+void launch_feed_target(const float* label, int64_t S, int normalize, int64_t* target, void* scratch, hipStream_t s);
 
 }  // namespace unet

@@ -142,14 +142,15 @@ def max_label_of(label):
     return int(np.trunc(np.asarray(label, dtype=np.float32)).max())
 
 
-def label_plan(cases, out_count, warn=True):
-    """qc.cpp:200-253 -> (max_template_label, shift flag per case).  The label information is read once per distinct label name."""
+def label_plan(cases, out_count, warn=True, max_of=max_label_of):
+    """qc.cpp:200-253 -> (max_template_label, shift flag per case).  The label information is read once per distinct label name;
+    max_of(label) reads it (feed.py passes the maxima it took on the device)."""
     info = {}
     mtl = 0
     for case in cases:
         name, is_template = case[1], bool(case[4])
         if name not in info:
-            info[name] = (is_template, max_label_of(case[3]))
+            info[name] = (is_template, max_of(case[3]))
         if info[name][0]:
             mtl = max(mtl, info[name][1])
     if not mtl:

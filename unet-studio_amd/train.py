@@ -73,6 +73,7 @@ class Trainer:
         if model.optimizer is None:
             model.create_optimizer(param.learning_rate)  # train.cpp:942
         self._stats = torch.zeros(4, dtype=torch.float32, device=model.device())
+        self._acc = None   # a sample_info source: {stats, count} in one buffer, _stats its first 4 floats
 
     def lr_at(self, epoch):
         """train.cpp:566."""
@@ -87,6 +88,21 @@ class Trainer:
         count = 0
         mine = list(range(self.rank, p.batch_size, self.world_size))
         works = []
+        # a source that knows where each sample came from (feed.TrainingFeed, train.cpp:612-613): a shifted subject is trained with the
+        # template classes collapsed (:673-674), and training errors count subject samples only when there are any (:676-682)
+        info = getattr(self.source, "sample_info", None)
+        if info is not None:
+            if self._acc is None:
+                self._acc = torch.zeros(5, dtype=torch.float32, device=m.device())   # {total, ce, dice, mse, counted samples}
+                self._stats = self._acc[:4]
+            collapse, counted = {}, {}
+            for b in mine:
+                is_template, is_shifted = info(cur_data_index + b)
+                collapse[b] = self.source.max_template_label + 1 if is_shifted else 0
+                counted[b] = not self.source.has_subject_data or not is_template
+            kc = {b: {"collapse_before": collapse[b]} if collapse[b] else {} for b in mine}
+        else:
+            kc, counted = {b: {} for b in mine}, None
         # The collective sequence must be a pure function of (plan, world_size, batch_size): a rank without a sample of this step
         # (batch_size < world_size; the reference simply starts min(gpus, batch_size) threads, train.cpp:581-582) never enters the
         # bucketed backward, so the per-bucket all-reduces are only used when EVERY rank has at least one micro-step.
@@ -105,12 +121,13 @@ class Trainer:
         # is exactly what one accumulating buffer would hold, so the update is bit-identical to the sequential order.  Not with bnorm
         # (the running statistics are updated in forward order) and not for models without lanes (test stand-ins).
         lanes_on = (self.in_flight > 1 and len(mine) > 1 and hasattr(m, "make_lane") and not m.buffers())
-        if lanes_on or not mine or not self.stats_direct:
-            self._stats.zero_()
+        if lanes_on or not mine or not self.stats_direct or counted is not None:
+            (self._acc if counted is not None else self._stats).zero_()
         if lanes_on:
-            losses_all = self._step_in_lanes(mine, cur_data_index)
-            for l in losses_all:
-                self._stats += l
+            losses_all = self._step_in_lanes(mine, cur_data_index, kc)
+            for b, l in zip(mine, losses_all):
+                if counted is None or counted[b]:
+                    self._stats += l
             count = len(mine)
             mine = []
             overlap = False
@@ -125,7 +142,8 @@ class Trainer:
             last_size = tuple(x.shape[2:])
             kw = {"packs_current": True} if (self.packs_reuse and last_size in packed_sizes) else {}
             packed_sizes.add(last_size)
-            first_direct = k == 0 and self.stats_direct
+            first_direct = k == 0 and self.stats_direct and counted is None
+            kw.update(kc[b])
             if first_direct:
                 kw["losses_out"] = self._stats
             if overlap and k == len(mine) - 1:
@@ -133,19 +151,25 @@ class Trainer:
                 losses = m.forward_backward_bucketed(x, t, reduce_bucket, p.cost_ce, p.cost_dice, p.cost_mse, **kw)
             else:
                 losses = m.forward_backward(x, t, p.cost_ce, p.cost_dice, p.cost_mse, **kw)
-            if not first_direct:
+            if not first_direct and (counted is None or counted[b]):
                 self._stats += losses
             count += 1
+        if counted is not None:
+            n_counted = sum(1 for b in counted if counted[b])
+            if n_counted:
+                self._acc[4:5].fill_(float(n_counted))
+        # the statistics and, for a sample_info source, the count of the samples they hold go through one collective
+        stats = self._acc if counted is not None else self._stats
         if self.comm is not None:
             if not overlap:
                 self.comm.allreduce(m.flat_grads, 0, m.flat_grads.numel(), stream)
-            self.comm.allreduce(self._stats, 0, 4, stream)          # loss-stat gather, train.cpp:732-741
+            self.comm.allreduce(stats, 0, stats.numel(), stream)    # loss-stat gather, train.cpp:732-741
             self.comm.join(stream)                                  # the update below reads the summed gradients
         elif self.world_size > 1:
             # gradient sum over replicas (unet.cpp:224-244 -> RCCL all-reduce of the flat buffer, in buckets when overlapped)
             if not overlap:
                 dist.all_reduce(m.flat_grads, op=dist.ReduceOp.SUM, group=self.group)
-            dist.all_reduce(self._stats, op=dist.ReduceOp.SUM, group=self.group)  # loss-stat gather, train.cpp:732-741
+            dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=self.group)  # loss-stat gather, train.cpp:732-741
             for w in works:
                 w.wait()
         m.optimizer.step(grad_scale=1.0 / p.batch_size, clip_norm=12.0)  # train.cpp:759-766
@@ -164,7 +188,7 @@ class Trainer:
         self.cur_epoch += 1
         return self._stats
 
-    def _step_in_lanes(self, mine, cur_data_index):
+    def _step_in_lanes(self, mine, cur_data_index, kc=None):
         """this rank's micro-steps of one optimizer step, `in_flight` at a time: micro-step k on lane k % in_flight (stream order inside a
         lane), gradients of micro-step k into buffer k (buffer 0 = flat_grads), then ONE ordered sum into flat_grads"""
         import torch.cuda as tc
@@ -192,7 +216,7 @@ class Trainer:
                                      % (tuple(x0.shape[2:]), tuple(x.shape[2:])))
                 # a lane's workspace holds its own filter packs: made by the lane's first micro-step of the step, reused by its later ones
                 l = m.forward_backward_lane(lane, x, t, self._gptrs[k], p.cost_ce, p.cost_dice, p.cost_mse,
-                                            packs_current=self.packs_reuse and k >= self.in_flight)
+                                            packs_current=self.packs_reuse and k >= self.in_flight, **(kc[b] if kc else {}))
             l.record_stream(main)
             losses.append(l)
         for lane in self._lanes:
@@ -224,8 +248,15 @@ class Trainer:
         return errors
 
     def record_errors(self):
-        """train.cpp:743-752: append the step's mean (ce, dice, mse) -- a host sync, call it sparingly"""
-        e = (self._stats[1:4] / float(self.param.batch_size)).tolist()
+        """train.cpp:743-752: append the step's mean (ce, dice, mse) -- a host sync, call it sparingly.  With a sample_info source
+        the mean is over the counted samples of all ranks, and nothing is appended when no sample was counted (train.cpp:729-752)."""
+        if getattr(self.source, "sample_info", None) is not None and self._acc is not None:
+            acc = self._acc.cpu()
+            if not float(acc[4]):
+                return []
+            e = (acc[1:4] / acc[4]).tolist()
+        else:
+            e = (self._stats[1:4] / float(self.param.batch_size)).tolist()
         with self.model.error_mutex:
             self.model.training_errors.extend(e)
         return e
