@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/unet_hip.h"
+#include "conv_select.h"
 #include "graph.hpp"
 #include "kernels.h"
 
@@ -44,6 +45,13 @@ struct DeviceGuard {
 };
 
 size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// the switches of DESIGN.md §9 that this file reads, once per process.  UNET_OP_POLITE: unet_op_conv3d_bwd_weight launches as the engine's
+// side stream does (one 4-wave block per CU, single (ca, cb) pairs), for micro-benchmarks and counters of the kernel as the step runs it
+struct EnvSwitches {
+    bool no_side_stream = getenv("UNET_NO_SIDE_STREAM"), no_first_wgrad_fuse = getenv("UNET_NO_FIRST_WGRAD_FUSE"), op_polite = getenv("UNET_OP_POLITE");
+};
+const EnvSwitches& env() { static const EnvSwitches e; return e; }
 
 // ---- per-op timing (unet_profile_begin / unet_profile_end) ----
 // While a host thread has a profile open, every forward / backward it issues runs on the caller's stream alone (no side
@@ -88,9 +96,7 @@ struct unet_plan {
     mutable std::unordered_map<const void*, std::pair<int, int>> bn_pending;
     // ... and the tensors whose whole norm backward a deep-level dgrad already ran in its epilogue (kernels_mfma_deep.hip): workspace -> tensors
     mutable std::unordered_map<const void*, std::vector<int>> bn_done;
-    std::vector<char> use_mfma;              // per op: forward runs on the MFMA kernel
-    std::vector<char> dgrad_mfma;            // per op: dgrad runs on the MFMA kernel
-    std::vector<char> wgrad_mfma;            // per op: wgrad runs on the MFMA kernel
+    std::vector<ConvChoice> conv;            // per op: the kernel family of each direction (conv / conv_trans; conv_select.h)
     size_t wgrad_off = 0;
     // sliding-window wgrads keep their slabs until ONE batched reduce per backward (part): per-op slab regions + the job table
     std::vector<size_t> wz_off;              // per op: slab region (SIZE_MAX: op does not use k_mfma_wgrad_z)
@@ -147,6 +153,10 @@ struct unet_plan {
         cg.ks = op.ks; cg.stride = op.stride;
         return cg;
     }
+    // the sources by their channel counts: what the kernel choice and the scratch sizes read
+    void src_chans(const Op& op, SrcDesc* sd) const {
+        for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
+    }
     // Which weight-gradient launches are "polite" (one 4-wave block per CU: mfma_util.h polite_lds): every one that runs on the side
     // stream.  The backward walks the ops from the last to the first -- the decoder's top levels (their gradients are HELD, see
     // backward()), then the small levels, then the encoder's top levels; polite launches for the tail of the step as well measured as
@@ -179,11 +189,12 @@ struct unet_plan {
     bool head_only(size_t t) const {
         if (dtype != UNET_DTYPE_BF16 || g.tensors[t].norm < 0 || g.tensors[t].C % 16) return false;
         int readers = 0;
-        for (const Op& op : g.ops) {
+        for (size_t i = 0; i < g.ops.size(); ++i) {
+            const Op& op = g.ops[i];
             if (op.kind == OP_NORM) continue;
             for (int k = 0; k < op.nsrc; ++k) {
                 if (op.src[k] != (int)t) continue;
-                if (!(op.kind == OP_CONV && op.out_level >= 0 && op.nsrc == 1 && head_supported(op_geom_of(op), 1))) return false;
+                if (conv[i].fwd != Fwd::head) return false;
                 ++readers;
             }
         }
@@ -191,6 +202,17 @@ struct unet_plan {
     }
     void layout() {
         choose_polite();
+        // The kernel of every direction of every conv / conv_trans.  The sources are described by their channel counts alone: in the AUTO
+        // engine a consumer reads a tensor with a norm or an activation through its activated copy (a_off below), except a tensor that
+        // only fused heads read, and a head's choice does not depend on its source.
+        conv.assign(g.ops.size(), ConvChoice());
+        for (size_t i = 0; i < g.ops.size(); ++i) {
+            const Op& op = g.ops[i];
+            if (op.kind != OP_CONV && op.kind != OP_CONVT) continue;
+            SrcDesc sd[2];
+            src_chans(op, sd);
+            conv[i] = choose_conv(dtype, impl, op_geom_of(op), sd, op.nsrc, op.out_level >= 0, op.kind == OP_CONVT);
+        }
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
         t_off.assign(g.tensors.size(), SIZE_MAX);
@@ -224,108 +246,56 @@ struct unet_plan {
         }
         w_fwd.assign(g.ops.size(), SIZE_MAX); w_dgrad.assign(g.ops.size(), SIZE_MAX);
         wm_fwd.assign(g.ops.size(), SIZE_MAX); wm_dgrad.assign(g.ops.size(), SIZE_MAX);
-        use_mfma.assign(g.ops.size(), 0);
-        dgrad_mfma.assign(g.ops.size(), 0);
+        auto grow = [](size_t& m, size_t b) { if (b > m) m = b; };
         for (size_t i = 0; i < g.ops.size(); ++i) {
             const Op& op = g.ops[i];
             if (op.kind != OP_CONV && op.kind != OP_CONVT) continue;
+            const ConvChoice& c = conv[i];
+            const ConvGeom cg = op_geom_of(op);
             int k3 = op.kind == OP_CONV ? op.ks * op.ks * op.ks : 8;
             w_fwd[i] = take((size_t)k3 * op.cin * round_up(op.cout, 8) * 4);
             w_dgrad[i] = take((size_t)k3 * op.cout * round_up(op.cin, 8) * 4);
-            if (op.kind == OP_CONV && impl == UNET_IMPL_AUTO && op.out_level < 0) {
-                ConvGeom cg = op_geom_of(op);
-                SrcDesc sd[2];
-                for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
-                if (mfma_conv_fwd_supported(dtype, cg, sd, op.nsrc)) {
-                    use_mfma[i] = 1;
-                    wm_fwd[i] = take(mfma_conv_w_bytes(cg));
-                    if (g.tensors[op.dst].norm >= 0) {
-                        size_t pb = (size_t)mfma_conv_blocks(cg) * op.cout * 2 * 4;
-                        if (pb > pmax) pmax = pb;
-                    }
-                }
-                if (conv_first_f32_mfma_supported(dtype, cg, sd, op.nsrc) && g.tensors[op.dst].norm >= 0) {
-                    size_t pb = (size_t)conv_first_f32_mfma_blocks(cg) * op.cout * 2 * 8;
-                    if (pb > pmax) pmax = pb;
-                }
-                if (conv_f32_mfma_supported(dtype, cg, sd, op.nsrc) && g.tensors[op.dst].norm >= 0) {   // fp64 statistics rows of the fp32 conv
-                    size_t pb = (size_t)conv_f32_mfma_stat_rows(cg, sd) * op.cout * 2 * 8;
-                    if (pb > pmax) pmax = pb;
-                }
-                if (mfma_conv_dgrad_supported(dtype, cg, sd, op.nsrc)) {
-                    dgrad_mfma[i] = 1;
-                    wm_dgrad[i] = take(mfma_conv_dgrad_w_bytes(cg));
-                    if (op.stride == 2) {      // norm-backward partial rows of the stride-2 dgrad's epilogue (kernels_mfma_s2.hip)
-                        size_t pb = (size_t)s2_conv_dgrad_rows_max() * op.cin * 2 * 4;
-                        if (pb > pmax) pmax = pb;
-                    }
-                }
+            if (op.kind == OP_CONVT) {
+                if (c.mfma_fwd()) { wm_fwd[i] = take(mfma_convt_w_bytes(cg)); wm_dgrad[i] = take(mfma_convt_dgrad_w_bytes(cg)); }
+                continue;
             }
-            if (op.kind == OP_CONVT && impl == UNET_IMPL_AUTO) {
-                ConvGeom cg = op_geom_of(op);
-                SrcDesc sd[2];
-                for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
-                if (mfma_convt_supported(dtype, cg, sd, op.nsrc)) {
-                    use_mfma[i] = 1; dgrad_mfma[i] = 1;
-                    wm_fwd[i] = take(mfma_convt_w_bytes(cg));
-                    wm_dgrad[i] = take(mfma_convt_dgrad_w_bytes(cg));
-                }
+            const bool stats = g.tensors[op.dst].norm >= 0;   // statistics partial rows of the forward's epilogue
+            SrcDesc sd[2];
+            src_chans(op, sd);
+            if (c.mfma_fwd()) {
+                wm_fwd[i] = take(mfma_conv_w_bytes(cg));
+                if (stats) grow(pmax, (size_t)mfma_conv_blocks(cg) * op.cout * 2 * 4);
+            }
+            if (c.fwd == Fwd::first_f32_mfma && stats) grow(pmax, (size_t)conv_first_f32_mfma_blocks(cg) * op.cout * 2 * 8);
+            if (c.fwd == Fwd::f32_mfma && stats) grow(pmax, (size_t)conv_f32_mfma_stat_rows(cg, sd) * op.cout * 2 * 8);   // fp64 rows
+            if (c.dgrad == Dgrad::mfma) {
+                wm_dgrad[i] = take(mfma_conv_dgrad_w_bytes(cg));
+                // norm-backward partial rows of the stride-2 dgrad's epilogue (kernels_mfma_s2.hip)
+                if (op.stride == 2) grow(pmax, (size_t)s2_conv_dgrad_rows_max() * op.cin * 2 * 4);
             }
         }
         partial_bytes = pmax ? pmax : 256;
         partial_off = take(partial_bytes);
-        // MFMA wgrad: one shared slab scratch (ops run one after another on the stream)
-        wgrad_mfma.assign(g.ops.size(), 0);
+        // weight gradients: one shared slab scratch (ops run one after another on the stream)
         size_t wmax = 0, hmax = 0;
         for (size_t i = 0; i < g.ops.size(); ++i) {
             const Op& op = g.ops[i];
-            if (op.kind != OP_CONV || impl != UNET_IMPL_AUTO) continue;
-            ConvGeom cg = op_geom_of(op);
-            SrcDesc sd[2];
-            for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
-            if (mfma_wgrad_supported(dtype, cg, sd, op.nsrc)) {
-                wgrad_mfma[i] = 1;
-                size_t b = mfma_wgrad_scratch_bytes(cg, side_polite[i]);
-                if (b > wmax) wmax = b;
-            }
-        }
-        for (size_t i = 0; i < g.ops.size(); ++i) {
-            const Op& op = g.ops[i];
             if (op.kind != OP_CONV && op.kind != OP_CONVT) continue;
-            ConvGeom cg = op_geom_of(op);
-            size_t b = wgrad_direct_scratch_bytes(cg, op.kind == OP_CONVT);
-            if (b > wmax) wmax = b;
-            if (op.kind == OP_CONV && wgrad_small_supported(cg, op.nsrc)) {
-                b = wgrad_small_scratch_bytes(cg);
-                if (b > wmax) wmax = b;
-            }
-            if (op.kind == OP_CONV && impl == UNET_IMPL_AUTO) {
-                SrcDesc sd[2];
-                for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
-                if (wgrad_f32_mfma_supported(dtype, cg, sd, op.nsrc)) {
-                    b = wgrad_f32_mfma_scratch_bytes(cg);
-                    if (b > wmax) wmax = b;
+            const ConvChoice& c = conv[i];
+            const ConvGeom cg = op_geom_of(op);
+            grow(wmax, wgrad_direct_scratch_bytes(cg, op.kind == OP_CONVT));   // (for every layer, whichever kernel it runs)
+            if (op.kind == OP_CONVT) {
+                if (c.wgrad == Wgrad::mfma) {
+                    grow(wmax, mfma_convt_wgrad_scratch_bytes(cg));
+                    grow(wmax, bias_grad_scratch_bytes(cg.Cout, (int64_t)cg.Do * cg.Ho * cg.Wo));
                 }
+                continue;
             }
-            if (op.kind == OP_CONV && cg.Cin == 1 && (cg.Cout == 16 || cg.Cout == 32)) {
-                b = conv_first_wgrad_mfma_scratch_bytes(cg);
-                if (b > wmax) wmax = b;
-            }
-            if (op.kind == OP_CONV && head_supported(cg, op.nsrc)) {
-                b = head_bwd_scratch_bytes(cg);
-                if (b > hmax) hmax = b;
-            }
-            if (op.kind == OP_CONVT && impl == UNET_IMPL_AUTO) {
-                SrcDesc sd[2];
-                for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
-                if (mfma_convt_wgrad_supported(dtype, cg, sd, op.nsrc)) {
-                    wgrad_mfma[i] = 1;
-                    b = mfma_convt_wgrad_scratch_bytes(cg);
-                    if (b > wmax) wmax = b;
-                    b = bias_grad_scratch_bytes(cg.Cout, (int64_t)cg.Do * cg.Ho * cg.Wo);
-                    if (b > wmax) wmax = b;
-                }
-            }
+            if (c.wgrad == Wgrad::mfma) grow(wmax, mfma_wgrad_scratch_bytes(cg, side_polite[i]));
+            if (c.wgrad == Wgrad::f32_mfma) grow(wmax, wgrad_f32_mfma_scratch_bytes(cg));
+            if (wgrad_small_supported(cg, op.nsrc)) grow(wmax, wgrad_small_scratch_bytes(cg));   // (also where another kernel runs)
+            if (cg.Cin == 1 && (cg.Cout == 16 || cg.Cout == 32)) grow(wmax, conv_first_wgrad_mfma_scratch_bytes(cg));   // (at any dtype)
+            if (head_supported(cg, op.nsrc)) grow(hmax, head_bwd_scratch_bytes(cg));   // (also for a conv that is no head)
         }
         wgrad_off = take(wmax ? wmax : 256);
         head_off = take(hmax ? hmax : 256);
@@ -335,23 +305,18 @@ struct unet_plan {
             deep_cnt_off = take((size_t)deep_ncnt * 4);
         }
         head_op_off.assign(g.ops.size(), SIZE_MAX);
-        for (size_t i = 0; i < g.ops.size(); ++i) {
-            const Op& op = g.ops[i];
-            if (op.kind != OP_CONV || op.out_level < 0 || impl != UNET_IMPL_AUTO) continue;
-            ConvGeom cg = op_geom_of(op);
-            if (head_supported(cg, op.nsrc)) head_op_off[i] = take(head_bwd_scratch_bytes(cg));
-        }
+        for (size_t i = 0; i < g.ops.size(); ++i)
+            if (conv[i].fwd == Fwd::head) head_op_off[i] = take(head_bwd_scratch_bytes(op_geom_of(g.ops[i])));
         // every matrix-core weight gradient keeps a slab region of its own until the batched reduce of the backward (part)
         wz_off.assign(g.ops.size(), SIZE_MAX);
         for (size_t i = 0; i < g.ops.size(); ++i) {
             const Op& op = g.ops[i];
-            if ((op.kind != OP_CONV && op.kind != OP_CONVT) || impl != UNET_IMPL_AUTO || op.out_level >= 0) continue;
-            ConvGeom cg = op_geom_of(op);
-            SrcDesc sd[2];
-            for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
-            if (op.kind == OP_CONV && conv_first_wgrad_mfma_supported(dtype, cg, sd, op.nsrc)) wz_off[i] = take(conv_first_wgrad_mfma_scratch_bytes(cg));
-            else if (op.kind == OP_CONV && wgrad_mfma[i]) { if (!mfma_conv_wgrad_direct(cg)) wz_off[i] = take(mfma_wgrad_scratch_bytes(cg, side_polite[i])); }
-            else if (op.kind == OP_CONVT && wgrad_mfma[i]) { if (!mfma_convt_wgrad_direct(cg)) wz_off[i] = take(mfma_convt_wgrad_scratch_bytes(cg)); }
+            const Wgrad w = conv[i].wgrad;
+            if (op.out_level >= 0 || (w != Wgrad::first_mfma && w != Wgrad::mfma)) continue;
+            const ConvGeom cg = op_geom_of(op);
+            if (w == Wgrad::first_mfma) wz_off[i] = take(conv_first_wgrad_mfma_scratch_bytes(cg));
+            else if (op.kind == OP_CONV) { if (!mfma_conv_wgrad_direct(cg)) wz_off[i] = take(mfma_wgrad_scratch_bytes(cg, side_polite[i])); }
+            else if (!mfma_convt_wgrad_direct(cg)) wz_off[i] = take(mfma_convt_wgrad_scratch_bytes(cg));
         }
         ws_bytes = off;
         // batched filter pack: one job per MFMA filter pack, sources as offsets into a flat parameter buffer
@@ -379,7 +344,7 @@ struct unet_plan {
                 j.bias_off = op.bias >= 0 ? j.slab_off + (long long)j.nsplit * j.n : -1;
                 j.db_off = op.bias >= 0 ? p_off[op.bias] : -1;
             } else {
-                j.nsplit = (op.cin == 1) ? conv_first_wgrad_splits(cg) : mfma_conv_wgrad_splits(cg, side_polite[i]);
+                j.nsplit = conv[i].wgrad == Wgrad::first_mfma ? conv_first_wgrad_splits(cg) : mfma_conv_wgrad_splits(cg, side_polite[i]);
                 j.n = (long long)27 * op.cin * op.cout;
                 j.bias_off = op.bias >= 0 ? j.slab_off + (long long)j.nsplit * j.n : -1;
                 j.db_off = op.bias >= 0 ? p_off[op.bias] : -1;
@@ -394,11 +359,11 @@ struct unet_plan {
         for (int which = 0; which < 2; ++which) {          // forward packs first, then the dgrad packs
             for (size_t i = 0; i < g.ops.size(); ++i) {
                 const Op& op = g.ops[i];
-                if ((op.kind != OP_CONV && op.kind != OP_CONVT) || !use_mfma[i]) continue;
+                if (!conv[i].mfma_fwd()) continue;
                 // first matrix-core op whose output is 16^3 voxels or smaller: its forward pack and the later ops' go into the second launch
                 if (which == 0 && pack_split_op < 0 && g.tensors[op.dst].voxels() <= (int64_t)16 * 16 * 16) { pack_split_op = (int)i; pack_split_blocks = pack_blocks; }
                 PackJob jb[2];
-                int n = op.kind == OP_CONV ? mfma_conv_pack_jobs(op_geom_of(op), dgrad_mfma[i] != 0, jb) : mfma_convt_pack_jobs(op_geom_of(op), jb);
+                int n = op.kind == OP_CONV ? mfma_conv_pack_jobs(op_geom_of(op), conv[i].dgrad == Dgrad::mfma, jb) : mfma_convt_pack_jobs(op_geom_of(op), jb);
                 if (which >= n) continue;
                 jb[which].src_off = p_off[op.weight];
                 jb[which].dst_off = (int64_t)(which == 0 ? wm_fwd[i] : wm_dgrad[i]);
@@ -453,14 +418,7 @@ struct Exec {
     void apply_view(int t) const {
         if (p.a_off[t] != SIZE_MAX) launch_apply_view(p.dtype, raw_src(t), ws + p.a_off[t], p.g.tensors[t].voxels(), s);
     }
-    ConvGeom geom(const Op& op) const {
-        const Tensor& a = p.g.tensors[op.src[0]];
-        const Tensor& o = p.g.tensors[op.dst];
-        ConvGeom g;
-        g.Cin = op.cin; g.Cout = op.cout; g.D = a.D; g.H = a.H; g.W = a.W; g.Do = o.D; g.Ho = o.H; g.Wo = o.W;
-        g.ks = op.ks; g.stride = op.stride;
-        return g;
-    }
+    ConvGeom geom(const Op& op) const { return p.op_geom_of(op); }
 
     // on_head(level): called right after the launches that produce results[level] (a fused forward + loss issues that level's loss there)
     void forward(const float* const* params, float* const* buffers, const float* x, float* const* outs, int mode,
@@ -483,9 +441,8 @@ struct Exec {
                 // training forward: the pack runs on the plan's side stream beside the input pack, the first conv (which reads the
                 // fp32 filter) and its norm; the first kernel that needs packed filters waits for it.  (Eval forwards stay on the
                 // caller's stream: they are re-entrant per workspace, the side stream and its events are per plan.)
-                static const bool no_side = getenv("UNET_NO_SIDE_STREAM") != nullptr;
                 const int njobs = (int)p.pack_jobs.size();
-                if (mode == 1 && p.side && !no_side && !g_prof) {
+                if (mode == 1 && p.side && !env().no_side_stream && !g_prof) {
                     HIP_OK(hipEventRecord(p.ev_fork, s));
                     HIP_OK(hipStreamWaitEvent(p.side, p.ev_fork, 0));
                     if (p.pack_split_op > 0 && p.pack_split_blocks > 0) {
@@ -533,79 +490,79 @@ struct Exec {
                     ConvGeom cg = geom(op);
                     float* wf = (float*)(ws + p.w_fwd[i]);
                     float* wd = (float*)(ws + p.w_dgrad[i]);
-                    if (p.use_mfma[i]) need_packs((int)i);
-                    if (op.kind == OP_CONV && p.use_mfma[i]) {
-                        if (!packed)
-                            launch_mfma_pack_conv_w(params[op.weight], ws + p.wm_fwd[i],
-                                                    (mode == 1 && p.dgrad_mfma[i]) ? ws + p.wm_dgrad[i] : nullptr, cg, s);
-                        if (mode == 1 && !p.dgrad_mfma[i] && !packs_current)
-                            launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, op.ks * op.ks * op.ks, s);
-                        const Tensor& T = g.tensors[op.dst];
-                        bool want_stats = T.norm >= 0 && !(g.norms[T.norm].batch && mode == 0);
-                        // the deep levels: split-K kernel, the norm layer behind the conv in its epilogue (statistics, running statistics,
-                        // activated copy: the OP_NORM that follows has nothing left to do)
-                        if (deep_on && deep_conv_applies(p.dtype, T.voxels(), op.cin, op.cout)) {
-                            DeepNormFwd nf;
-                            const bool fuse = T.norm >= 0 && p.a_off[op.dst] != SIZE_MAX;
-                            if (fuse) {
-                                const Norm& n = g.norms[T.norm];
-                                nf = {params[n.gamma], params[n.beta], n.eps, stat(T.norm), n.batch ? buffers[n.buffer] : nullptr,
-                                      n.batch ? buffers[n.buffer + 1] : nullptr, 0.1, (n.batch && mode == 0) ? 1 : 0, T.act, ws + p.a_off[op.dst]};
-                            }
-                            if (launch_deep_conv_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), fuse ? &nf : nullptr, deep(), s)) {
-                                if (fuse) fused_done[T.norm] = 1;
-                                break;
-                            }
+                    const int k3 = op.ks * op.ks * op.ks;
+                    const ConvChoice& c = p.conv[i];
+                    const Tensor& T = g.tensors[op.dst];
+                    const bool want_stats = T.norm >= 0 && !(g.norms[T.norm].batch && mode == 0);
+                    if (op.kind == OP_CONVT) {
+                        if (c.mfma_fwd()) {
+                            need_packs((int)i);
+                            if (!packed) launch_mfma_pack_convt_w(params[op.weight], ws + p.wm_fwd[i], mode == 1 ? ws + p.wm_dgrad[i] : nullptr, cg, s);
+                            if (!(deep_on && launch_deep_convt_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), deep(), s)))
+                                launch_mfma_convt_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), s);
+                            break;
                         }
-                        int rows = launch_mfma_conv_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst),
-                                                        want_stats ? partial() : nullptr, s);
-                        if (want_stats) fused_blocks[T.norm] = rows;
-                    } else if (op.kind == OP_CONV && p.impl == UNET_IMPL_AUTO && op.out_level >= 0 && head_supported(cg, op.nsrc)) {
-                        // a head: results[level] straight from the source tensor (the channels-last copy only if nobody asked for the level)
-                        float* o = outs[op.out_level];
-                        launch_head_fwd(p.dtype, cg, sd[0], params[op.weight], params[op.bias], o ? nullptr : tptr(op.dst), o, s);
-                    } else if (op.kind == OP_CONV && p.impl == UNET_IMPL_AUTO && op.out_level < 0 &&
-                               conv_first_mfma_supported(p.dtype, cg, sd, op.nsrc)) {
-                        const Tensor& T = g.tensors[op.dst];
-                        bool want_stats = T.norm >= 0 && !(g.norms[T.norm].batch && mode == 0);
-                        int rows = launch_conv_first_mfma(cg, sd, params[op.weight], params[op.bias], tptr(op.dst),
-                                                          want_stats ? partial() : nullptr, s);
-                        if (want_stats) fused_blocks[T.norm] = rows;
-                        // the fp32 [tap][cin][cout] copies are read by the direct dgrad only: not made when the input needs no gradient
-                        if (mode == 1 && !packs_current && g.tensors[op.src[0]].needs_grad)
-                            launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, op.ks * op.ks * op.ks, s);
-                    } else if (op.kind == OP_CONV && p.impl == UNET_IMPL_AUTO && op.out_level < 0 &&
-                               conv_first_f32_mfma_supported(p.dtype, cg, sd, op.nsrc)) {
-                        // fp32 engine, Cin = 1: the first conv on the fp32 matrix cores (filter read in torch layout), statistics in its epilogue
-                        const Tensor& T = g.tensors[op.dst];
-                        const bool want_stats = T.norm >= 0 && !(g.norms[T.norm].batch && mode == 0);
-                        const int rows = launch_conv_first_f32_mfma(cg, sd, params[op.weight], params[op.bias], (float*)tptr(op.dst),
-                                                                    want_stats ? (double*)partial() : nullptr, s);
-                        if (want_stats) { fused_blocks[T.norm] = rows; fused_dbl[T.norm] = 1; }
-                        if (mode == 1 && !packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, op.ks * op.ks * op.ks, s);
-                    } else if (op.kind == OP_CONV && p.impl == UNET_IMPL_AUTO && op.out_level < 0 &&
-                               conv_f32_mfma_supported(p.dtype, cg, sd, op.nsrc)) {
-                        // fp32 engine: the same IEEE fp32 products and sums as the VALU kernel below, on the fp32 matrix cores
-                        if (!packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, op.ks * op.ks * op.ks, s);
-                        const Tensor& T = g.tensors[op.dst];
-                        const bool want_stats = T.norm >= 0 && !(g.norms[T.norm].batch && mode == 0);
-                        const int rows = launch_conv_f32_mfma(cg, sd, op.nsrc, wf, params[op.bias], (float*)tptr(op.dst), s,
-                                                              want_stats ? (double*)partial() : nullptr);
-                        if (want_stats) { fused_blocks[T.norm] = rows; fused_dbl[T.norm] = 1; }
-                    } else if (op.kind == OP_CONV) {
-                        if (!packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, op.ks * op.ks * op.ks, s);
-                        launch_conv_fwd_direct(p.dtype, cg, sd, op.nsrc, wf, params[op.bias], tptr(op.dst),
-                                               op.out_level >= 0 ? outs[op.out_level] : nullptr, s);
-                    } else if (p.use_mfma[i]) {
-                        if (!packed) launch_mfma_pack_convt_w(params[op.weight], ws + p.wm_fwd[i], mode == 1 ? ws + p.wm_dgrad[i] : nullptr, cg, s);
-                        if (!(deep_on && launch_deep_convt_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), deep(), s)))
-                            launch_mfma_convt_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), s);
-                    } else {
                         if (!packs_current) launch_pack_convt_w(params[op.weight], wf, wd, op.cin, op.cout, s);
-                        if (p.impl == UNET_IMPL_AUTO && convt_f32_mfma_supported(p.dtype, cg, sd, op.nsrc))
-                            launch_convt_f32_mfma(cg, sd, wf, params[op.bias], (float*)tptr(op.dst), s);
-                        else
-                            launch_convt_fwd_direct(p.dtype, cg, sd, op.nsrc, wf, params[op.bias], tptr(op.dst), s);
+                        if (c.fwd == Fwd::f32_mfma) launch_convt_f32_mfma(cg, sd, wf, params[op.bias], (float*)tptr(op.dst), s);
+                        else launch_convt_fwd_direct(p.dtype, cg, sd, op.nsrc, wf, params[op.bias], tptr(op.dst), s);
+                        break;
+                    }
+                    float* const part = want_stats ? partial() : nullptr;
+                    int rows = 0;              // statistics partial rows the conv left in part
+                    switch (c.fwd) {
+                        case Fwd::deep:
+                        case Fwd::mfma:
+                            need_packs((int)i);
+                            if (!packed)
+                                launch_mfma_pack_conv_w(params[op.weight], ws + p.wm_fwd[i],
+                                                        (mode == 1 && c.dgrad == Dgrad::mfma) ? ws + p.wm_dgrad[i] : nullptr, cg, s);
+                            if (mode == 1 && c.dgrad != Dgrad::mfma && !packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
+                            // the deep levels: split-K kernel, the norm layer behind the conv in its epilogue (statistics, running statistics,
+                            // activated copy: the OP_NORM that follows has nothing left to do)
+                            if (c.fwd == Fwd::deep && deep_on) {
+                                DeepNormFwd nf;
+                                const bool fuse = T.norm >= 0 && p.a_off[op.dst] != SIZE_MAX;
+                                if (fuse) {
+                                    const Norm& n = g.norms[T.norm];
+                                    nf = {params[n.gamma], params[n.beta], n.eps, stat(T.norm), n.batch ? buffers[n.buffer] : nullptr,
+                                          n.batch ? buffers[n.buffer + 1] : nullptr, 0.1, (n.batch && mode == 0) ? 1 : 0, T.act, ws + p.a_off[op.dst]};
+                                }
+                                if (launch_deep_conv_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), fuse ? &nf : nullptr, deep(), s)) {
+                                    if (fuse) fused_done[T.norm] = 1;
+                                    break;
+                                }
+                            }
+                            rows = launch_mfma_conv_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), part, s);
+                            break;
+                        case Fwd::head:   // results[level] straight from the source tensor (the channels-last copy only if nobody asked for the level)
+                            launch_head_fwd(p.dtype, cg, sd[0], params[op.weight], params[op.bias], outs[op.out_level] ? nullptr : tptr(op.dst),
+                                            outs[op.out_level], s);
+                            break;
+                        case Fwd::first_mfma:
+                            rows = launch_conv_first_mfma(cg, sd, params[op.weight], params[op.bias], tptr(op.dst), part, s);
+                            // the fp32 [tap][cin][cout] copies are read by the direct dgrad only: not made when the input needs no gradient
+                            if (mode == 1 && !packs_current && g.tensors[op.src[0]].needs_grad)
+                                launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
+                            break;
+                        case Fwd::first_f32_mfma:
+                            // fp32 engine, Cin = 1: the first conv on the fp32 matrix cores (filter read in torch layout), statistics in its epilogue
+                            rows = launch_conv_first_f32_mfma(cg, sd, params[op.weight], params[op.bias], (float*)tptr(op.dst), (double*)part, s);
+                            if (mode == 1 && !packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
+                            break;
+                        case Fwd::f32_mfma:
+                            // fp32 engine: the same IEEE fp32 products and sums as the VALU kernel below, on the fp32 matrix cores
+                            if (!packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
+                            rows = launch_conv_f32_mfma(cg, sd, op.nsrc, wf, params[op.bias], (float*)tptr(op.dst), s, (double*)part);
+                            break;
+                        case Fwd::direct:
+                            if (!packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
+                            launch_conv_fwd_direct(p.dtype, cg, sd, op.nsrc, wf, params[op.bias], tptr(op.dst),
+                                                   op.out_level >= 0 ? outs[op.out_level] : nullptr, s);
+                            break;
+                    }
+                    if (want_stats) {   // (the fp32 matrix-core convs leave fp64 rows)
+                        fused_blocks[T.norm] = rows;
+                        fused_dbl[T.norm] = c.fwd == Fwd::first_f32_mfma || c.fwd == Fwd::f32_mfma;
                     }
                     break;
                 }
@@ -732,8 +689,7 @@ struct Exec {
         };
         // sb: where the parameter-gradient kernels go.  fork() orders them after everything issued so far on the caller's stream
         // (dL/d(raw output) of the layer is final); the join at the end orders the caller's stream after them.
-        static const bool no_side = getenv("UNET_NO_SIDE_STREAM") != nullptr;
-        const hipStream_t sb = (p.side && !no_side && !g_prof) ? p.side : s;
+        const hipStream_t sb = (p.side && !env().no_side_stream && !g_prof) ? p.side : s;
         auto fork = [&]() {
             if (sb == s) return;
             HIP_OK(hipEventRecord(p.ev_fork, s));
@@ -768,37 +724,42 @@ struct Exec {
             const int t = op.dst;
             SrcDesc sd[2] = {src(op.src[0]), op.nsrc > 1 ? src(op.src[1]) : SrcDesc()};
             ConvGeom cg = geom(op);
+            // the stride-2 convs above 32^3 (wgrad_on_main, choose_polite): the kernel and its slab sum on the caller's stream, the slab in
+            // the op's own region (the shared scratch is the side stream's)
+            const bool on_main = op.kind == OP_CONV && p.wgrad_on_main[i] && p.wz_off[i] != SIZE_MAX;
+            const bool defer = gflat && p.wz_job_of_op[i] >= 0 && !on_main;   // slab only: summed by the batched reduce below
             {   // the op's own bracket closes before flush_wz opens the batched reduce's (they would nest and count the reduce twice)
             ProfScope pw(i, UNET_PROF_WGRAD, sb);
-            if (op.kind == OP_CONV) {
-                if (p.impl == UNET_IMPL_AUTO && conv_first_wgrad_mfma_supported(p.dtype, cg, sd, op.nsrc)) {
-                    const bool defer = gflat && p.wz_job_of_op[i] >= 0;
+            switch (p.conv[i].wgrad) {
+                case Wgrad::first_mfma:
                     launch_conv_first_wgrad_mfma(cg, sd, gptr(t), gparams[op.weight], gparams[op.bias],
                                                  ws + (defer ? p.wz_off[i] : p.wgrad_off), sb, defer);
-                    if (defer) { wz_ran[p.wz_job_of_op[i]] = 1; ++wz_pending; }
-                } else if (p.wgrad_mfma[i] && p.wgrad_on_main[i] && p.wz_off[i] != SIZE_MAX) {
-                    // experiment: kernel and its slab sum on the caller's stream (slab in the op's own region: the shared scratch is the side stream's)
-                    launch_mfma_conv_wgrad(cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wz_off[i], s, false, 0);
-                } else if (p.wgrad_mfma[i]) {
-                    const bool defer = gflat && p.wz_job_of_op[i] >= 0;   // slab only: summed by the batched reduce below
-                    launch_mfma_conv_wgrad(cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias],
-                                           ws + (p.wz_off[i] != SIZE_MAX ? p.wz_off[i] : p.wgrad_off), sb, defer, p.side_polite[i]);
-                    if (defer) { wz_ran[p.wz_job_of_op[i]] = 1; ++wz_pending; }
-                }
-                else if (p.impl == UNET_IMPL_AUTO && wgrad_f32_mfma_supported(p.dtype, cg, sd, op.nsrc))
+                    break;
+                case Wgrad::mfma:
+                    if (op.kind == OP_CONVT)
+                        launch_mfma_convt_wgrad(cg, sd, gptr(t), gparams[op.weight], ws + (defer ? p.wz_off[i] : p.wgrad_off), sb, defer, gparams[op.bias],
+                                                p.side_polite[i]);
+                    else if (on_main)
+                        launch_mfma_conv_wgrad(cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wz_off[i], s, false, 0);
+                    else
+                        launch_mfma_conv_wgrad(cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias],
+                                               ws + (p.wz_off[i] != SIZE_MAX ? p.wz_off[i] : p.wgrad_off), sb, defer, p.side_polite[i]);
+                    break;
+                case Wgrad::f32_mfma:
                     launch_wgrad_f32_mfma(cg, sd, op.nsrc, (const float*)gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-                else if (p.impl == UNET_IMPL_AUTO && wgrad_small_supported(cg, op.nsrc))
+                    break;
+                case Wgrad::small:
                     launch_conv_wgrad_small(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-                else
-                    launch_conv_wgrad_direct(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-            } else if (p.wgrad_mfma[i]) {
-                const bool defer = gflat && p.wz_job_of_op[i] >= 0;
-                launch_mfma_convt_wgrad(cg, sd, gptr(t), gparams[op.weight], ws + (defer ? p.wz_off[i] : p.wgrad_off), sb, defer, gparams[op.bias], p.side_polite[i]);
-                if (defer) { wz_ran[p.wz_job_of_op[i]] = 1; ++wz_pending; }
-            } else {
-                launch_convt_wgrad_direct(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
+                    break;
+                case Wgrad::direct:
+                    if (op.kind == OP_CONVT)
+                        launch_convt_wgrad_direct(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
+                    else
+                        launch_conv_wgrad_direct(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
+                    break;
             }
             }
+            if (defer) { wz_ran[p.wz_job_of_op[i]] = 1; ++wz_pending; }
             if (wz_pending >= 3) flush_wz(sb);      // (every layer and one flush at the end both measured slower: profiles/r06 A/Bs)
         };
         // The backward starts at full resolution, where the caller's stream is bandwidth-bound, and then spends a long stretch in the
@@ -834,7 +795,7 @@ struct Exec {
             int t = op.dst;
             if ((op.kind == OP_CONV) && op.out_level >= 0) {
                 if (!(grad_outs && grad_outs[op.out_level])) continue;
-                if (p.impl == UNET_IMPL_AUTO && head_supported(geom(op), op.nsrc)) {
+                if (p.conv[i].fwd == Fwd::head) {
                     // fused head backward: dL/dW, dL/db and dL/d(source view) in one pass over (source, dL/dresults[level])
                     DstGrad dgh = dst_of(op.src[0]);
                     ProfScope ph(dry ? -2 : i, UNET_PROF_OTHER, s);
@@ -857,12 +818,9 @@ struct Exec {
             // The network's first conv with a norm behind it: dL/d(raw output) is only read by its weight gradient (the input needs no
             // gradient), which applies the norm backward's element-wise pass itself (NormBwdFuse) -- see the OP_CONV case below
             bool first_fused = false;
-            if (!dry && op.kind == OP_CONV && p.impl == UNET_IMPL_AUTO && p.dtype == UNET_DTYPE_BF16 && g.tensors[t].norm >= 0 && op.nsrc == 1 &&
-                !g.tensors[op.src[0]].needs_grad && sb != s && p.wz_off[i] != SIZE_MAX && g.tensors[t].C % 8 == 0) {
-                static const bool off = getenv("UNET_NO_FIRST_WGRAD_FUSE") != nullptr;
-                SrcDesc sd0 = src(op.src[0]);
-                first_fused = !off && conv_first_wgrad_mfma_supported(p.dtype, geom(op), &sd0, 1);
-            }
+            if (!dry && p.conv[i].wgrad == Wgrad::first_mfma && g.tensors[t].norm >= 0 && !g.tensors[op.src[0]].needs_grad && sb != s &&
+                p.wz_off[i] != SIZE_MAX && g.tensors[t].C % 8 == 0)
+                first_fused = !env().no_first_wgrad_fuse;
             if (!dry) { ProfScope ps(i, UNET_PROF_NORM_BWD, s); view_backward(t, params, gparams, first_fused); }
             switch (op.kind) {
                 case OP_CONV:
@@ -876,8 +834,7 @@ struct Exec {
                     // The network's first conv (its input needs no gradient: nothing follows on the caller's stream) -- its weight gradient is
                     // the last kernel of the backward whichever stream it is on; on the caller's stream it starts without waiting for a fork
                     // and its reduce is not behind the side stream's queue.  Slab in the op's own region (the shared scratch is the side stream's).
-                    if (!dry && !any && sb != s && op.kind == OP_CONV && p.impl == UNET_IMPL_AUTO && p.wz_off[i] != SIZE_MAX &&
-                        conv_first_wgrad_mfma_supported(p.dtype, cg, sd, op.nsrc)) {
+                    if (!dry && !any && sb != s && p.conv[i].wgrad == Wgrad::first_mfma && p.wz_off[i] != SIZE_MAX) {
                         ProfScope pw(i, UNET_PROF_WGRAD, s);
                         const Tensor& To = g.tensors[t];
                         NormBwdFuse nf = {tptr(t), first_fused ? stat(To.norm) : nullptr, first_fused ? coef(To.norm) : nullptr, To.act};
@@ -901,39 +858,17 @@ struct Exec {
                             if ((int)pending.size() >= fork_every || sb == s || vox >= hold_below) issue_pending();
                         }
                     }
-                    if (op.kind == OP_CONV) {
-                        ProfScope pd(i, UNET_PROF_DGRAD, s);
-                        if (!dry && (any && p.dgrad_mfma[i])) {
+                    ProfScope pd(i, UNET_PROF_DGRAD, s);
+                    if (!dry && any) switch (p.conv[i].dgrad) {
+                        case Dgrad::mfma: {
                             // The source is a norm layer's view read by this conv alone: its gradient is complete when this dgrad
                             // has written it, so the statistics pass of that norm's backward (a second read of the gradient and of the
                             // raw tensor) moves into the dgrad's epilogue where the kernel has one (k_mfma_conv_z16).  The rows wait in
                             // partial(): the next thing the caller's stream runs is that tensor's view_backward.
-                            const int ts = op.src[0];
-                            const Tensor& Ts = g.tensors[ts];
-                            BnBwdStats bn = {tptr(ts), Ts.norm >= 0 ? stat(Ts.norm) : nullptr, partial(), Ts.act, Ts.C};
                             // With several consumers the one with the lowest op index writes last -- accumulating -- and sees the complete
                             // gradient: for the skip tensors that is the stride-2 conv, whose dgrad (k_s2_scatter) fetches the old gradient
                             // and the raw tensor by LDS-DMA and has the epilogue too.  (Stride-1 kernels only take it when they WRITE.)
-                            const bool can = op.nsrc == 1 && Ts.norm >= 0 && p.first_consumer[ts] == i && p.dtype == UNET_DTYPE_BF16;
-                            int rows = 0, served = 0;
-                            if (deep_on) {      // the deep levels: split-K kernel; as the last writer of a norm layer's view it runs that norm's backward too
-                                DeepNormBwd nb;
-                                if (can) {
-                                    const Norm& n = g.norms[Ts.norm];
-                                    nb = {tptr(ts), stat(Ts.norm), params[n.gamma], coef(Ts.norm), gparams[n.gamma], gparams[n.beta], Ts.act};
-                                }
-                                served = launch_deep_conv_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr, deep(), s);
-                                if (served == 2) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_done[ws].push_back(ts); }
-                            }
-                            if (!served) rows = launch_mfma_conv_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, s, can ? &bn : nullptr);
-                            if (rows > 0) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_pending[ws] = {ts, rows}; }
-                        }
-                        else if (!dry && any && p.impl == UNET_IMPL_AUTO && conv_f32_mfma_dgrad_supported(p.dtype, cg, dg, op.nsrc))
-                            launch_conv_f32_mfma_dgrad(cg, (const float*)gptr(t), wd, dg, op.nsrc, s);
-                        else if (!dry && (any)) launch_conv_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
-                    } else {
-                        ProfScope pd(i, UNET_PROF_DGRAD, s);
-                        if (!dry && (any && p.dgrad_mfma[i])) {
+                            // The deep levels' split-K kernels, as the last writer of a norm layer's view, run that norm's whole backward.
                             const int ts = op.src[0];
                             const Tensor& Ts = g.tensors[ts];
                             const bool can = op.nsrc == 1 && Ts.norm >= 0 && p.first_consumer[ts] == i && p.dtype == UNET_DTYPE_BF16;
@@ -942,13 +877,27 @@ struct Exec {
                                 const Norm& n = g.norms[Ts.norm];
                                 nb = {tptr(ts), stat(Ts.norm), params[n.gamma], coef(Ts.norm), gparams[n.gamma], gparams[n.beta], Ts.act};
                             }
-                            int norm_done = 0;
-                            if (deep_on && launch_deep_convt_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr, deep(), &norm_done, s)) {
-                                if (norm_done) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_done[ws].push_back(ts); }
-                            } else
-                                launch_mfma_convt_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, s);
+                            if (op.kind == OP_CONVT) {
+                                int norm_done = 0;
+                                if (deep_on && launch_deep_convt_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr, deep(), &norm_done, s)) {
+                                    if (norm_done) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_done[ws].push_back(ts); }
+                                } else
+                                    launch_mfma_convt_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, s);
+                                break;
+                            }
+                            BnBwdStats bn = {tptr(ts), Ts.norm >= 0 ? stat(Ts.norm) : nullptr, partial(), Ts.act, Ts.C};
+                            int rows = 0;
+                            const int served = deep_on ? launch_deep_conv_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr, deep(), s) : 0;
+                            if (served == 2) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_done[ws].push_back(ts); }
+                            if (!served) rows = launch_mfma_conv_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, s, can ? &bn : nullptr);
+                            if (rows > 0) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_pending[ws] = {ts, rows}; }
+                            break;
                         }
-                        else if (!dry && (any)) launch_convt_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
+                        case Dgrad::f32_mfma: launch_conv_f32_mfma_dgrad(cg, (const float*)gptr(t), wd, dg, op.nsrc, s); break;
+                        case Dgrad::direct:
+                            if (op.kind == OP_CONVT) launch_convt_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
+                            else launch_conv_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
+                            break;
                     }
                     if (any) mark(op);
                     break;
@@ -1373,8 +1322,7 @@ int unet_forward_loss_mode(const unet_plan* p, const float* const* params, float
         LossRun lr(p, outs, target, cost_mask, collapse_before, grad_outs, losses_out, loss_scratch);
         DeviceGuard dg(p->device);
         hipStream_t s = (hipStream_t)stream;
-        static const bool no_side = getenv("UNET_NO_SIDE_STREAM") != nullptr;
-        const bool side = p->side && !no_side && !g_prof;
+        const bool side = p->side && !env().no_side_stream && !g_prof;
         Exec ex(*p, workspace, stream);
         if (!side) {
             ex.forward(params, buffers, x, outs, mode);
@@ -1506,9 +1454,15 @@ int unet_sgd_step(const unet_plan* p, float* params, float* grads, float* mom, f
 }
 
 // ---- single-op surface ----
+// The scratch of one call: the fp32 filter copies ([forward | dgrad], `half` bytes each), the bf16 MFMA filter pack, the statistics partials
+struct OpScratch {
+    size_t half, pack, partials;   // byte offsets of the dgrad copy, the pack and the partials
+    OpScratch(int cin, int cout)
+        : half(align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4)), pack(2 * half),
+          partials(pack + align_up((size_t)160 * round_up(cin, 32) * round_up(cout, 32))) {}   // largest pack: stride-2 dgrad, 128 B per Cin*Cout
+};
 int unet_op_scratch_bytes(int cin, int cout, int D, int H, int W, size_t* bytes) {
-    size_t b = 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4) + 4096 +
-               align_up((size_t)160 * round_up(cin, 32) * round_up(cout, 32));   // largest MFMA filter pack: stride-2 dgrad, 128 B per Cin*Cout
+    size_t b = OpScratch(cin, cout).partials + 4096;
     if (D > 0 && H > 0 && W > 0) {   // statistics partials of unet_op_conv3d_fwd_fused, behind the filter packs
         int64_t S = (int64_t)D * H * W;
         size_t blocks = (size_t)(S / 32 + 4096);   // >= any conv tile count (>= 64 voxels per tile, ragged edges) and >= stats_blocks(S)
@@ -1523,14 +1477,9 @@ int unet_op_scratch_bytes(int cin, int cout, int D, int H, int W, size_t* bytes)
         if (w > b) b = w;
     }
     if (cin % 16 == 0 && cout % 16 == 0 && D > 0 && H > 0 && W > 0) {
-        ConvGeom gf;   // fp32 matrix-core wgrad: per-wave slabs (<= 64 MB) + the bias partials
-        gf.Cin = cin; gf.Cout = cout; gf.D = gf.Do = D; gf.H = gf.Ho = H; gf.W = gf.Wo = W; gf.ks = 3; gf.stride = 1;
-        size_t wf32 = wgrad_f32_mfma_scratch_bytes(gf);
-        if (wf32 > b) b = wf32;
-    }
-    if (cin % 16 == 0 && cout % 16 == 0 && D > 0 && H > 0 && W > 0) {
-        ConvGeom g;   // MFMA wgrad slabs: stride-1 geometry has the most tiles
+        ConvGeom g;   // matrix-core wgrad slabs: stride-1 geometry has the most tiles
         g.Cin = cin; g.Cout = cout; g.D = g.Do = D; g.H = g.Ho = H; g.W = g.Wo = W; g.ks = 3; g.stride = 1;
+        b = std::max(b, wgrad_f32_mfma_scratch_bytes(g));   // fp32: per-wave slabs (<= 64 MB) + the bias partials
         size_t w = std::max(mfma_wgrad_scratch_bytes(g, 0), mfma_wgrad_scratch_bytes(g, 1));   // unet_op_conv3d_bwd_weight may launch politely (UNET_OP_POLITE): more slab rows
         if (w > b) b = w;
         g.stride = 2; g.Do = (D - 1) / 2 + 1; g.Ho = (H - 1) / 2 + 1; g.Wo = (W - 1) / 2 + 1;
@@ -1555,8 +1504,7 @@ static ConvGeom op_geom(int cin, int cout, int D, int H, int W, int ks, int stri
     return g;
 }
 static void op_pack(const float* w, int cin, int cout, int k3, bool transposed, void* scratch, float** wf, float** wd, hipStream_t s) {
-    size_t half = align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4);
-    *wf = (float*)scratch; *wd = (float*)((char*)scratch + half);
+    *wf = (float*)scratch; *wd = (float*)((char*)scratch + OpScratch(cin, cout).half);
     if (transposed) launch_pack_convt_w(w, *wf, *wd, cin, cout, s);
     else launch_pack_conv_w(w, *wf, *wd, cin, cout, k3, s);
 }
@@ -1589,17 +1537,18 @@ int unet_op_conv3d_fwd(int dtype, int impl, const void* x, const float* w, const
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
         float *wf, *wd;
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        if (impl == UNET_IMPL_AUTO && mfma_conv_fwd_supported(dtype, g, &sd, 1)) {
-            void* wm = (char*)scratch + 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4);
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
+        if (c.mfma_fwd()) {
+            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
             launch_mfma_pack_conv_w(w, wm, nullptr, g, s);
             if (!launch_deep_conv_fwd(g, &sd, 1, wm, b, y, nullptr, op_deep(), s)) launch_mfma_conv_fwd(g, &sd, 1, wm, b, y, nullptr, s);
-        } else if (impl == UNET_IMPL_AUTO && conv_first_mfma_supported(dtype, g, &sd, 1)) {
+        } else if (c.fwd == Fwd::first_mfma) {
             launch_conv_first_mfma(g, &sd, w, b, y, nullptr, s);
-        } else if (impl == UNET_IMPL_AUTO && conv_first_f32_mfma_supported(dtype, g, &sd, 1)) {
+        } else if (c.fwd == Fwd::first_f32_mfma) {
             (void)launch_conv_first_f32_mfma(g, &sd, w, b, (float*)y, nullptr, s);
         } else {
             op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
-            if (impl == UNET_IMPL_AUTO && conv_f32_mfma_supported(dtype, g, &sd, 1)) (void)launch_conv_f32_mfma(g, &sd, 1, wf, b, (float*)y, s);
+            if (c.fwd == Fwd::f32_mfma) (void)launch_conv_f32_mfma(g, &sd, 1, wf, b, (float*)y, s);
             else launch_conv_fwd_direct(dtype, g, &sd, 1, wf, b, y, nullptr, s);
         }
     })
@@ -1613,20 +1562,20 @@ int unet_op_conv3d_fwd_fused(int dtype, int impl, const void* x, const float* sc
         float *wf, *wd;
         SrcDesc sd; sd.ptr = x; sd.C = cin; sd.scale = scale; sd.shift = shift; sd.act = act;
         int64_t So = (int64_t)g.Do * g.Ho * g.Wo;
-        // partials live behind the filter packs
-        size_t poff = 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4) + align_up((size_t)160 * round_up(cin, 32) * round_up(cout, 32));
-        float* part = (float*)((char*)scratch + poff);
-        if (impl == UNET_IMPL_AUTO && mfma_conv_fwd_supported(dtype, g, &sd, 1)) {
-            void* wm = (char*)scratch + 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4);
+        const OpScratch L(cin, cout);
+        float* part = (float*)((char*)scratch + L.partials);
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
+        if (c.mfma_fwd()) {
+            void* wm = (char*)scratch + L.pack;
             launch_mfma_pack_conv_w(w, wm, nullptr, g, s);
             int rows = launch_mfma_conv_fwd(g, &sd, 1, wm, b, y, stats ? part : nullptr, s);
             if (stats) launch_stats_sum(part, rows, cout, stats, s);
-        } else if (impl == UNET_IMPL_AUTO && conv_first_mfma_supported(dtype, g, &sd, 1)) {
+        } else if (c.fwd == Fwd::first_mfma) {
             int rows = launch_conv_first_mfma(g, &sd, w, b, y, stats ? part : nullptr, s);
             if (stats) launch_stats_sum(part, rows, cout, stats, s);
-        } else {
+        } else {   // (the fp32 first conv too: this entry runs it on the direct kernel + a statistics pass)
             op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
-            if (impl == UNET_IMPL_AUTO && conv_f32_mfma_supported(dtype, g, &sd, 1)) {
+            if (c.fwd == Fwd::f32_mfma) {
                 // the fp32 matrix-core conv leaves its own fp64 statistics rows (one per tile)
                 const int rows = launch_conv_f32_mfma(g, &sd, 1, wf, b, (float*)y, s, stats ? (double*)part : nullptr);
                 if (stats) launch_stats_sum(part, rows, cout, stats, s, true);
@@ -1645,7 +1594,8 @@ int unet_op_conv3d_pack(int dtype, const float* w, void* wpacked, int cin, int c
     OP_TRY({
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
         SrcDesc sd; sd.C = cin;
-        if (!mfma_conv_fwd_supported(dtype, g, &sd, 1)) throw std::runtime_error("unet_op_conv3d_pack: shape not covered by the MFMA kernels");
+        if (!choose_conv(dtype, UNET_IMPL_AUTO, g, &sd, 1, false, false).mfma_fwd())
+            throw std::runtime_error("unet_op_conv3d_pack: shape not covered by the MFMA kernels");
         launch_mfma_pack_conv_w(w, wpacked, nullptr, g, (hipStream_t)stream);
     })
 }
@@ -1654,7 +1604,8 @@ int unet_op_conv3d_fwd_packed(int dtype, const void* x, const void* wpacked, con
     OP_TRY({
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        if (!mfma_conv_fwd_supported(dtype, g, &sd, 1)) throw std::runtime_error("unet_op_conv3d_fwd_packed: shape not covered by the MFMA kernels");
+        if (!choose_conv(dtype, UNET_IMPL_AUTO, g, &sd, 1, false, false).mfma_fwd())
+            throw std::runtime_error("unet_op_conv3d_fwd_packed: shape not covered by the MFMA kernels");
         launch_mfma_conv_fwd(g, &sd, 1, wpacked, b, y, stats_partials, (hipStream_t)stream);
     })
 }
@@ -1666,13 +1617,14 @@ int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w,
         float *wf, *wd;
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = 0;
         SrcDesc sd; sd.C = cin;
-        if (impl == UNET_IMPL_AUTO && mfma_conv_dgrad_supported(dtype, g, &sd, 1)) {
-            void* wm = (char*)scratch + 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4);
+        const Dgrad c = choose_conv(dtype, impl, g, &sd, 1, false, false).dgrad;
+        if (c == Dgrad::mfma) {
+            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
             launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
             if (!launch_deep_conv_dgrad(g, dy, wm, &d, 1, nullptr, op_deep(), s)) launch_mfma_conv_dgrad(g, dy, wm, &d, 1, s);
         } else {
             op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
-            if (impl == UNET_IMPL_AUTO && conv_f32_mfma_dgrad_supported(dtype, g, &d, 1)) launch_conv_f32_mfma_dgrad(g, (const float*)dy, wd, &d, 1, s);
+            if (c == Dgrad::f32_mfma) launch_conv_f32_mfma_dgrad(g, (const float*)dy, wd, &d, 1, s);
             else launch_conv_dgrad_direct(dtype, g, dy, wd, &d, 1, s);
         }
     })
@@ -1680,21 +1632,16 @@ int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w,
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D,
                               int H, int W, int ks, int stride, void* scratch, void* stream) {
     OP_TRY({
+        hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        // UNET_OP_POLITE=1: the launch configuration the engine gives this layer's gradient on its side stream (one 4-wave block per
-        // CU, single (ca, cb) pairs) -- for micro-benchmarks and counter collection of the kernel as the train step runs it
-        static const bool op_polite = getenv("UNET_OP_POLITE") != nullptr;
-        if (impl == UNET_IMPL_AUTO && mfma_wgrad_supported(dtype, g, &sd, 1))
-            launch_mfma_conv_wgrad(g, &sd, 1, dy, dw, db, scratch, (hipStream_t)stream, false, op_polite ? 1 : 0);
-        else if (impl == UNET_IMPL_AUTO && conv_first_wgrad_mfma_supported(dtype, g, &sd, 1))
-            launch_conv_first_wgrad_mfma(g, &sd, dy, dw, db, scratch, (hipStream_t)stream);
-        else if (impl == UNET_IMPL_AUTO && wgrad_f32_mfma_supported(dtype, g, &sd, 1))
-            launch_wgrad_f32_mfma(g, &sd, 1, (const float*)dy, dw, db, scratch, (hipStream_t)stream);
-        else if (impl == UNET_IMPL_AUTO && wgrad_small_supported(g, 1))
-            launch_conv_wgrad_small(dtype, g, &sd, 1, dy, dw, db, scratch, (hipStream_t)stream);
-        else
-            launch_conv_wgrad_direct(dtype, g, &sd, 1, dy, dw, db, nullptr, (hipStream_t)stream);
+        switch (choose_conv(dtype, impl, g, &sd, 1, false, false).wgrad) {
+            case Wgrad::first_mfma: launch_conv_first_wgrad_mfma(g, &sd, dy, dw, db, scratch, s); break;
+            case Wgrad::mfma: launch_mfma_conv_wgrad(g, &sd, 1, dy, dw, db, scratch, s, false, env().op_polite ? 1 : 0); break;
+            case Wgrad::f32_mfma: launch_wgrad_f32_mfma(g, &sd, 1, (const float*)dy, dw, db, scratch, s); break;
+            case Wgrad::small: launch_conv_wgrad_small(dtype, g, &sd, 1, dy, dw, db, scratch, s); break;
+            case Wgrad::direct: launch_conv_wgrad_direct(dtype, g, &sd, 1, dy, dw, db, nullptr, s);
+        }
     })
 }
 int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D, int H,
@@ -1704,13 +1651,14 @@ int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const 
         ConvGeom g = op_geom(cin, cout, D, H, W, 2, 2, true);
         float *wf, *wd;
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        if (impl == UNET_IMPL_AUTO && mfma_convt_supported(dtype, g, &sd, 1)) {
-            void* wm = (char*)scratch + 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4);
+        const Fwd f = choose_conv(dtype, impl, g, &sd, 1, false, true).fwd;
+        if (f == Fwd::mfma) {
+            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
             launch_mfma_pack_convt_w(w, wm, nullptr, g, s);
             if (!launch_deep_convt_fwd(g, &sd, 1, wm, b, y, op_deep(), s)) launch_mfma_convt_fwd(g, &sd, 1, wm, b, y, s);
         } else {
             op_pack(w, cin, cout, 8, true, scratch, &wf, &wd, s);
-            if (impl == UNET_IMPL_AUTO && convt_f32_mfma_supported(dtype, g, &sd, 1)) launch_convt_f32_mfma(g, &sd, wf, b, (float*)y, s);
+            if (f == Fwd::f32_mfma) launch_convt_f32_mfma(g, &sd, wf, b, (float*)y, s);
             else launch_convt_fwd_direct(dtype, g, &sd, 1, wf, b, y, s);
         }
     })
@@ -1723,8 +1671,8 @@ int unet_op_convt_bwd_data(int dtype, int impl, const void* dy, const float* w, 
         float *wf, *wd;
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = 0;
         SrcDesc sd; sd.C = cin;
-        if (impl == UNET_IMPL_AUTO && mfma_convt_supported(dtype, g, &sd, 1)) {
-            void* wm = (char*)scratch + 2 * align_up((size_t)27 * round_up(cin, 8) * round_up(cout, 8) * 4);
+        if (choose_conv(dtype, impl, g, &sd, 1, false, true).dgrad == Dgrad::mfma) {
+            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
             launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
             if (!launch_deep_convt_dgrad(g, dy, wm, &d, 1, nullptr, op_deep(), nullptr, s)) launch_mfma_convt_dgrad(g, dy, wm, &d, 1, s);
         } else {
@@ -1738,11 +1686,10 @@ int unet_op_convt_bwd_weight(int dtype, int impl, const void* x, const void* dy,
     OP_TRY({
         ConvGeom g = op_geom(cin, cout, D, H, W, 2, 2, true);
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        if (impl == UNET_IMPL_AUTO && mfma_convt_wgrad_supported(dtype, g, &sd, 1)) {
+        if (choose_conv(dtype, impl, g, &sd, 1, false, true).wgrad == Wgrad::mfma)
             launch_mfma_convt_wgrad(g, &sd, dy, dw, scratch, (hipStream_t)stream, false, db);
-        } else {
+        else
             launch_convt_wgrad_direct(dtype, g, &sd, 1, dy, dw, db, nullptr, (hipStream_t)stream);
-        }
     })
 }
 int unet_op_pack_ndhwc(int dtype, const float* x, void* y, int C, int64_t S, void* stream) {
