@@ -200,6 +200,25 @@ int unet_op_conv3d_fwd_packed(int dtype, const void* x, const void* wpacked, con
                               int cin, int cout, int D, int H, int W, int ks, int stride, void* stream);
 int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w, void* dx, int cin, int cout, int D, int H,
                             int W, int ks, int stride, void* scratch, void* stream);
+/* A conv k3 (stride 1 or 2) and the norm layer + activation behind it, bf16 only, run as the engine runs that layer (on the deep levels
+ * one split-K launch with the norm in its epilogue, else the conv and the norm's own launches).  Sources x0 [.., cin0] and x1
+ * [.., cin1] (NULL, cin1 = 0: one source) are read as their channel concatenation; w [cout][cin0 + cin1][3][3][3].  Writes the raw
+ * output y, the activated copy y_act = act(y * scale + shift) and stat fp32 [4][cout] = {mean, rstd, scale = gamma * rstd,
+ * shift = beta - mean * scale}.  use_running = 0: statistics of y as stored (biased variance, eps), and rm / rv (may be NULL)
+ * updated with momentum and the unbiased variance; use_running = 1 (eval BatchNorm): mean = rm, var = rv, rm / rv unchanged.
+ * scratch: unet_op_scratch_bytes(cin0 + cin1, cout, D, H, W) bytes. */
+int unet_op_conv3d_fwd_norm(const void* x0, const void* x1, int cin0, int cin1, const float* w, const float* b, const float* gamma,
+                            const float* beta, double eps, float* rm, float* rv, double momentum, int use_running, int act, void* y,
+                            void* y_act, float* stat, int cout, int D, int H, int W, int stride, void* scratch, void* stream);
+/* The backward of that pair seen from the consumer: the dgrad of a conv k3 s1 (transposed = 0) or of a conv_trans k2 s2
+ * (transposed = 1; w [cin][cout][2][2][2]) from dy [.., cout] into dx [D][H][W][cin], the view of a norm layer's raw tensor u with
+ * statistics stat [4][cin] (as unet_op_conv3d_fwd_norm leaves them), then that norm's backward, bf16 only.  accumulate: dx holds an
+ * older dL/d(view) that is added first.  On return dx holds dL/d(raw u), coef fp32 [3][cin] = {gamma * rstd, mean(dv),
+ * mean(dv * xhat)}, and dgamma += sum dv * xhat, dbeta += sum dv (dv = dL/d(view) * act').
+ * scratch: unet_op_scratch_bytes(cout, cin, D, H, W) bytes (its statistics rows are per channel of dx). */
+int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w, void* dx, int accumulate, const void* u, const float* stat,
+                                 const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin, int cout, int D, int H,
+                                 int W, void* scratch, void* stream);
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout,
                               int D, int H, int W, int ks, int stride, void* scratch, void* stream);
 int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D,

@@ -128,12 +128,72 @@ def test_hand_counted_kernels_passed_the_build_time_assembly_check():
     import glob
     import json
     recs = sorted(glob.glob(os.path.join(ROOT, "unet-studio_amd", "asm_loads_check_*.json")))
-    assert {os.path.basename(r) for r in recs} >= {"asm_loads_check_conv_z.json", "asm_loads_check_wgrad_z.json", "asm_loads_check_conv_zdma.json"}
+    assert {os.path.basename(r) for r in recs} >= {"asm_loads_check_conv_z.json", "asm_loads_check_wgrad_z.json", "asm_loads_check_conv_zdma.json",
+                                                   "asm_loads_check_deep.json"}
     for r in recs:
         d = json.load(open(r))
         assert d["ok"] and d["kernels"] and all(k["ok"] for k in d["kernels"]), r
     dma = json.load(open(os.path.join(ROOT, "unet-studio_amd", "asm_loads_check_conv_zdma.json")))
     assert {k["planes_ahead"] for k in dma["kernels"]} == {5}
+    # k_deep_conv: every instantiation (3 forward kinds + 3 dgrad kinds; plain / forward-norm / backward-norm epilogues; 1 or 2 row
+    # tiles) drains its sc1 partial-tile stores before the barrier in front of the split-K ticket
+    deep = json.load(open(os.path.join(ROOT, "unet-studio_amd", "asm_loads_check_deep.json")))
+    assert deep["checked"] == "deep" and deep["ok"] and len(deep["kernels"]) == 22
+    assert all(k["ticket_atomics"] == 1 and k["publish_stores"] >= 2 and k["sc1_loads_after_ticket"] > 0 for k in deep["kernels"])
+
+
+_DEEP_FRAGMENT = """
+_ZN4unet11k_deep_convILi1ELi3ELi1ELb0ELi1ELi1EEEvNS_8DeepArgsE: ; @k
+	ds_write_b128 v4, v[8:11]
+	s_barrier
+	v_pk_add_f32 v[6:7], v[6:7], v[24:25]
+	global_store_dwordx2 v[40:41], v[6:7], off sc1
+	global_store_dwordx2 v[40:41], v[8:9], off offset:8 {plain}
+{wait}
+	s_barrier
+	s_and_saveexec_b64 s[0:1], vcc
+	s_cbranch_execz .LBB0_193
+	global_atomic_add v2, v2, v3, s[2:3] sc0
+.LBB0_193:
+	s_or_b64 exec, exec, s[0:1]
+	global_load_dwordx2 v[52:53], v[2:3], off sc1
+	s_endpgm
+.Lfunc_end0:
+amdhsa.kernels:
+  - .agpr_count:     0
+    .private_segment_fixed_size: 0
+    .sgpr_spill_count: 0
+    .symbol:         _ZN4unet11k_deep_convILi1ELi3ELi1ELb0ELi1ELi1EEEvNS_8DeepArgsE.kd
+    .vgpr_count:     64
+    .vgpr_spill_count: 0
+"""
+
+
+@pytest.mark.parametrize("wait,plain,why", [("", "sc1", "no s_waitcnt vmcnt(0)"), ("\ts_waitcnt vmcnt(0)", "sc1", None),
+                                            ("\ts_waitcnt vmcnt(0) lgkmcnt(0)", "sc1", None), ("\ts_waitcnt vmcnt(1)", "sc1", "no s_waitcnt vmcnt(0)"),
+                                            ("\ts_waitcnt vmcnt(0)", "", "without sc1")])
+def test_deep_ticket_check_rejects_a_ticket_taken_before_the_partial_tiles_have_landed(tmp_path, wait, plain, why):
+    """tools/check_asm_loads.py deep on hand-written fragments shaped like k_deep_conv's hand-off (no hipcc run): sc1 stores ->
+    s_barrier -> the ticket's atomic is rejected (s_barrier waits for no counter); with s_waitcnt vmcnt(0) between the last store and
+    the barrier it is accepted; a partial-tile store without sc1 or a wait that leaves a store in flight is rejected."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("check_asm_loads", os.path.join(ROOT, "unet-studio_amd", "csrc", "tools", "check_asm_loads.py"))
+    K = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(K)
+    asm = tmp_path / "frag.s"
+    asm.write_text(_DEEP_FRAGMENT.format(wait=wait, plain=plain))
+    out = tmp_path / "frag.json"
+    ok = why is None
+    if ok:
+        K.main("deep", str(asm), str(out))
+    else:
+        with pytest.raises(SystemExit):
+            K.main("deep", str(asm), str(out))
+    rec = json.load(open(out))
+    assert rec["ok"] == ok and len(rec["kernels"]) == 1 and rec["kernels"][0]["publish_stores"] == 2
+    errs = rec["kernels"][0]["errors"]
+    assert (not errs) if ok else (len(errs) == 1 and why in errs[0]), errs
 
 
 def test_unet_hpp_keeps_the_reference_class_surface():

@@ -17,14 +17,16 @@ done
 [ -f ../asm_loads_check_conv_zdma.json ] || todo="$todo check:kernels_mfma_conv_z16.hip"
 [ -f ../asm_loads_check_s2dma.json ] || todo="$todo check:kernels_mfma_s2.hip"
 [ -f ../asm_loads_check_wgrad_zd.json ] || todo="$todo check:kernels_mfma_wgrad_zd.hip"
+[ -f ../asm_loads_check_deep.json ] || todo="$todo check:kernels_mfma_deep.hip"
 todo_src=$(echo $todo | tr ' ' '\n' | grep -v '^check:' | tr '\n' ' ')
 if [ -n "$(echo $todo_src | tr -d ' ')" ]; then
     echo $todo_src | tr ' ' '\n' | xargs -P 6 -I{} sh -c 'f={}; hipcc '"$FLAGS"' -c "$f" -o build/${f%.*}.o'
 fi
 # k_mfma_conv_z and k_mfma_wgrad_z wait for inline-asm loads with hand-counted vmcnt values: check the emitted code whenever
 # their file was rebuilt (tools/check_asm_loads.py: no scratch, the expected memory operations, no instruction touching a load's
-# registers while it is in flight); the result and the toolchain it was validated with are recorded next to the library
-for pair in conv_z:kernels_mfma_conv wgrad_z:kernels_mfma_wgrad_z conv_zdma:kernels_mfma_conv_z16 s2dma:kernels_mfma_s2 wgrad_zd:kernels_mfma_wgrad_zd; do
+# registers while it is in flight; k_deep_conv: every wave drains its sc1 partial-tile stores before the barrier in front of the
+# split-K ticket); the result and the toolchain it was validated with are recorded next to the library
+for pair in conv_z:kernels_mfma_conv wgrad_z:kernels_mfma_wgrad_z conv_zdma:kernels_mfma_conv_z16 s2dma:kernels_mfma_s2 wgrad_zd:kernels_mfma_wgrad_zd deep:kernels_mfma_deep; do
     which=${pair%%:*}; f=${pair##*:}
     case " $todo " in *" $f.hip "*|*" check:$f.hip "*)
         hipcc $FLAGS --cuda-device-only -S $f.hip -o build/$f.s 2>/dev/null

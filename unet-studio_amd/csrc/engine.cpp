@@ -378,6 +378,42 @@ struct unet_plan {
 
 namespace {
 
+// The separate launches of a norm layer, shared by the executor (OP_NORM, view_backward) and the single-op surface.  Forward: the
+// statistics from `rows` partial rows in `partial` (0: a statistics pass over `raw` first; dbl: fp64 rows) or, in eval mode, the
+// running ones; then the activated copy into act_out (may be nullptr), in one launch with the finalize where the rows are few.
+void norm_fwd_passes(int dtype, const void* raw, int C, int64_t S, float* partial, int rows, bool dbl, bool eval, const float* gamma,
+                     const float* beta, double eps, float* stat, float* rm, float* rv, int act, void* act_out, hipStream_t s) {
+    if (eval) launch_norm_eval(C, gamma, beta, rm, rv, eps, stat, s);
+    else {
+        if (!rows) {
+            launch_stats_partial(dtype, raw, C, S, partial, s);
+            rows = stats_blocks(S);
+            dbl = dtype == UNET_DTYPE_F32;
+        }
+        // few partial rows (32^3 and deeper): finalize + activated copy in one launch
+        if (!dbl && act_out && launch_norm_finalize_apply(dtype, partial, rows, C, S, gamma, beta, eps, stat, rm, rv, 0.1, raw, act, act_out, s))
+            return;
+        launch_norm_finalize(partial, rows, C, S, gamma, beta, eps, stat, rm, rv, 0.1, s, dbl);
+    }
+    if (act_out) {
+        SrcDesc d;
+        d.ptr = raw; d.C = C; d.act = act; d.scale = stat + 2 * C; d.shift = stat + 3 * C;
+        launch_apply_view(dtype, d, act_out, S, s);
+    }
+}
+// Backward: g holds dL/d(view of u) and becomes dL/d(raw u); coef and the affine gradients (+=) are written.  rows > 0: the statistics
+// rows a dgrad epilogue left in `partial`.  no_apply: stop after the finalize (the element-wise pass is fused into the consumer).
+void norm_bwd_passes(int dtype, void* g, const void* u, int C, int64_t S, const float* stat, int act, const float* gamma, float* coef,
+                     float* dgamma, float* dbeta, float* partial, int rows, bool no_apply, hipStream_t s) {
+    if (rows <= 0) {
+        launch_norm_bwd_partial(dtype, g, u, C, S, stat, act, partial, s);
+        rows = stats_blocks(S);
+    }
+    if (!no_apply && launch_norm_bwd_finalize_apply(dtype, partial, rows, C, S, gamma, stat, coef, dgamma, dbeta, g, u, act, s)) return;
+    launch_norm_bwd_finalize(partial, rows, C, S, gamma, stat, coef, dgamma, dbeta, s, dtype == UNET_DTYPE_F32);
+    if (!no_apply) launch_norm_bwd_apply(dtype, g, u, C, S, stat, coef, act, s);
+}
+
 struct Exec {
     const unet_plan& p;
     char* ws;
@@ -570,29 +606,11 @@ struct Exec {
                     const Norm& n = g.norms[op.norm];
                     const Tensor& T = g.tensors[n.tensor];
                     if (fused_done[op.norm]) break;
-                    if (n.batch && mode == 0) {
-                        launch_norm_eval(n.C, params[n.gamma], params[n.beta], buffers[n.buffer], buffers[n.buffer + 1], n.eps,
-                                         stat(op.norm), s);
-                    } else {
-                        int nb = fused_blocks[op.norm];
-                        bool dbl = fused_dbl[op.norm] != 0;   // fp32 tensors leave fp64 block partials (k_stats_partial, k_conv_f32_mfma)
-                        if (!nb) {
-                            launch_stats_partial(p.dtype, tptr(n.tensor), n.C, T.voxels(), partial(), s);
-                            nb = stats_blocks(T.voxels());
-                            dbl = p.dtype == UNET_DTYPE_F32;
-                        }
-                        // few partial rows (32^3 and deeper): finalize + activated copy in one launch
-                        if (!dbl && p.a_off[n.tensor] != SIZE_MAX &&
-                            launch_norm_finalize_apply(p.dtype, partial(), nb, n.C, T.voxels(), params[n.gamma], params[n.beta], n.eps,
-                                                       stat(op.norm), n.batch ? buffers[n.buffer] : nullptr,
-                                                       n.batch ? buffers[n.buffer + 1] : nullptr, 0.1, tptr(n.tensor), T.act,
-                                                       ws + p.a_off[n.tensor], s))
-                            break;
-                        launch_norm_finalize(partial(), nb, n.C, T.voxels(), params[n.gamma], params[n.beta],
-                                             n.eps, stat(op.norm), n.batch ? buffers[n.buffer] : nullptr,
-                                             n.batch ? buffers[n.buffer + 1] : nullptr, 0.1, s, dbl);
-                    }
-                    apply_view(n.tensor);
+                    // (fp32 tensors leave fp64 block partials: k_stats_partial, k_conv_f32_mfma)
+                    norm_fwd_passes(p.dtype, tptr(n.tensor), n.C, T.voxels(), partial(), fused_blocks[op.norm], fused_dbl[op.norm] != 0,
+                                    n.batch && mode == 0, params[n.gamma], params[n.beta], n.eps, stat(op.norm),
+                                    n.batch ? buffers[n.buffer] : nullptr, n.batch ? buffers[n.buffer + 1] : nullptr, T.act,
+                                    p.a_off[n.tensor] != SIZE_MAX ? ws + p.a_off[n.tensor] : nullptr, s);
                     break;
                 }
                 case OP_MATERIALIZE: {
@@ -634,7 +652,7 @@ struct Exec {
         if (T.norm >= 0) {
             const Norm& n = p.g.norms[T.norm];
             // the statistics pass, unless the dgrad that produced this gradient already left its partial rows (bn_rows_tensor == t)
-            int rows = stats_blocks(T.voxels()), have = 0;
+            int have = 0;
             {
                 std::lock_guard<std::mutex> lk(p.bn_mu);
                 auto d = p.bn_done.find(ws);
@@ -645,15 +663,8 @@ struct Exec {
                 auto it = p.bn_pending.find(ws);
                 if (it != p.bn_pending.end()) { if (it->second.first == t) have = it->second.second; p.bn_pending.erase(it); }
             }
-            if (have > 0) rows = have;
-            else launch_norm_bwd_partial(p.dtype, gptr(t), tptr(t), T.C, T.voxels(), stat(T.norm), T.act, partial(), s);
-            if (!no_apply && launch_norm_bwd_finalize_apply(p.dtype, partial(), rows, T.C, T.voxels(), params[n.gamma], stat(T.norm),
-                                                            coef(T.norm), gparams[n.gamma], gparams[n.beta], gptr(t), tptr(t), T.act, s))
-                return;
-            launch_norm_bwd_finalize(partial(), rows, T.C, T.voxels(), params[n.gamma], stat(T.norm), coef(T.norm),
-                                     gparams[n.gamma], gparams[n.beta], s, p.dtype == UNET_DTYPE_F32);
-            if (no_apply) return;
-            launch_norm_bwd_apply(p.dtype, gptr(t), tptr(t), T.C, T.voxels(), stat(T.norm), coef(T.norm), T.act, s);
+            norm_bwd_passes(p.dtype, gptr(t), tptr(t), T.C, T.voxels(), stat(T.norm), T.act, params[n.gamma], coef(T.norm),
+                            gparams[n.gamma], gparams[n.beta], partial(), have, no_apply, s);
         } else if (T.act != ACT_NONE) {
             launch_act_bwd(p.dtype, gptr(t), tptr(t), T.act, T.numel(), s);
         }
@@ -1627,6 +1638,67 @@ int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w,
             if (c == Dgrad::f32_mfma) launch_conv_f32_mfma_dgrad(g, (const float*)dy, wd, &d, 1, s);
             else launch_conv_dgrad_direct(dtype, g, dy, wd, &d, 1, s);
         }
+    })
+}
+// A conv k3 and the norm + activation behind it, bf16, as the executor runs that layer: on the deep levels the split-K kernel with
+// the norm in its epilogue (DEEP_FWD_NORM), else the MFMA conv with its statistics rows and the norm's separate launches.
+int unet_op_conv3d_fwd_norm(const void* x0, const void* x1, int cin0, int cin1, const float* w, const float* b, const float* gamma,
+                            const float* beta, double eps, float* rm, float* rv, double momentum, int use_running, int act, void* y,
+                            void* y_act, float* stat, int cout, int D, int H, int W, int stride, void* scratch, void* stream) {
+    OP_TRY({
+        hipStream_t s = (hipStream_t)stream;
+        const int cin = cin0 + cin1, nsrc = x1 ? 2 : 1;
+        ConvGeom g = op_geom(cin, cout, D, H, W, 3, stride, false);
+        SrcDesc sd[2];
+        sd[0].ptr = x0; sd[0].C = cin0;
+        if (x1) { sd[1].ptr = x1; sd[1].C = cin1; }
+        const ConvChoice c = choose_conv(UNET_DTYPE_BF16, UNET_IMPL_AUTO, g, sd, nsrc, false, false);
+        if (!c.mfma_fwd() || (use_running && (!rm || !rv)))
+            throw std::runtime_error("unet_op_conv3d_fwd_norm: shape not covered by the MFMA kernels, or eval mode without running statistics");
+        const OpScratch L(cin, cout);
+        void* wm = (char*)scratch + L.pack;
+        float* part = (float*)((char*)scratch + L.partials);
+        launch_mfma_pack_conv_w(w, wm, nullptr, g, s);
+        const DeepNormFwd nf = {gamma, beta, eps, stat, rm, rv, momentum, use_running ? 1 : 0, act, y_act};
+        if (!(c.fwd == Fwd::deep && launch_deep_conv_fwd(g, sd, nsrc, wm, b, y, &nf, op_deep(), s))) {
+            const int rows = launch_mfma_conv_fwd(g, sd, nsrc, wm, b, y, use_running ? nullptr : part, s);
+            norm_fwd_passes(UNET_DTYPE_BF16, y, cout, (int64_t)g.Do * g.Ho * g.Wo, part, rows, false, use_running != 0, gamma, beta, eps,
+                            stat, rm, rv, act, y_act, s);
+        }
+    })
+}
+// The dgrad of a conv k3 s1 (or of a conv_trans k2 s2: transposed) into the view of a norm layer's tensor u, then that norm's backward
+// as the executor runs it: on the deep levels in the split-K kernel's epilogue (DEEP_BWD_NORM), else the dgrad (with the statistics
+// epilogue where the kernel has one) and the norm's separate backward launches.
+int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w, void* dx, int accumulate, const void* u, const float* stat,
+                                 const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin, int cout, int D, int H,
+                                 int W, void* scratch, void* stream) {
+    OP_TRY({
+        hipStream_t s = (hipStream_t)stream;
+        ConvGeom g = op_geom(cin, cout, D, H, W, transposed ? 2 : 3, transposed ? 2 : 1, transposed != 0);
+        SrcDesc sd; sd.C = cin;
+        if (choose_conv(UNET_DTYPE_BF16, UNET_IMPL_AUTO, g, &sd, 1, false, transposed != 0).dgrad != Dgrad::mfma)
+            throw std::runtime_error("unet_op_conv3d_bwd_data_norm: shape not covered by the MFMA kernels");
+        const OpScratch L(cin, cout);
+        void* wm = (char*)scratch + L.pack;
+        float* part = (float*)((char*)scratch + L.partials);
+        DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = accumulate ? 1 : 0;
+        const DeepNormBwd nb = {u, stat, gamma, coef, dgamma, dbeta, act};
+        bool done = false;
+        int rows = 0;
+        if (transposed) {
+            launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
+            int norm_done = 0;
+            if (launch_deep_convt_dgrad(g, dy, wm, &d, 1, &nb, op_deep(), &norm_done, s)) done = norm_done != 0;
+            else launch_mfma_convt_dgrad(g, dy, wm, &d, 1, s);
+        } else {
+            launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
+            const BnBwdStats bn = {u, stat, part, act, cin};
+            const int served = launch_deep_conv_dgrad(g, dy, wm, &d, 1, &nb, op_deep(), s);
+            done = served == 2;
+            if (!served) rows = launch_mfma_conv_dgrad(g, dy, wm, &d, 1, s, &bn);
+        }
+        if (!done) norm_bwd_passes(UNET_DTYPE_BF16, dx, u, cin, (int64_t)D * H * W, stat, act, gamma, coef, dgamma, dbeta, part, rows, false, s);
     })
 }
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D,

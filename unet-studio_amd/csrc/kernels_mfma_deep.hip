@@ -428,7 +428,10 @@ __global__ void __launch_bounds__(256) k_deep_conv(DeepArgs a) {
 #pragma unroll
     for (int n = 0; n < NTW; ++n)
         deep_publish(a.part + (((size_t)(ksp * NTT + ng * NTW + n) * a.Vpad + mw) * 16 + gq * 4), o[n]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // this wave's stores have completed (no cache maintenance at this scope)
+    // every wave waits until its sc1 stores have reached the memory side before the barrier that lets lane 0 take the ticket: s_barrier
+    // waits for no counter, and a ticket taken with partial tiles still in flight lets the last arriver sum stale ones (no cache
+    // maintenance: the stores write through, the last arriver reads with sc1 loads).  tools/check_asm_loads.py deep checks the .s.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
         const int cidx = EPI == DEEP_PLAIN ? mg * NG + ng : ng, target = EPI == DEEP_PLAIN ? a.ksplit : a.MG * a.ksplit;

@@ -3,6 +3,7 @@
 (kernels_mfma_conv.hip) and every instantiation of k_mfma_wgrad_z (kernels_mfma_wgrad_z.hip) -- run by build.sh on the device
 assembly of those files:   check_asm_loads.py conv_z <asm> <json>   |   check_asm_loads.py wgrad_z <asm> <json>   |   check_asm_loads.py conv_zdma <asm> <json>
 (conv_zdma: k_mfma_conv_z16 / k_mfma_conv_z32 of kernels_mfma_conv_z16.hip, LDS-DMA planes: see scan_dma)
+(deep: every k_deep_conv of kernels_mfma_deep.hip, the split-K ticket hand-off and no scratch: see scan_deep_ticket)
 
 What follows describes the conv_z rules; wgrad_z is checked the same way with its own expectations (per instantiation: the
 inline-asm loads come in groups of NL = loads per step, every hand-placed wait is vmcnt(NL) or vmcnt(0), no compiler-generated
@@ -304,11 +305,82 @@ def scan_dma_cfg(body):
     return errors, st
 
 
+def function_bodies(text, match):
+    """[(symbol, lines)] of every kernel whose mangled name contains `match`, from its label to its .Lfunc_end (a kernel with early
+    returns has several s_endpgm)"""
+    out = []
+    for m in re.finditer(r"\n(_Z[A-Za-z0-9_]*%s[A-Za-z0-9_]*):" % re.escape(match), text):
+        end = text.find(".Lfunc_end", m.end())
+        out.append((m.group(1), text[m.start():end if end >= 0 else len(text)].split("\n")))
+    return out
+
+
+def scan_deep_ticket(body):
+    """k_deep_conv (kernels_mfma_deep.hip): the split-K hand-off of a partial tile to the block that draws the last ticket
+    (cdna_hip_programming.md, "In-launch split-K reduction" item 2, sc1 form).  Checked in layout order, which the check requires to
+    be the order of execution over the stretch (no branch or label inside it):
+      the stretch = from the first global store after the block's last s_barrier before the ticket's barrier, through that barrier,
+      to the ticket's global_atomic_add (the kernel's only one);
+      (a) every global / buffer store in the stretch carries sc1 (written through to the memory side: the last arriver may sit on
+          another XCD);
+      (b) between the stretch's last store and the ticket's s_barrier there is an s_waitcnt vmcnt(0): s_barrier waits for no counter,
+          so without it the ticket can be visible while the wave's partial-tile stores are still in flight;
+      (c) the last arriver reads the partial tiles with sc1 loads (deep_fetch<true>, no acquire fence): some are there after the
+          ticket (counted; the plain loads after it read bytes no other block writes in the launch: bias, statistics, gamma, the
+          old gradient, the raw tensor).
+    No scratch memory (rule 1 in the form of the LDS-DMA checks: no VGPR spills, no private segment, no scratch_* instruction;
+    SGPR spills go to VGPR lanes, not to memory, and are recorded only)."""
+    ins = []
+    for line in body:
+        t = line.split(";")[0].strip()
+        if not t or (t[0] == "." and not t.endswith(":")):
+            continue
+        ins.append(t)
+    errors = []
+    atom = [i for i, t in enumerate(ins) if t.split()[0].startswith("global_atomic_add")]
+    st = {"ticket_atomics": len(atom)}
+    if len(atom) != 1:
+        errors.append("expected exactly one ticket global_atomic_add, found %d" % len(atom))
+        return errors, st
+    a = atom[0]
+    bar = max([i for i in range(a) if ins[i] == "s_barrier"] or [-1])
+    prev = max([i for i in range(bar) if ins[i] == "s_barrier"] or [-1]) if bar >= 0 else -1
+    if bar < 0:
+        errors.append("no s_barrier before the ticket")
+        return errors, st
+    stores_to_memory = lambda t: t.split()[0].startswith(("global_store", "buffer_store", "flat_store"))
+    stores = [i for i in range(prev + 1, bar) if stores_to_memory(ins[i])]
+    st["publish_stores"] = len(stores)
+    if not stores:
+        errors.append("no partial-tile store before the ticket's s_barrier")
+        return errors, st
+    for i in range(stores[0], bar):
+        op = ins[i].split()[0]
+        if ins[i].endswith(":") or op.startswith("s_cbranch") or op == "s_branch" or op == "s_setpc_b64":
+            errors.append("control flow inside the publish stretch (the check reads it in layout order): %s" % ins[i])
+            break
+    for i in stores:
+        if not re.search(r"\bsc1\b", ins[i]):
+            errors.append("partial-tile store without sc1: %s" % ins[i])
+    if not any(ins[i].startswith("s_waitcnt") and re.search(r"vmcnt\(0\)", ins[i]) for i in range(stores[-1] + 1, bar)):
+        errors.append("no s_waitcnt vmcnt(0) between the last partial-tile store and the ticket's s_barrier: the ticket can be "
+                      "taken while partial tiles are in flight")
+    after = ins[a + 1:]
+    st["sc1_loads_after_ticket"] = sum(1 for t in after if t.startswith("global_load") and re.search(r"\bsc1\b", t))
+    if not st["sc1_loads_after_ticket"]:
+        errors.append("no sc1 load after the ticket: the last arriver does not read the partial tiles from the memory side")
+    return errors, st
+
+
 def main(which, path, out_json=None):
     text = open(path).read()
     ver = subprocess.run(["hipcc", "--version"], capture_output=True, text=True).stdout.strip().split("\n")
     recs, failed = [], False
-    if which == "conv_z":
+    if which == "deep":
+        # kernels_mfma_deep.hip: no hand-counted loads; the ticket hand-off of the split-K partial tiles (scan_deep_ticket) and no scratch
+        bodies = function_bodies(text, "k_deep_conv")
+        mode = "deep"
+    elif which == "conv_z":
         bodies = kernel_bodies(text, "k_mfma_conv_zE")
         mode = "consume"
     elif which == "conv_zdma":
@@ -329,7 +401,14 @@ def main(which, path, out_json=None):
         sys.exit("check_asm_loads: no %s kernel found in %s" % (which, path))
     for sym, body in bodies:
         meta = metadata(text, sym)
-        if mode == "dma":
+        if mode == "deep":
+            errors, st = scan_deep_ticket(body)
+            errors += ["scratch instruction: %s" % l.strip() for l in body if l.strip().startswith("scratch_")][:1]
+            for key in (".vgpr_spill_count", ".private_segment_fixed_size"):
+                if meta.get(key) != 0:
+                    errors.append("%s = %s (must be 0)" % (key, meta.get(key)))
+            st.update({"asm_loads": 0, "sgpr_spills_to_vgpr_lanes": meta.get(".sgpr_spill_count")})
+        elif mode == "dma":
             errors, st = scan_dma_cfg(body) if which in ("s2dma", "wgrad_zd") else scan_dma(body)     # (spills outside the hand-counted steps are harmless here: the steps are checked instruction by instruction)
             st.update({"asm_loads": st.get("dma_pieces_per_step", 0), "buffer_store_dwordx2": st.get("stores_per_step", 0)})
         else:
@@ -337,7 +416,9 @@ def main(which, path, out_json=None):
             for key in (".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size"):
                 if meta.get(key) != 0:
                     errors.append("%s = %s (must be 0)" % (key, meta.get(key)))
-        if mode == "dma":
+        if mode == "deep":
+            pass
+        elif mode == "dma":
             if which in ("s2dma", "wgrad_zd") and (meta.get(".vgpr_spill_count") or meta.get(".private_segment_fixed_size")):
                 errors.append("scratch in use: vgpr spills %s, private segment %s" % (meta.get(".vgpr_spill_count"), meta.get(".private_segment_fixed_size")))
         elif which == "conv_z":
@@ -371,7 +452,10 @@ def main(which, path, out_json=None):
         for r in recs:
             for e in r["errors"][:12]:
                 print("   %s: %s" % (r["kernel"][-40:], e), file=sys.stderr)
-        print("   (UNET_NO_CONV_Z=1 / UNET_NO_WGRAD_Z=1 select the halo-tile kernels instead; fix the kernel or the counts before shipping)", file=sys.stderr)
+        if which == "deep":
+            print("   (UNET_NO_DEEP_KERNELS=1 selects the halo-tile kernels and the separate norm launches instead; fix the hand-off before shipping)", file=sys.stderr)
+        else:
+            print("   (UNET_NO_CONV_Z=1 / UNET_NO_WGRAD_Z=1 select the halo-tile kernels instead; fix the kernel or the counts before shipping)", file=sys.stderr)
         sys.exit(1)
     print("check_asm_loads: %s ok (%s; %s)" % (which, ", ".join("%s VGPRs / %d asm loads" % (r["vgpr_count"], r["asm_loads"]) for r in recs), ver[0] if ver else "?"))
 
