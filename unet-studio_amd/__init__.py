@@ -16,6 +16,8 @@ from . import qc  # noqa: F401  (the module: qc.qc() is the reference's qc(), qc
 from .qc import QcStat, calculate_qc, qc_counts, run_qc  # noqa: F401
 from . import feed  # noqa: F401  (the module: feed.EXPORTS the symbols of include/unet_feed.h)
 from .feed import TrainingFeed  # noqa: F401
+from . import postproc  # noqa: F401  (the module: postproc.EXPORTS the symbols of include/unet_postproc.h)
+from .postproc import parse_chain, run_postproc  # noqa: F401
 
 
 def save_to_file(model, file_name):

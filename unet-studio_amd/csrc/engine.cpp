@@ -1922,4 +1922,73 @@ int unet_feed_schedule(uint64_t seed, int batch_size, int n_template, int n_subj
     return 0;
 }
 
+// ---- inference post-processing chain (include/unet_postproc.h) ----
+static const char* pp_class_error(int out_c, int64_t voxels) {
+    if (out_c < 2) return "unet_postproc: out_c must be at least 2 (channel 0 is the background)";
+    if (out_c - 1 > 65535) return "unet_postproc: more than 65535 foreground classes do not fit a uint16 label";
+    if (voxels <= 0) return "unet_postproc: voxels must be positive";
+    return nullptr;
+}
+static const char* pp_volume_error(int w, int h, int d, int n_planes, void* scratch, size_t scratch_bytes) {
+    if (w <= 0 || h <= 0 || d <= 0) return "unet_postproc: volume dimensions must be positive";
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31) || d > 65535 || h > 4 * 65535)
+        return "unet_postproc: volume beyond 2^31 voxels, 65535 slices or 4 x 65535 rows";
+    if (n_planes < 0 || n_planes > 65535) return "unet_postproc: n_planes must be in [0, 65535]";
+    if (!scratch) return "unet_postproc: null scratch";
+    if (scratch_bytes < postproc_scratch_bytes(n_planes, (int64_t)w * h * d))
+        return "unet_postproc: scratch too small (see unet_postproc_scratch_bytes)";
+    return nullptr;
+}
+static int pp_run(const void* any, void* stream, const std::function<void(hipStream_t)>& f) {
+    OP_TRY({
+        hipPointerAttribute_t at;
+        HIP_OK(hipPointerGetAttributes(&at, any));
+        DeviceGuard guard(at.device);
+        f((hipStream_t)stream);
+    })
+}
+int unet_postproc_scratch_bytes(int out_c, int64_t voxels, size_t* bytes) {
+    if (const char* e = pp_class_error(out_c, voxels)) return fail(e);
+    if (!bytes) return fail("unet_postproc_scratch_bytes: null output");
+    *bytes = postproc_scratch_bytes(out_c - 1, voxels);
+    return 0;
+}
+int unet_postproc_softmax(const float* logits, int out_c, int64_t voxels, float threshold, float* label_prob, float* fg_prob,
+                          uint16_t* label, void* stream) {
+    if (const char* e = pp_class_error(out_c, voxels)) return fail(e);
+    if (!logits) return fail("unet_postproc_softmax: null logits");
+    if (!label_prob && !fg_prob && !label) return fail("unet_postproc_softmax: no output wanted");
+    return pp_run(logits, stream, [&](hipStream_t s) {
+        launch_postproc_softmax(logits, out_c, voxels, threshold, label_prob, fg_prob, label, s);
+    });
+}
+int unet_postproc_argmax_planes(const float* label_prob, int n_planes, int64_t voxels, const float* fg_prob, float threshold,
+                                uint16_t* label, void* stream) {
+    if (const char* e = pp_class_error(n_planes + 1, voxels)) return fail(e);
+    if (!label_prob || !fg_prob || !label) return fail("unet_postproc_argmax_planes: null device pointer");
+    return pp_run(label_prob, stream, [&](hipStream_t s) {
+        launch_postproc_argmax_planes(label_prob, n_planes, voxels, fg_prob, threshold, label, s);
+    });
+}
+int unet_postproc_defragment(int w, int h, int d, int each, float threshold, double size_ratio, float* fg_prob, float* label_prob,
+                             int n_planes, uint16_t* label, void* scratch, size_t scratch_bytes, void* stream) {
+    if (const char* e = pp_volume_error(w, h, d, each ? n_planes : 1, scratch, scratch_bytes)) return fail(e);
+    if (n_planes < 0 || n_planes > 65535) return fail("unet_postproc: n_planes must be in [0, 65535]");
+    if (each && (!label_prob || n_planes < 1)) return fail("unet_postproc_defragment: defragment_each needs label_prob planes");
+    if (!each && !fg_prob) return fail("unet_postproc_defragment: defragment needs fg_prob (create_mask)");
+    if (label_prob && n_planes < 1 && !each) return fail("unet_postproc_defragment: label_prob given with no planes");
+    if (!(size_ratio == size_ratio)) return fail("unet_postproc_defragment: size_ratio is NaN");
+    return pp_run(each ? label_prob : fg_prob, stream, [&](hipStream_t s) {
+        launch_postproc_defragment(w, h, d, each, threshold, size_ratio, fg_prob, each ? label_prob : (n_planes ? label_prob : nullptr),
+                                   n_planes, each ? nullptr : label, scratch, s);
+    });
+}
+int unet_postproc_plane_op(int op, float param, int w, int h, int d, float* label_prob, int n_planes, void* scratch,
+                           size_t scratch_bytes, void* stream) {
+    if (op < UNET_PP_UPPER_THRESHOLD || op > UNET_PP_SMOOTH) return fail("unet_postproc_plane_op: unknown op " + std::to_string(op));
+    if (const char* e = pp_volume_error(w, h, d, n_planes, scratch, scratch_bytes)) return fail(e);
+    if (!label_prob || n_planes < 1) return fail("unet_postproc_plane_op: no label_prob planes");
+    return pp_run(label_prob, stream, [&](hipStream_t s) { launch_postproc_plane_op(op, param, w, h, d, label_prob, n_planes, scratch, s); });
+}
+
 }  // extern "C"

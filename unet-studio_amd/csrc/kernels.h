@@ -8,6 +8,7 @@
 #include "../../include/unet_augment.h"
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
+#include "../../include/unet_postproc.h"
 #include "../../include/unet_qc.h"
 
 namespace unet {
@@ -322,5 +323,13 @@ void launch_feed_label_max(const float* label, int64_t S, int* out_max, void* sc
 void launch_feed_prepare(const float* image0, float* label, int64_t S, int normalize, int shift, int* label_max, void* scratch,
                          hipStream_t s);
 void launch_feed_target(const float* label, int64_t S, int normalize, int64_t* target, void* scratch, hipStream_t s);
+
+// kernels_postproc.hip: the inference post-processing chain (include/unet_postproc.h)
+size_t postproc_scratch_bytes(int planes, int64_t S);
+void launch_postproc_softmax(const float* logits, int C, int64_t S, float thr, float* lp, float* fg, uint16_t* lab, hipStream_t s);
+void launch_postproc_argmax_planes(const float* lp, int np, int64_t S, const float* fg, float thr, uint16_t* lab, hipStream_t s);
+void launch_postproc_defragment(int W, int H, int D, int each, float thr, double ratio, float* fg, float* lp, int np, uint16_t* lab,
+                                void* scratch, hipStream_t s);
+void launch_postproc_plane_op(int op, float t, int W, int H, int D, float* lp, int np, void* scratch, hipStream_t s);
 
 }  // namespace unet

@@ -21,6 +21,7 @@
 #include <string>
 
 #include "../../include/unet_augment.h"
+#include "device_util.h"   // binomial3, shared with kernels_postproc.hip
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -627,24 +628,12 @@ __global__ void __launch_bounds__(AUG_T) k_sim_smooth(int W, int H, int D, const
     }
     int x, y, z;
     if (!row_voxel(W, H, x, y, z)) return;
-    float acc = 0.f;
-#pragma unroll
-    for (int kz = 0; kz < 3; ++kz) {
-        const int zz = min(max(z + kz - 1, 0), D - 1);
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int yy = min(max(y + ky - 1, 0), H - 1);
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int xx = min(max(x + kx - 1, 0), W - 1);
-                float v = src[(unsigned)((zz * H + yy) * W + xx)];     // volumes < 2^31 voxels (checked by the launcher)
-                if (lut) v = lds_lut[min(max((int)v, 0), T->max_label)];
-                const float w = (float)((kz == 1 ? 2 : 1) * (ky == 1 ? 2 : 1) * (kx == 1 ? 2 : 1)) * (1.0f / 64.0f);
-                acc += w * v;
-            }
-        }
-    }
-    dst[((int64_t)z * H + y) * W + x] = acc;
+    // volumes < 2^31 voxels (checked by the launcher)
+    dst[((int64_t)z * H + y) * W + x] = binomial3(W, H, D, x, y, z, [&](unsigned i) {
+        float v = src[i];
+        if (lut) v = lds_lut[min(max((int)v, 0), T->max_label)];
+        return v;
+    });
 }
 
 __global__ void __launch_bounds__(AUG_T) k_sim_remap(int64_t n, const SimTables* __restrict__ T, float* __restrict__ t1w,

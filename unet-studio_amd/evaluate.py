@@ -5,16 +5,24 @@
 One `model_io` buffer is a float32 host array of shape (in_count*D, H, W): the input channels stacked along z
 (evaluate.cpp:226-227).  After the forward it holds (out_count*D, H, W): the full-resolution logits [0] of the network, copied
 back to the host (evaluate.cpp:228-229).  Errors do not propagate: like the reference's thread they set `error_msg` and `aborted`
-(evaluate.cpp:234-242)."""
+(evaluate.cpp:234-242).
+
+With `postproc` (a chain string, or "model" for model.postproc; postproc.py) the chain runs on the device after every forward
+(evaluate.cpp:274) and each buffer is replaced by a dict of the wanted `outputs` instead: "label" uint16 (D, H, W), "fg_prob"
+float32 (D, H, W), "label_prob" float32 ((out_count-1)*D, H, W).  Only those are copied back.  An empty chain returns logits."""
 import numpy as np
 import torch
 
 from . import engine as E
+from . import postproc as P
 
 
 class EvaluateUNet:
-    def __init__(self, model, device=None):
+    def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None):
         self.model = model
+        self.postproc = postproc
+        self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
+        self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
         self.error_msg = ""
         self.aborted = False
@@ -29,16 +37,29 @@ class EvaluateUNet:
         self.model.prepare_for_inference(self.device)     # evaluate.cpp:391
         self.aborted, self.running, self.error_msg, self.cur_prog = False, True, "", 0
         out = [list(ios) for ios in model_io]
-        pending = None      # (file index, buffer index, pinned host tensor, shape, event): the previous result, still in flight
+        pending = None      # (file index, buffer index, {name: (pinned host tensor, shape)}, event): the previous result, in flight
         copy_stream = torch.cuda.Stream(self.device)
 
         def land(p):
-            fi, bi, host, shape, ev = p
+            fi, bi, hosts, ev = p
             ev.synchronize()
-            out[fi][bi] = host.numpy().reshape(shape)   # a view of the pinned buffer the copy landed in (owned by the array)
+            # views of the pinned buffers the copies landed in (owned by the arrays)
+            res = {k: host.numpy().reshape(shape) for k, (host, shape) in hosts.items()}
+            out[fi][bi] = res[None] if None in res else res
 
         try:
             m = self.model
+            chain = m.postproc if self.postproc == "model" else self.postproc
+            steps = None
+            if chain:
+                try:                                       # a bad chain ends the run as run_postproc's failure does (evaluate.cpp:274)
+                    steps = P.parse_chain(chain, self.params)
+                    P.check_chain(steps)
+                    P.check_outputs(steps, self.outputs)
+                except E.UNetError as e:
+                    self.error_msg, self.aborted, self.running = str(e), True, False
+                    return out
+            scratch = None                                 # the chain's scratch (defragment, per-plane commands), reused across volumes
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
             with torch.no_grad():                          # evaluate.cpp:221
                 while self.cur_prog < len(out) and not self.aborted:
@@ -52,22 +73,35 @@ class EvaluateUNet:
                         size = tuple(x.shape[2:])
                         result = m.forward(x, packs_current=size in packed_sizes)[0]     # evaluate.cpp:226-227
                         packed_sizes.add(size)
+                        if steps is not None:                                            # evaluate.cpp:274, on the compute stream
+                            if P.needs_scratch(steps):
+                                need = P.postproc_scratch_bytes(m.out_count, result.numel() // m.out_count)
+                                if scratch is None or scratch.numel() < need:
+                                    scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                            results = P.run_postproc(result, steps, outputs=self.outputs, scratch=scratch)
+                            results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2]))
+                                       for k, v in results.items()}
+                        else:
+                            results = {None: (result, (m.out_count * d, io.shape[1], io.shape[2]))}
                         # evaluate.cpp:228-229 copies the logits to the host before the next forward starts; here the copy runs on its
                         # own stream into pinned memory under the next buffer's upload + forward (same bytes, same order of results)
                         done = torch.cuda.Event()
                         done.record(torch.cuda.current_stream(self.device))
                         # (pinning costs ~2.6 ms per 50 MB result whether it is done per volume or in one arena for the whole run:
                         # measured 4.5 vs 7.1 ms per volume, profiles/bench_evaluate.py)
-                        host = torch.empty(result.shape, dtype=torch.float32, pin_memory=True)
+                        hosts = {}
                         with torch.cuda.stream(copy_stream):
                             copy_stream.wait_event(done)
-                            host.copy_(result, non_blocking=True)
-                            result.record_stream(copy_stream)
+                            for k, (r, shape) in results.items():
+                                host = torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
+                                host.copy_(r, non_blocking=True)
+                                r.record_stream(copy_stream)
+                                hosts[k] = (host, shape)
                             ev = torch.cuda.Event()
                             ev.record(copy_stream)
                         if pending is not None:
                             land(pending)
-                        pending = (self.cur_prog, i, host, (m.out_count * d, io.shape[1], io.shape[2]), ev)
+                        pending = (self.cur_prog, i, hosts, ev)
                     self.cur_prog += 1
                 if pending is not None:
                     land(pending)

@@ -1,0 +1,244 @@
+"""The inference post-processing chain of the reference (postproc, unet.cpp:112; evaluate.cpp:274,303-376) on the device.
+
+A chain is commands separated by '+', run left to right (the model's default: "softmax+create_mask+argmax").  The definitions are in
+include/unet_postproc.h; they are this project's, and parity with TIPL's run_postproc / softmax / argmax / defragment_by_size_ratio
+/ normalize is not pinned.  Out of scope (TIPL): soft_max, anisotropic_smoothing, defragment_smoothing, and the
+pre-processing, FOV and orientation handling around the chain.
+
+A result holds up to three outputs: `label_prob` {C-1, D, H, W} fp32 (softmax), `fg_prob` {D, H, W} fp32 (create_mask) and `label`
+{D, H, W} uint16 (argmax).  create_mask and argmax need a softmax earlier in the chain; defragment needs a create_mask before it.
+argmax reads the current state: right after the fused pass that is the logits' probabilities, after a command that changed
+label_prob or fg_prob (defragment, defragment_each, a per-plane command) it is label_prob and fg_prob as they now are, so such an
+argmax needs a create_mask before it.  create_mask always sums the exponentials of the logits, so it may not follow such a command.
+The per-plane commands and defragment_each act on label_prob.  A wanted output the chain does not produce is refused.
+Adjacent softmax / create_mask / argmax run as one fused kernel, and an output nobody asked for and no later command reads is
+never written (the default chain with outputs=("label",) reads the logits once and writes 2 bytes per voxel)."""
+import ctypes as C
+
+import torch
+
+from . import engine as E
+from .engine import UNetError
+
+E._sig("unet_postproc_scratch_bytes", C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t))
+E._sig("unet_postproc_softmax", C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+E._sig("unet_postproc_argmax_planes", C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p)
+E._sig("unet_postproc_defragment", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+E._sig("unet_postproc_plane_op", C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+       C.c_void_p)
+# every symbol include/unet_postproc.h declares
+EXPORTS = ["unet_postproc_scratch_bytes", "unet_postproc_softmax", "unet_postproc_argmax_planes", "unet_postproc_defragment",
+           "unet_postproc_plane_op"]
+
+# the ops of unet_postproc_plane_op (include/unet_postproc.h)
+PP_UPPER_THRESHOLD, PP_LOWER_THRESHOLD, PP_MINUS, PP_BINARIZE, PP_NORMALIZE, PP_SMOOTH = 1, 2, 3, 4, 5, 6
+PLANE_OPS = {"upper_threshold": PP_UPPER_THRESHOLD, "lower_threshold": PP_LOWER_THRESHOLD, "minus": PP_MINUS,
+             "binarize": PP_BINARIZE, "normalize_each": PP_NORMALIZE, "gaussian_smoothing": PP_SMOOTH}
+
+# command -> its parameters and their defaults, in order
+COMMANDS = {
+    "softmax": (),
+    "create_mask": (),
+    "argmax": (("threshold", 0.5),),
+    "defragment": (("threshold", 0.5), ("size_ratio", 0.05)),
+    "defragment_each": (("threshold", 0.5), ("size_ratio", 0.05)),
+    "upper_threshold": (("t", 1.0),),
+    "lower_threshold": (("t", 0.0),),
+    "minus": (("v", 0.5),),
+    "binarize": (("t", 0.5),),
+    "normalize_each": (),
+    "gaussian_smoothing": (),
+}
+OUTPUTS = ("label_prob", "fg_prob", "label")
+MUTATORS = ("defragment", "defragment_each") + tuple(PLANE_OPS)   # commands that change label_prob / fg_prob / label in place
+PRODUCER = {"label_prob": "softmax", "fg_prob": "create_mask", "label": "argmax"}
+
+
+def parse_chain(text, params=None):
+    """'softmax+create_mask+argmax' -> [(command, {parameter: value}), ...].  Host only.
+    params: {command: value, a tuple of values in the order of COMMANDS, or a {parameter: value} dict}, applied to every use of
+    that command (postproc.txt's role in the reference GUI).  Raises UNetError("unknown command <name>") (evaluate.cpp:375)."""
+    params = dict(params or {})
+    steps = []
+    for name in (s.strip() for s in (text or "").split("+")):
+        if not name:
+            continue
+        if name not in COMMANDS:
+            raise UNetError("unknown command " + name)
+        steps.append((name, {k: float(v) for k, v in COMMANDS[name]}))
+    for name, p in params.items():
+        if name not in COMMANDS:
+            raise UNetError("unknown command " + name)
+        spec = COMMANDS[name]
+        if isinstance(p, dict):
+            vals = dict(p)
+        else:
+            seq = p if isinstance(p, (tuple, list)) else (p,)
+            if len(seq) > len(spec):
+                raise UNetError("%s takes %d parameter(s), got %d" % (name, len(spec), len(seq)))
+            vals = {spec[i][0]: v for i, v in enumerate(seq)}
+        for k, v in vals.items():
+            if k not in dict(spec):
+                raise UNetError("%s has no parameter %s" % (name, k))
+            for step_name, sp in steps:
+                if step_name == name:
+                    sp[k] = float(v)
+    return steps
+
+
+def check_chain(steps):
+    """The order rules of this project's definitions (module docstring); raises UNetError.  Host only."""
+    seen, changed = set(), None
+    for name, _ in steps:
+        if name in ("create_mask", "argmax", "defragment_each") or name in PLANE_OPS:
+            if "softmax" not in seen:
+                raise UNetError("%s needs softmax before it" % name)
+        if name == "defragment" and "create_mask" not in seen:
+            raise UNetError("defragment needs create_mask before it")
+        if name == "create_mask" and changed:
+            raise UNetError("create_mask after %s is not supported (create_mask sums the exponentials of the logits)" % changed)
+        if name == "argmax" and changed and "create_mask" not in seen:
+            raise UNetError("argmax after %s needs create_mask before it" % changed)
+        if name in MUTATORS:
+            changed = name
+        seen.add(name)
+
+
+def check_outputs(steps, outputs):
+    """every wanted output must be one the chain produces; raises UNetError.  Host only."""
+    names = [n for n, _ in steps]
+    for o in outputs:
+        if o not in OUTPUTS:
+            raise UNetError("unknown output %s (one of %s)" % (o, ", ".join(OUTPUTS)))
+        if PRODUCER[o] not in names:
+            raise UNetError("output %s is not produced by the chain (it needs %s)" % (o, PRODUCER[o]))
+
+
+def argmax_after_change(steps):
+    """True when some argmax of the chain follows a command that changed the state (it then reads label_prob and fg_prob)"""
+    changed = False
+    for name, _ in steps:
+        changed = changed or name in MUTATORS
+        if name == "argmax" and changed:
+            return True
+    return False
+
+
+def needs_scratch(steps):
+    return any(n in MUTATORS for n, _ in steps)
+
+
+def postproc_scratch_bytes(out_c, voxels):
+    n = C.c_size_t()
+    E.check(E.lib.unet_postproc_scratch_bytes(int(out_c), int(voxels), C.byref(n)))
+    return n.value
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def softmax_call(logits, out_c, voxels, threshold=0.5, label_prob=None, fg_prob=None, label=None, stream=None):
+    """unet_postproc_softmax on device pointers / tensors (None: not wanted); stream: the current one when None"""
+    st = stream if stream is not None else torch.cuda.current_stream(logits.device).cuda_stream
+    E.check(E.lib.unet_postproc_softmax(_ptr(logits), int(out_c), int(voxels), float(threshold), _ptr(label_prob), _ptr(fg_prob),
+                                        _ptr(label), st))
+
+
+def argmax_planes_call(label_prob, n_planes, voxels, fg_prob, threshold, label, stream=None):
+    """unet_postproc_argmax_planes"""
+    st = stream if stream is not None else torch.cuda.current_stream(label_prob.device).cuda_stream
+    E.check(E.lib.unet_postproc_argmax_planes(_ptr(label_prob), int(n_planes), int(voxels), _ptr(fg_prob), float(threshold), _ptr(label),
+                                              st))
+
+
+def defragment_call(dims, each, threshold, size_ratio, fg_prob, label_prob, n_planes, label, scratch, stream=None):
+    """unet_postproc_defragment; dims = (W, H, D)"""
+    any_t = label_prob if each else fg_prob
+    dev = any_t.device if any_t is not None else torch.device("cuda", torch.cuda.current_device())
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    E.check(E.lib.unet_postproc_defragment(int(dims[0]), int(dims[1]), int(dims[2]), int(bool(each)), float(threshold), float(size_ratio),
+                                           _ptr(fg_prob), _ptr(label_prob), int(n_planes), _ptr(label), _ptr(scratch),
+                                           scratch.numel() * scratch.element_size() if scratch is not None else 0, st))
+
+
+def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
+    """unet_postproc_plane_op; dims = (W, H, D)"""
+    dev = label_prob.device if label_prob is not None else torch.device("cuda", torch.cuda.current_device())
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    E.check(E.lib.unet_postproc_plane_op(int(op), float(param), int(dims[0]), int(dims[1]), int(dims[2]), _ptr(label_prob), int(n_planes),
+                                         _ptr(scratch), scratch.numel() * scratch.element_size() if scratch is not None else 0, st))
+
+
+def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None):
+    """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
+    chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
+    scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed)."""
+    steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
+    check_chain(steps)
+    outputs = tuple(outputs)
+    check_outputs(steps, outputs)
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
+        raise UNetError("run_postproc: logits must be a contiguous float32 device tensor")
+    if logits.dim() == 5:
+        if logits.shape[0] != 1:
+            raise UNetError("run_postproc: one volume at a time, got a batch of %d" % logits.shape[0])
+        logits = logits[0]
+    if logits.dim() != 4:
+        raise UNetError("run_postproc: logits must be {C, D, H, W}, got %s" % (tuple(logits.shape),))
+    out_c, D, H, W = (int(v) for v in logits.shape)
+    S = D * H * W
+    postproc_scratch_bytes(out_c, S)   # the class / size checks, before any device work
+    dev = logits.device
+    names = [n for n, _ in steps]
+    from_state = argmax_after_change(steps) and "label" in outputs
+    want_lp = ("label_prob" in outputs or from_state) and "softmax" in names
+    want_fg = "create_mask" in names and ("fg_prob" in outputs or "defragment" in names or from_state)
+    want_lab = "argmax" in names and "label" in outputs
+    changed = False
+    res = {}
+    scr = [scratch]
+
+    def get_scratch():
+        need = postproc_scratch_bytes(out_c, S)
+        if scr[0] is None or scr[0].numel() * scr[0].element_size() < need:
+            scr[0] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return scr[0]
+
+    i = 0
+    while i < len(steps):
+        name, p = steps[i]
+        if name in ("softmax", "create_mask", "argmax"):
+            j, run = i, {}
+            while j < len(steps) and steps[j][0] in ("softmax", "create_mask", "argmax"):
+                run[steps[j][0]] = steps[j][1]
+                j += 1
+            lp = fg = lab = None
+            if "softmax" in run and want_lp:
+                lp = res["label_prob"] = torch.empty((out_c - 1, D, H, W), dtype=torch.float32, device=dev)
+            if "create_mask" in run and want_fg:
+                fg = res["fg_prob"] = torch.empty((D, H, W), dtype=torch.float32, device=dev)
+            if "argmax" in run and want_lab:
+                lab = res["label"] = res.get("label", torch.empty((D, H, W), dtype=torch.uint16, device=dev))
+            thr = run.get("argmax", {}).get("threshold", 0.5)
+            fused_lab = lab if not changed else None      # after a change argmax reads the current planes, below
+            if lp is not None or fg is not None or fused_lab is not None:
+                softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
+            if lab is not None and changed:
+                argmax_planes_call(res["label_prob"], out_c - 1, S, res["fg_prob"], thr, lab)
+            i = j
+            continue
+        changed = True   # every command below changes the state in place
+        lp = res.get("label_prob")
+        if name == "defragment":
+            defragment_call((W, H, D), False, p["threshold"], p["size_ratio"], res["fg_prob"], lp, out_c - 1 if lp is not None else 0,
+                            res.get("label"), get_scratch())
+        elif name == "defragment_each":
+            if lp is not None:
+                defragment_call((W, H, D), True, p["threshold"], p["size_ratio"], None, lp, out_c - 1, None, get_scratch())
+        elif lp is not None:   # a per-plane command: it only changes label_prob
+            param = next(iter(p.values())) if p else 0.0
+            plane_op_call(PLANE_OPS[name], param, (W, H, D), lp, out_c - 1, get_scratch())
+        i += 1
+    return {k: v for k, v in res.items() if k in outputs}
