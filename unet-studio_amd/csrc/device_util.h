@@ -72,6 +72,103 @@ __device__ __forceinline__ float binomial3(int W, int H, int D, int x, int y, in
     return acc;
 }
 
+// ---- the gather passes' thread -> voxel map (kernels_augment.hip, kernels_space.hip) ---------------------------------------------
+// A block of 256 threads on a 16 x 4 x 4 brick; gx, gy: bricks along x and y.  The grid is the brick count rounded up to a multiple
+// of 8, and bricks are numbered so that each XCD (blocks are dealt round-robin to the 8 XCDs) works through one contiguous z-range
+// of the volume.  Returns false for a thread whose voxel is outside the volume (x = y = z = 0 for a block with no brick).
+constexpr int BRICK_X = 16, BRICK_Y = 4, BRICK_Z = 4;
+
+__device__ __forceinline__ bool brick_walk(int W, int H, int D, int gx, int gy, int& x, int& y, int& z) {
+    const unsigned nb = gridDim.x, per = (nb + 7) / 8;
+    const unsigned b = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // uniform
+    if (b >= nb) { x = y = z = 0; return false; }                     // only when nb is not a multiple of 8: ids >= nb idle
+    const unsigned bx = b % gx, r = b / gx, by = r % gy, bz = r / gy;
+    x = bx * BRICK_X + (threadIdx.x & (BRICK_X - 1));
+    y = by * BRICK_Y + ((threadIdx.x / BRICK_X) & (BRICK_Y - 1));
+    z = bz * BRICK_Z + threadIdx.x / (BRICK_X * BRICK_Y);
+    return x < W && y < H && z < D;
+}
+
+// ---- the sampler (this project's stand-in for tipl::compose_mapping / tipl::resample; oracle/augment_ref.py _locate, _trilinear,
+// _majority restate it).  FMA contraction is off inside the bodies, whatever the including file's mode, so the restatement rounds
+// identically.
+struct Tri {   // trilinear footprint: the 8 corner offsets (corner i: bit 0 = x, bit 1 = y, bit 2 = z; upper neighbours clamped), fractions
+    unsigned o[8];
+    float tx, ty, tz;
+    bool ok;
+};
+
+// 32-bit offsets inside one volume (the launchers check D*H*W < 2^31): the loads become base + 32-bit-offset accesses and the
+// address arithmetic stays off the quarter-rate 64-bit multiplier
+__device__ __forceinline__ Tri locate(float x, float y, float z, int W, int H, int D) {
+#pragma clang fp contract(off)
+    Tri t;
+    // NaN positions (a distortion focus's own centre voxel, .cu:151: 0/0) fail these comparisons, as out-of-volume ones do
+    t.ok = (x >= 0.f) && (y >= 0.f) && (z >= 0.f) && (x <= (float)(W - 1)) && (y <= (float)(H - 1)) && (z <= (float)(D - 1));
+    if (!t.ok) return t;
+    float fx = floorf(x), fy = floorf(y), fz = floorf(z);
+    t.tx = x - fx; t.ty = y - fy; t.tz = z - fz;
+    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1), z1 = min(z0 + 1, D - 1);
+    const unsigned r00 = (unsigned)(z0 * H + y0) * (unsigned)W, r10 = (unsigned)(z0 * H + y1) * (unsigned)W,
+                   r01 = (unsigned)(z1 * H + y0) * (unsigned)W, r11 = (unsigned)(z1 * H + y1) * (unsigned)W;
+    t.o[0] = r00 + x0; t.o[1] = r00 + x1; t.o[2] = r10 + x0; t.o[3] = r10 + x1;
+    t.o[4] = r01 + x0; t.o[5] = r01 + x1; t.o[6] = r11 + x0; t.o[7] = r11 + x1;
+    return t;
+}
+
+__device__ __forceinline__ float lerp1(float t, float a, float b) {
+#pragma clang fp contract(off)
+    return a + t * (b - a);
+}
+
+__device__ __forceinline__ float trilinear(const Tri& t, const float* __restrict__ vol) {
+    float c00 = lerp1(t.tx, vol[t.o[0]], vol[t.o[1]]);
+    float c10 = lerp1(t.tx, vol[t.o[2]], vol[t.o[3]]);
+    float c01 = lerp1(t.tx, vol[t.o[4]], vol[t.o[5]]);
+    float c11 = lerp1(t.tx, vol[t.o[6]], vol[t.o[7]]);
+    return lerp1(t.tz, lerp1(t.ty, c00, c10), lerp1(t.ty, c01, c11));
+}
+
+// label resampling for class ids: the value holding the largest total trilinear weight among the 8 corners
+// (first corner wins ties; corner order x fastest)
+__device__ __forceinline__ float majority(const Tri& t, const float* __restrict__ vol) {
+#pragma clang fp contract(off)
+    float v[8], w[8];
+    float wx[2] = {1.0f - t.tx, t.tx}, wy[2] = {1.0f - t.ty, t.ty}, wz[2] = {1.0f - t.tz, t.tz};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        v[i] = vol[t.o[i]];
+        w[i] = wx[i & 1] * wy[(i >> 1) & 1] * wz[i >> 2];
+    }
+    float best = v[0], best_score = -1.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += (v[i] == v[j]) ? w[i] : 0.f;
+        if (s > best_score) { best_score = s; best = v[j]; }
+    }
+    return best;
+}
+
+// ---- the softmax / create_mask accumulator of the post-processing pass (kernels_postproc.hip, kernels_space.hip) -------------------
+// one channel into the online state: m the running max, s = sum exp(x - m), sf the same over the foreground (fgc = 1).
+// -inf adds nothing; a NaN makes s NaN; +inf makes m infinite.  Both mark the voxel bad at the end (torch.softmax's NaN rows).
+// Compiled in the default contraction mode on purpose: both users must round alike.
+__device__ __forceinline__ void pp_acc(float x, float& m, float& s, float& sf, float fgc) {
+    if (x > m) {
+        const float e = expf(m - x);
+        s = s * e + 1.f;
+        sf = sf * e + fgc;
+        m = x;
+    } else if (x != -INFINITY) {
+        const float e = expf(x - m);
+        s += e;
+        sf += fgc * e;
+    }
+}
+
 static inline unsigned cdiv64(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace unet

@@ -1991,4 +1991,49 @@ int unet_postproc_plane_op(int op, float param, int w, int h, int d, float* labe
     return pp_run(label_prob, stream, [&](hipStream_t s) { launch_postproc_plane_op(op, param, w, h, d, label_prob, n_planes, scratch, s); });
 }
 
+// ---- between a scan's grid and the model's (include/unet_space.h) ----
+static const char* space_grid_error(int w, int h, int d) {
+    if (w <= 0 || h <= 0 || d <= 0) return "unet_space: volume dimensions must be positive";
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31) || space_bricks(w, h, d) > ((int64_t)1 << 30))
+        return "unet_space: a grid must stay below 2^31 voxels (and 2^30 bricks of 16 x 4 x 4)";
+    return nullptr;
+}
+int unet_space_scratch_bytes(int64_t dst_voxels, int channels, size_t* bytes) {
+    if (dst_voxels <= 0 || dst_voxels >= ((int64_t)1 << 31)) return fail("unet_space: dst_voxels must be in [1, 2^31)");
+    if (channels <= 0) return fail("unet_space: channels must be positive");
+    if (!bytes) return fail("unet_space_scratch_bytes: null output");
+    *bytes = space_scratch_bytes(dst_voxels, channels);
+    return 0;
+}
+int unet_space_resample(const float* src, int sw, int sh, int sd, float* dst, int dw, int dh, int dd, int channels,
+                        const UnetSpaceMap* map, int mode, int normalize, void* scratch, size_t scratch_bytes, void* stream) {
+    if (const char* e = space_grid_error(sw, sh, sd)) return fail(e);
+    if (const char* e = space_grid_error(dw, dh, dd)) return fail(e);
+    if (channels <= 0) return fail("unet_space: channels must be positive");
+    if (!src || !dst) return fail("unet_space_resample: null device pointer");
+    if (!map) return fail("unet_space_resample: null map");
+    if (mode != UNET_SPACE_LINEAR && mode != UNET_SPACE_MAJORITY) return fail("unet_space_resample: unknown mode " + std::to_string(mode));
+    if (normalize && mode != UNET_SPACE_LINEAR) return fail("unet_space_resample: normalize goes with UNET_SPACE_LINEAR only");
+    if (normalize && !scratch) return fail("unet_space_resample: normalize needs scratch");
+    if (normalize && scratch_bytes < space_scratch_bytes((int64_t)dw * dh * dd, channels))
+        return fail("unet_space_resample: scratch too small (see unet_space_scratch_bytes)");
+    const UnetSpaceMap m = *map;
+    return pp_run(dst, stream, [&](hipStream_t s) {
+        launch_space_resample(src, sw, sh, sd, dst, dw, dh, dd, channels, m, mode, normalize, scratch, s);
+    });
+}
+int unet_space_postproc(const float* logits, int out_c, int mw, int mh, int md, const UnetSpaceMap* map, int nw, int nh, int nd,
+                        float threshold, float* label_prob, float* fg_prob, uint16_t* label, void* stream) {
+    if (const char* e = pp_class_error(out_c, 1)) return fail(e);
+    if (const char* e = space_grid_error(mw, mh, md)) return fail(e);
+    if (const char* e = space_grid_error(nw, nh, nd)) return fail(e);
+    if (!logits) return fail("unet_space_postproc: null logits");
+    if (!map) return fail("unet_space_postproc: null map");
+    if (!label_prob && !fg_prob && !label) return fail("unet_space_postproc: no output wanted");
+    const UnetSpaceMap m = *map;
+    return pp_run(logits, stream, [&](hipStream_t s) {
+        launch_space_postproc(logits, out_c, mw, mh, md, m, nw, nh, nd, threshold, label_prob, fg_prob, label, s);
+    });
+}
+
 }  // extern "C"

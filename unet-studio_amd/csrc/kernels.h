@@ -10,6 +10,7 @@
 #include "../../include/unet_hip.h"
 #include "../../include/unet_postproc.h"
 #include "../../include/unet_qc.h"
+#include "../../include/unet_space.h"
 
 namespace unet {
 
@@ -331,5 +332,13 @@ void launch_postproc_argmax_planes(const float* lp, int np, int64_t S, const flo
 void launch_postproc_defragment(int W, int H, int D, int each, float thr, double ratio, float* fg, float* lp, int np, uint16_t* lab,
                                 void* scratch, hipStream_t s);
 void launch_postproc_plane_op(int op, float t, int W, int H, int D, float* lp, int np, void* scratch, hipStream_t s);
+
+// kernels_space.hip: resampling between a scan's grid and the model's, and the fused pass on the native grid (include/unet_space.h)
+int64_t space_bricks(int w, int h, int d);
+size_t space_scratch_bytes(int64_t dst_voxels, int channels);
+void launch_space_resample(const float* src, int sw, int sh, int sd, float* dst, int dw, int dh, int dd, int channels,
+                           const UnetSpaceMap& map, int mode, int normalize, void* scratch, hipStream_t s);
+void launch_space_postproc(const float* logits, int C, int mw, int mh, int md, const UnetSpaceMap& map, int nw, int nh, int nd, float thr,
+                           float* lp, float* fg, uint16_t* lab, hipStream_t s);
 
 }  // namespace unet

@@ -43,18 +43,11 @@ struct AugGeom {
 // touch hundreds of cache lines with no reuse between corners (the blend pass at 2 x 256^3: 12.8 ms by rows, 6.6 ms by bricks).  Bricks are numbered so
 // that each XCD (blocks are dealt round-robin to the 8 XCDs) works through one contiguous z-range of the volume and its
 // private L2 keeps that range's halo.
-constexpr int TX = 16, TY = 4, TZ = 4;
+constexpr int TX = BRICK_X, TY = BRICK_Y, TZ = BRICK_Z;   // the walk itself: device_util.h (shared with kernels_space.hip)
 static_assert(TX * TY * TZ == AUG_T, "brick = block");
 
 __device__ __forceinline__ bool brick_voxel(const AugGeom& g, int& x, int& y, int& z) {
-    const unsigned nb = gridDim.x, per = (nb + 7) / 8;
-    const unsigned b = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // uniform
-    if (b >= nb) { x = y = z = 0; return false; }                     // only when nb is not a multiple of 8: ids >= nb idle
-    const unsigned bx = b % g.gx, r = b / g.gx, by = r % g.gy, bz = r / g.gy;
-    x = bx * TX + (threadIdx.x & (TX - 1));
-    y = by * TY + ((threadIdx.x / TX) & (TY - 1));
-    z = bz * TZ + threadIdx.x / (TX * TY);
-    return x < g.W && y < g.H && z < g.D;
+    return brick_walk(g.W, g.H, g.D, g.gx, g.gy, x, y, z);
 }
 
 // element-wise passes that need coordinates: a block = 64 (x) x 4 (y) at one z, launched on a 3-D grid
@@ -155,60 +148,7 @@ __device__ __forceinline__ float hash_u01(uint64_t index, unsigned seed) {
     return (float)((h >> 8) + 1u) * (1.0f / 16777216.0f);
 }
 
-struct Tri {   // trilinear footprint: the 8 corner offsets (corner i: bit 0 = x, bit 1 = y, bit 2 = z; upper neighbours clamped), fractions
-    unsigned o[8];
-    float tx, ty, tz;
-    bool ok;
-};
-
-// 32-bit offsets inside one volume (launch_augment checks D*H*W < 2^31): the loads become base + 32-bit-offset accesses and the
-// address arithmetic stays off the quarter-rate 64-bit multiplier
-__device__ __forceinline__ Tri locate(float x, float y, float z, int W, int H, int D) {
-    Tri t;
-    // NaN positions (a distortion focus's own centre voxel, .cu:151: 0/0) fail these comparisons, as out-of-volume ones do
-    t.ok = (x >= 0.f) && (y >= 0.f) && (z >= 0.f) && (x <= (float)(W - 1)) && (y <= (float)(H - 1)) && (z <= (float)(D - 1));
-    if (!t.ok) return t;
-    float fx = floorf(x), fy = floorf(y), fz = floorf(z);
-    t.tx = x - fx; t.ty = y - fy; t.tz = z - fz;
-    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1), z1 = min(z0 + 1, D - 1);
-    const unsigned r00 = (unsigned)(z0 * H + y0) * (unsigned)W, r10 = (unsigned)(z0 * H + y1) * (unsigned)W,
-                   r01 = (unsigned)(z1 * H + y0) * (unsigned)W, r11 = (unsigned)(z1 * H + y1) * (unsigned)W;
-    t.o[0] = r00 + x0; t.o[1] = r00 + x1; t.o[2] = r10 + x0; t.o[3] = r10 + x1;
-    t.o[4] = r01 + x0; t.o[5] = r01 + x1; t.o[6] = r11 + x0; t.o[7] = r11 + x1;
-    return t;
-}
-
-__device__ __forceinline__ float lerp1(float t, float a, float b) { return a + t * (b - a); }
-
-__device__ __forceinline__ float trilinear(const Tri& t, const float* __restrict__ vol) {
-    float c00 = lerp1(t.tx, vol[t.o[0]], vol[t.o[1]]);
-    float c10 = lerp1(t.tx, vol[t.o[2]], vol[t.o[3]]);
-    float c01 = lerp1(t.tx, vol[t.o[4]], vol[t.o[5]]);
-    float c11 = lerp1(t.tx, vol[t.o[6]], vol[t.o[7]]);
-    return lerp1(t.tz, lerp1(t.ty, c00, c10), lerp1(t.ty, c01, c11));
-}
-
-// label resampling for class ids: the value holding the largest total trilinear weight among the 8 corners
-// (first corner wins ties; corner order x fastest)
-__device__ __forceinline__ float majority(const Tri& t, const float* __restrict__ vol) {
-    float v[8], w[8];
-    float wx[2] = {1.0f - t.tx, t.tx}, wy[2] = {1.0f - t.ty, t.ty}, wz[2] = {1.0f - t.tz, t.tz};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        v[i] = vol[t.o[i]];
-        w[i] = wx[i & 1] * wy[(i >> 1) & 1] * wz[i >> 2];
-    }
-    float best = v[0], best_score = -1.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += (v[i] == v[j]) ? w[i] : 0.f;
-        if (s > best_score) { best_score = s; best = v[j]; }
-    }
-    return best;
-}
+// Tri, locate, lerp1, trilinear, majority: device_util.h (shared with kernels_space.hip)
 
 __device__ __forceinline__ void apply_affine(const UnetAugAffine& a, float& x, float& y, float& z) {
     float nx = a.sr[0] * x + a.sr[1] * y + a.sr[2] * z + a.shift[0];

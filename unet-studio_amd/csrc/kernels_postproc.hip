@@ -61,21 +61,7 @@ template <int VEC> __device__ __forceinline__ void stv(float* __restrict__ p, in
     else p[i] = x[0];
 }
 
-// one channel into the online state: m the running max, s = sum exp(x - m), sf the same over the foreground (fgc = 1).
-// -inf adds nothing; a NaN makes s NaN; +inf makes m infinite.  Both mark the voxel bad at the end (torch.softmax's NaN rows)
-__device__ __forceinline__ void pp_acc(float x, float& m, float& s, float& sf, float fgc) {
-    if (x > m) {
-        const float e = expf(m - x);
-        s = s * e + 1.f;
-        sf = sf * e + fgc;
-        m = x;
-    } else if (x != -INFINITY) {
-        const float e = expf(x - m);
-        s += e;
-        sf += fgc * e;
-    }
-}
-
+// pp_acc, the per-voxel online softmax state: device_util.h (shared with kernels_space.hip)
 template <int VEC>
 __global__ void __launch_bounds__(PP_T) k_pp_softmax(const float* __restrict__ lg, int C, int64_t S, float thr,
                                                      float* __restrict__ lp, float* __restrict__ fg, uint16_t* __restrict__ lab) {

@@ -1,6 +1,7 @@
 """Inference loop of the reference over the engine: `evaluate_unet::start()` -> `prepare_for_inference`, then
-`evaluate_unet::evaluate()` (evaluate.cpp:386-399, 211-246) for volumes that are already pre-processed host buffers
-(reading, pre-/post-processing and file output are TIPL code and out of scope).
+`evaluate_unet::evaluate()` (evaluate.cpp:386-399, 211-246) for host buffers that are either already at the model's grid or
+`space.NativeVolume`s on the scan's own grid (reading files, handle_orientation, the preproc commands and file output are TIPL
+code and out of scope).
 
 One `model_io` buffer is a float32 host array of shape (in_count*D, H, W): the input channels stacked along z
 (evaluate.cpp:226-227).  After the forward it holds (out_count*D, H, W): the full-resolution logits [0] of the network, copied
@@ -9,12 +10,19 @@ back to the host (evaluate.cpp:228-229).  Errors do not propagate: like the refe
 
 With `postproc` (a chain string, or "model" for model.postproc; postproc.py) the chain runs on the device after every forward
 (evaluate.cpp:274) and each buffer is replaced by a dict of the wanted `outputs` instead: "label" uint16 (D, H, W), "fg_prob"
-float32 (D, H, W), "label_prob" float32 ((out_count-1)*D, H, W).  Only those are copied back.  An empty chain returns logits."""
+float32 (D, H, W), "label_prob" float32 ((out_count-1)*D, H, W).  Only those are copied back.  An empty chain returns logits.
+
+An entry may be a `space.NativeVolume` (in_count*d, h, w) with its voxel size instead: it is uploaded, brought to model.dim on the
+device (space.to_model_space: read_image_and_label, train.cpp:13-40), run through the forward, and the results come back on ITS grid,
+in the reference's order, handle_fov_post then run_postproc (evaluate.cpp:274): without a chain the logits resampled linear,
+(out_count*d, h, w); with one, the chain on the native grid, its fused softmax / create_mask / argmax group interpolating the
+logits it reads (include/unet_space.h) and every later command unchanged.  Plain arrays take the path above unchanged."""
 import numpy as np
 import torch
 
 from . import engine as E
 from . import postproc as P
+from . import space as SP
 
 
 class EvaluateUNet:
@@ -65,23 +73,39 @@ class EvaluateUNet:
                 while self.cur_prog < len(out) and not self.aborted:
                     self.status = "inferencing"
                     for i, io in enumerate(out[self.cur_prog]):
+                        nv = io if isinstance(io, SP.NativeVolume) else None
+                        if nv is not None:
+                            nv.check()
+                            io = nv.data
                         io = np.ascontiguousarray(io, dtype=np.float32)
                         if io.ndim != 3 or io.shape[0] % m.in_count:
                             raise E.UNetError("model_io buffer must be (in_count*D, H, W), got %s" % (io.shape,))
                         d = io.shape[0] // m.in_count
-                        x = torch.from_numpy(io).view(1, m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
+                        if nv is None:
+                            x = torch.from_numpy(io).view(1, m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
+                            back = None
+                        else:                                                            # read_image_and_label, on the compute stream
+                            native = (d, io.shape[1], io.shape[2])
+                            fwd = nv.map if nv.map is not None else SP.model_to_image_map(m.dim, m.voxel_size, native[::-1], nv.voxel_size)
+                            back = SP.invert_map(fwd)                                    # native voxel -> model position
+                            x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
+                            x = SP.to_model_space(m, x, nv.voxel_size, map=fwd)[0].unsqueeze(0)
                         size = tuple(x.shape[2:])
                         result = m.forward(x, packs_current=size in packed_sizes)[0]     # evaluate.cpp:226-227
                         packed_sizes.add(size)
                         if steps is not None:                                            # evaluate.cpp:274, on the compute stream
+                            voxels = result.numel() // m.out_count if nv is None else d * io.shape[1] * io.shape[2]
                             if P.needs_scratch(steps):
-                                need = P.postproc_scratch_bytes(m.out_count, result.numel() // m.out_count)
+                                need = P.postproc_scratch_bytes(m.out_count, voxels)
                                 if scratch is None or scratch.numel() < need:
                                     scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            results = P.run_postproc(result, steps, outputs=self.outputs, scratch=scratch)
+                            results = P.run_postproc(result, steps, outputs=self.outputs, scratch=scratch,
+                                                     native=None if nv is None else (back, native))
                             results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2]))
                                        for k, v in results.items()}
                         else:
+                            if nv is not None:                                           # handle_fov_post alone: the logits on the native grid
+                                result = SP.resample(result.view(m.out_count, *size), native, back, "linear")
                             results = {None: (result, (m.out_count * d, io.shape[1], io.shape[2]))}
                         # evaluate.cpp:228-229 copies the logits to the host before the next forward starts; here the copy runs on its
                         # own stream into pinned memory under the next buffer's upload + forward (same bytes, same order of results)

@@ -171,10 +171,14 @@ def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
                                          _ptr(scratch), scratch.numel() * scratch.element_size() if scratch is not None else 0, st))
 
 
-def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None):
+def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
-    scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed)."""
+    scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
+    native: (map, (d, h, w)) runs the chain on that grid instead, map taking a native voxel to its position in the logits' grid
+    (handle_fov_post before run_postproc, evaluate.cpp:274): every fused softmax / create_mask / argmax group interpolates the logits
+    it reads (space.postproc_native), the other commands run unchanged on the native planes, and the scratch is the native grid's.
+    check_chain lets no command read the logits outside a fused group, so they are never stored on the native grid."""
     steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
     check_chain(steps)
     outputs = tuple(outputs)
@@ -188,6 +192,9 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None):
     if logits.dim() != 4:
         raise UNetError("run_postproc: logits must be {C, D, H, W}, got %s" % (tuple(logits.shape),))
     out_c, D, H, W = (int(v) for v in logits.shape)
+    if native is not None:
+        from . import space as SP
+        native_map, (D, H, W) = native[0], SP._shape3(native[1], "native shape")
     S = D * H * W
     postproc_scratch_bytes(out_c, S)   # the class / size checks, before any device work
     dev = logits.device
@@ -224,7 +231,12 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None):
             thr = run.get("argmax", {}).get("threshold", 0.5)
             fused_lab = lab if not changed else None      # after a change argmax reads the current planes, below
             if lp is not None or fg is not None or fused_lab is not None:
-                softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
+                if native is None:
+                    softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
+                else:
+                    wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
+                    wanted = {k: v for k, v in wanted.items() if v is not None}
+                    SP.postproc_native(logits, native_map, (D, H, W), thr, tuple(wanted), out=wanted)
             if lab is not None and changed:
                 argmax_planes_call(res["label_prob"], out_c - 1, S, res["fg_prob"], thr, lab)
             i = j
