@@ -20,6 +20,8 @@ from . import feed  # noqa: F401  (the module: feed.EXPORTS the symbols of inclu
 from .feed import TrainingFeed  # noqa: F401
 from . import postproc  # noqa: F401  (the module: postproc.EXPORTS the symbols of include/unet_postproc.h)
 from .postproc import parse_chain, run_postproc  # noqa: F401
+from . import preproc  # noqa: F401  (the module: preproc.EXPORTS the symbols of include/unet_preproc.h)
+from .preproc import run_preproc  # noqa: F401
 
 
 def save_to_file(model, file_name):

@@ -2036,4 +2036,48 @@ int unet_space_postproc(const float* logits, int out_c, int mw, int mh, int md, 
     });
 }
 
+// ---- the pre-processing commands of a model (include/unet_preproc.h) ----
+static const char* preproc_volume_error(const void* src, const void* dst, int w, int h, int d, int channels) {
+    if (!src || !dst) return "unet_preproc: null device pointer";
+    if (src == dst) return "unet_preproc: src and dst must differ (the commands run out of place)";
+    if (w <= 0 || h <= 0 || d <= 0) return "unet_preproc: volume dimensions must be positive";
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return "unet_preproc: a grid must stay below 2^31 voxels";
+    if (channels <= 0 || channels > 65535) return "unet_preproc: channels must be in [1, 65535]";
+    return nullptr;
+}
+int unet_preproc_filter(const float* src, float* dst, int w, int h, int d, int channels, int kind, int impl, void* stream) {
+    if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
+    if (kind != UNET_PREPROC_GAUSSIAN && kind != UNET_PREPROC_MEAN) return fail("unet_preproc_filter: unknown kind " + std::to_string(kind));
+    if (impl < UNET_PREPROC_IMPL_DEFAULT || impl > UNET_PREPROC_IMPL_VOXEL) return fail("unet_preproc_filter: unknown impl " + std::to_string(impl));
+    if (preproc_filter_blocks(w, h, d, channels) >= ((int64_t)1 << 31)) return fail("unet_preproc_filter: too many tiles for one launch");
+    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_filter(src, dst, w, h, d, channels, kind, impl, s); });
+}
+int unet_preproc_downsample(const float* src, float* dst, int w, int h, int d, int channels, void* stream) {
+    if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
+    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_downsample(src, dst, w, h, d, channels, s); });
+}
+int unet_preproc_upsample(const float* src, float* dst, int w, int h, int d, int channels, void* stream) {
+    if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
+    if (8 * (int64_t)w * h * d >= ((int64_t)1 << 31)) return fail("unet_preproc_upsample: the result must stay below 2^31 voxels");
+    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_upsample(src, dst, w, h, d, channels, s); });
+}
+int unet_preproc_permute(const float* src, float* dst, int w, int h, int d, int channels, int op, void* stream) {
+    if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
+    if (op < UNET_PREPROC_FLIP_X || op > UNET_PREPROC_SWAP_XZ) return fail("unet_preproc_permute: unknown op " + std::to_string(op));
+    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_permute(src, dst, w, h, d, channels, op, s); });
+}
+int unet_preproc_scratch_bytes(int64_t values, size_t* bytes) {
+    if (values <= 0) return fail("unet_preproc: values must be positive");
+    if (!bytes) return fail("unet_preproc_scratch_bytes: null output");
+    *bytes = preproc_scratch_bytes(values);
+    return 0;
+}
+int unet_preproc_normalize(float* buf, int64_t values, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!buf) return fail("unet_preproc_normalize: null device pointer");
+    if (values <= 0) return fail("unet_preproc: values must be positive");
+    if (!scratch) return fail("unet_preproc_normalize: null scratch");
+    if (scratch_bytes < preproc_scratch_bytes(values)) return fail("unet_preproc_normalize: scratch too small (see unet_preproc_scratch_bytes)");
+    return pp_run(buf, stream, [&](hipStream_t s) { launch_preproc_normalize(buf, values, scratch, s); });
+}
+
 }  // extern "C"

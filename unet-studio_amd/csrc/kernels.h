@@ -9,6 +9,7 @@
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
 #include "../../include/unet_postproc.h"
+#include "../../include/unet_preproc.h"
 #include "../../include/unet_qc.h"
 #include "../../include/unet_space.h"
 
@@ -340,5 +341,14 @@ void launch_space_resample(const float* src, int sw, int sh, int sd, float* dst,
                            const UnetSpaceMap& map, int mode, int normalize, void* scratch, hipStream_t s);
 void launch_space_postproc(const float* logits, int C, int mw, int mh, int md, const UnetSpaceMap& map, int nw, int nh, int nd, float thr,
                            float* lp, float* fg, uint16_t* lab, hipStream_t s);
+
+// kernels_preproc.hip: the pre-processing commands of a model (include/unet_preproc.h); w, h, d are the source's dimensions
+int64_t preproc_filter_blocks(int w, int h, int d, int channels);
+size_t preproc_scratch_bytes(int64_t values);
+void launch_preproc_filter(const float* src, float* dst, int w, int h, int d, int channels, int kind, int impl, hipStream_t s);
+void launch_preproc_downsample(const float* src, float* dst, int w, int h, int d, int channels, hipStream_t s);
+void launch_preproc_upsample(const float* src, float* dst, int w, int h, int d, int channels, hipStream_t s);
+void launch_preproc_permute(const float* src, float* dst, int w, int h, int d, int channels, int op, hipStream_t s);
+void launch_preproc_normalize(float* buf, int64_t values, void* scratch, hipStream_t s);
 
 }  // namespace unet

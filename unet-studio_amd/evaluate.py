@@ -1,7 +1,6 @@
 """Inference loop of the reference over the engine: `evaluate_unet::start()` -> `prepare_for_inference`, then
 `evaluate_unet::evaluate()` (evaluate.cpp:386-399, 211-246) for host buffers that are either already at the model's grid or
-`space.NativeVolume`s on the scan's own grid (reading files, handle_orientation, the preproc commands and file output are TIPL
-code and out of scope).
+`space.NativeVolume`s on the scan's own grid (reading files and file output are TIPL code and out of scope).
 
 One `model_io` buffer is a float32 host array of shape (in_count*D, H, W): the input channels stacked along z
 (evaluate.cpp:226-227).  After the forward it holds (out_count*D, H, W): the full-resolution logits [0] of the network, copied
@@ -16,19 +15,28 @@ An entry may be a `space.NativeVolume` (in_count*d, h, w) with its voxel size in
 device (space.to_model_space: read_image_and_label, train.cpp:13-40), run through the forward, and the results come back on ITS grid,
 in the reference's order, handle_fov_post then run_postproc (evaluate.cpp:274): without a chain the logits resampled linear,
 (out_count*d, h, w); with one, the chain on the native grid, its fused softmax / create_mask / argmax group interpolating the
-logits it reads (include/unet_space.h) and every later command unchanged.  Plain arrays take the path above unchanged."""
+logits it reads (include/unet_space.h) and every later command unchanged.  Plain arrays take the path above unchanged.
+
+With `preproc` / `orientation` (chain strings, or "model" for model.preproc / model.orientation; preproc.py) a NativeVolume runs the
+reference's full order (evaluate.cpp:201-204, 274): run_preproc on the device on its own grid, then the model -> image map of the
+preprocessed grid composed with the orientation's map (handle_orientation costs no pass in either direction), the forward, and
+the way back through the inverse of preproc geometry o model -> image o orientation, so the results land on the scan's ORIGINAL
+grid and orientation.  A plain array is already past the read stage: with a preproc or orientation in force it ends the run."""
 import numpy as np
 import torch
 
 from . import engine as E
 from . import postproc as P
+from . import preproc as PRE
 from . import space as SP
 
 
 class EvaluateUNet:
-    def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None):
+    def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None):
         self.model = model
         self.postproc = postproc
+        self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
+        self.orientation = orientation         # a flip / swap chain, "model" for model.orientation, None / "": none
         self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
         self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
@@ -67,6 +75,14 @@ class EvaluateUNet:
                 except E.UNetError as e:
                     self.error_msg, self.aborted, self.running = str(e), True, False
                     return out
+            try:                                           # run_preproc / handle_orientation's failure (evaluate.cpp:201-204)
+                pre = PRE.active(PRE.parse_chain(m.preproc if self.preproc == "model" else self.preproc))
+                ori = PRE.parse_orientation(m.orientation if self.orientation == "model" else self.orientation)
+                D0, vs0, M = PRE.orientation_map(ori, m.dim, m.voxel_size) if ori else (None, None, None)
+            except E.UNetError as e:
+                self.error_msg, self.aborted, self.running = str(e), True, False
+                return out
+            pre_scratch = None                             # normalize's reduction scratch, reused across volumes
             scratch = None                                 # the chain's scratch (defragment, per-plane commands), reused across volumes
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
             with torch.no_grad():                          # evaluate.cpp:221
@@ -77,6 +93,9 @@ class EvaluateUNet:
                         if nv is not None:
                             nv.check()
                             io = nv.data
+                        elif pre or ori:
+                            raise E.UNetError("a plain model_io array is already at the model's grid: preproc / orientation need a "
+                                              "NativeVolume")
                         io = np.ascontiguousarray(io, dtype=np.float32)
                         if io.ndim != 3 or io.shape[0] % m.in_count:
                             raise E.UNetError("model_io buffer must be (in_count*D, H, W), got %s" % (io.shape,))
@@ -84,6 +103,23 @@ class EvaluateUNet:
                         if nv is None:
                             x = torch.from_numpy(io).view(1, m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
                             back = None
+                        elif pre or ori:                                                 # evaluate.cpp:201-204, on the compute stream
+                            native = (d, io.shape[1], io.shape[2])
+                            x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
+                            pdims, pvs, G = PRE.geometry(pre, native[::-1], nv.voxel_size)
+                            if PRE.needs_scratch(pre):
+                                need = PRE.preproc_scratch_bytes(m.in_count * pdims[0] * pdims[1] * pdims[2])
+                                if pre_scratch is None or pre_scratch.numel() < need:
+                                    pre_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                            x = PRE.run_preproc(x, pre, scratch=pre_scratch)
+                            if nv.map is not None:
+                                fwd = nv.map
+                            else:
+                                fwd = SP.model_to_image_map(D0 or m.dim, vs0 or m.voxel_size, pdims, pvs)
+                            if ori:
+                                fwd = SP.compose_map(fwd, M)                             # model voxel -> preprocessed-grid position
+                            back = SP.invert_map(SP.compose_map(G, fwd))                 # original native voxel -> model position
+                            x = SP.to_model_space(m, x, pvs, map=fwd)[0].unsqueeze(0)
                         else:                                                            # read_image_and_label, on the compute stream
                             native = (d, io.shape[1], io.shape[2])
                             fwd = nv.map if nv.map is not None else SP.model_to_image_map(m.dim, m.voxel_size, native[::-1], nv.voxel_size)

@@ -2,8 +2,8 @@
 
 A chain is commands separated by '+', run left to right (the model's default: "softmax+create_mask+argmax").  The definitions are in
 include/unet_postproc.h; they are this project's, and parity with TIPL's run_postproc / softmax / argmax / defragment_by_size_ratio
-/ normalize is not pinned.  Out of scope (TIPL): soft_max, anisotropic_smoothing, defragment_smoothing, and the
-pre-processing, FOV and orientation handling around the chain.
+/ normalize is not pinned.  Out of scope (TIPL): soft_max, anisotropic_smoothing, defragment_smoothing.  The
+pre-processing and orientation handling around the chain are preproc.py's, the FOV handling space.py's.
 
 A result holds up to three outputs: `label_prob` {C-1, D, H, W} fp32 (softmax), `fg_prob` {D, H, W} fp32 (create_mask) and `label`
 {D, H, W} uint16 (argmax).  create_mask and argmax need a softmax earlier in the chain; defragment needs a create_mask before it.
