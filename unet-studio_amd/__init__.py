@@ -22,6 +22,7 @@ from . import postproc  # noqa: F401  (the module: postproc.EXPORTS the symbols 
 from .postproc import parse_chain, run_postproc  # noqa: F401
 from . import preproc  # noqa: F401  (the module: preproc.EXPORTS the symbols of include/unet_preproc.h)
 from .preproc import run_preproc  # noqa: F401
+from . import components  # noqa: F401  (the module: components.EXPORTS the symbols of include/unet_components.h)
 
 
 def save_to_file(model, file_name):

@@ -1,0 +1,75 @@
+"""A model's single_component_label (unet.hpp:23; main.cpp:186 loads it, evaluate.cpp:199 hands it to every evaluation set) on the
+device (include/unet_components.h): every listed class of a label map keeps its largest 6-connected component, the one holding the
+smallest linear index among equal counts, and every other voxel of that class becomes 0.  Unlisted values are never touched.
+
+The definition is this project's; parity with TIPL's evalution_set is not pinned.  All listed classes are labelled
+in one pass over the uint16 label map: IMPL_TILED builds each TILE's union-find in LDS and hooks the tiles together across their
+faces, IMPL_GLOBAL hooks every voxel in global memory (the measured baseline and a second witness of the bits)."""
+import ctypes as C
+
+import torch
+
+from . import engine as E
+from .engine import UNetError
+
+E._sig("unet_components_scratch_bytes", C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_size_t))
+E._sig("unet_components_keep_largest", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_int,
+       C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
+# every symbol include/unet_components.h declares
+EXPORTS = ["unet_components_scratch_bytes", "unet_components_keep_largest"]
+
+IMPL_DEFAULT, IMPL_TILED, IMPL_GLOBAL = 0, 1, 2
+TILE = (32, 8, 8)   # (TX, TY, TZ) of IMPL_TILED: UNET_COMPONENTS_TILE_X / _Y / _Z
+
+
+def resolve(spec, model):
+    """The caller's choice -> a sorted list of distinct classes.  None and () give []; "model" gives model.single_component_label;
+    an iterable of ints gives its entries.  An entry that is 0 or >= model.out_count raises UNetError naming it.  Host only."""
+    if spec is None:
+        return []
+    if isinstance(spec, str):
+        if spec != "model":
+            raise UNetError('single_component: "model" or a list of classes, got %r' % (spec,))
+        spec = model.single_component_label
+    out = set()
+    for v in spec:
+        if isinstance(v, bool) or int(v) != v:
+            raise UNetError("single_component: class %r is not an integer" % (v,))
+        v = int(v)
+        if v <= 0 or v >= model.out_count:
+            raise UNetError("single_component: class %d is not in [1, %d]" % (v, model.out_count - 1))
+        out.add(v)
+    return sorted(out)
+
+
+def components_scratch_bytes(voxels, n_classes):
+    n = C.c_size_t()
+    E.check(E.lib.unet_components_scratch_bytes(int(voxels), int(n_classes), C.byref(n)))
+    return n.value
+
+
+def keep_largest(label, classes, n_classes, removed=None, scratch=None, impl=IMPL_DEFAULT, stream=None):
+    """In place on label, a (D, H, W) uint16 device tensor, on the current stream (or the raw `stream`); returns label.
+    classes: the listed classes (an empty list changes nothing).  removed: a uint32 / int32 device tensor of n_classes entries that
+    receives the voxels zeroed per class.  scratch: a uint8 device tensor of components_scratch_bytes(D*H*W, n_classes) bytes to
+    reuse (one is made when needed)."""
+    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.uint16 and label.is_contiguous() and label.dim() == 3):
+        raise UNetError("components: label must be a contiguous uint16 (D, H, W) device tensor")
+    D, H, W = (int(v) for v in label.shape)
+    if removed is not None and not (torch.is_tensor(removed) and removed.is_cuda and removed.device == label.device
+                                    and removed.dtype in (torch.uint32, torch.int32) and removed.is_contiguous()
+                                    and removed.numel() == int(n_classes)):
+        raise UNetError("components: removed must be a contiguous uint32 device tensor of n_classes entries on label's device")
+    classes = [int(v) for v in classes]
+    need = components_scratch_bytes(D * H * W, n_classes)        # the size checks, before any device work
+    for v in classes:
+        if not 0 <= v < 1 << 32:
+            raise UNetError("components: listed class %d is not in [1, %d]" % (v, int(n_classes) - 1))
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=label.device)
+    st = stream if stream is not None else torch.cuda.current_stream(label.device).cuda_stream
+    arr = (C.c_uint32 * max(1, len(classes)))(*classes)
+    E.check(E.lib.unet_components_keep_largest(W, H, D, label.data_ptr(), int(n_classes), arr, len(classes),
+                                               removed.data_ptr() if removed is not None else None, int(impl), scratch.data_ptr(),
+                                               scratch.numel() * scratch.element_size(), st))
+    return label

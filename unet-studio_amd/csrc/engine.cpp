@@ -2080,4 +2080,40 @@ int unet_preproc_normalize(float* buf, int64_t values, void* scratch, size_t scr
     return pp_run(buf, stream, [&](hipStream_t s) { launch_preproc_normalize(buf, values, scratch, s); });
 }
 
+// ---- a model's single_component_label (include/unet_components.h) ----
+static const char* components_size_error(int64_t voxels, int n_classes) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return "unet_components: voxels must be in [1, 2^31)";
+    if (n_classes < 1 || n_classes > 65536) return "unet_components: n_classes must be in [1, 65536]";
+    return nullptr;
+}
+int unet_components_scratch_bytes(int64_t voxels, int n_classes, size_t* bytes) {
+    if (const char* e = components_size_error(voxels, n_classes)) return fail(e);
+    if (!bytes) return fail("unet_components_scratch_bytes: null output");
+    *bytes = components_scratch_bytes(voxels, n_classes);
+    return 0;
+}
+int unet_components_keep_largest(int w, int h, int d, uint16_t* label, int n_classes, const uint32_t* listed, int n_listed,
+                                 uint32_t* removed, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    if (w <= 0 || h <= 0 || d <= 0) return fail("unet_components: volume dimensions must be positive");
+    if (const char* e = components_size_error((int64_t)w * h * d, n_classes)) return fail(e);
+    if (!label) return fail("unet_components_keep_largest: null label");
+    if (n_listed < 0) return fail("unet_components_keep_largest: n_listed must not be negative");
+    if (n_listed > 0 && !listed) return fail("unet_components_keep_largest: null list");
+    if (impl < UNET_COMPONENTS_IMPL_DEFAULT || impl > UNET_COMPONENTS_IMPL_GLOBAL)
+        return fail("unet_components_keep_largest: unknown impl " + std::to_string(impl));
+    if (!scratch) return fail("unet_components_keep_largest: null scratch");
+    if (scratch_bytes < components_scratch_bytes((int64_t)w * h * d, n_classes))
+        return fail("unet_components_keep_largest: scratch too small (see unet_components_scratch_bytes)");
+    for (int i = 0; i < n_listed; ++i)
+        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
+            return fail("unet_components_keep_largest: listed class " + std::to_string(listed[i]) + " is not in [1, " +
+                        std::to_string(n_classes - 1) + "]");
+    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
+    std::sort(classes.begin(), classes.end());
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    return pp_run(label, stream, [&](hipStream_t s) {
+        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, scratch, s);
+    });
+}
+
 }  // extern "C"

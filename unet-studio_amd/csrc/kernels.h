@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/unet_augment.h"
+#include "../../include/unet_components.h"
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
 #include "../../include/unet_postproc.h"
@@ -350,5 +351,10 @@ void launch_preproc_downsample(const float* src, float* dst, int w, int h, int d
 void launch_preproc_upsample(const float* src, float* dst, int w, int h, int d, int channels, hipStream_t s);
 void launch_preproc_permute(const float* src, float* dst, int w, int h, int d, int channels, int op, hipStream_t s);
 void launch_preproc_normalize(float* buf, int64_t values, void* scratch, hipStream_t s);
+
+// kernels_components.hip: a model's single_component_label (include/unet_components.h); classes: sorted distinct host entries
+size_t components_scratch_bytes(int64_t S, int n_classes);
+void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_classes, const uint32_t* classes, int n,
+                                    uint32_t* removed, int impl, void* scratch, hipStream_t s);
 
 }  // namespace unet

@@ -13,6 +13,7 @@
 //
 // Scratch: UNET_POSTPROC_CHUNK slots per call at most (one for defragment), each {parent int32[S], count uint32[S],
 // partial[PP_MAXB], max}: defragment_each, normalize_each and smoothing go over the planes that many at a time.
+#include "cc_union_find.h"
 #include "device_util.h"
 
 namespace unet {
@@ -21,7 +22,6 @@ namespace {
 
 constexpr int PP_T = 256;          // threads per block
 constexpr int PP_MAXB = 2048;      // grid cap of the streaming kernels (256 CUs x 8 blocks); they stride over the rest
-constexpr int CC_RUN = 16;         // consecutive voxels per thread in the size count
 
 __host__ __device__ inline size_t pp_align(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t pp_slot_bytes(int64_t S) { return 2 * pp_align((size_t)S * 4) + pp_align((PP_MAXB + 1) * 4); }
@@ -129,38 +129,7 @@ __global__ void __launch_bounds__(PP_T) k_pp_argmax_planes(const float* __restri
 }
 
 // ---- connected components --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cc_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cc_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of i, halving the path on the way.  parent[j] <= j always, so every store points j at one of its ancestors
-__device__ __forceinline__ int cc_find(int* parent, int i) {
-    int cur = cc_ld(parent + i);
-    if (cur != i) {
-        int prev = i, next;
-        while (cur > (next = cc_ld(parent + cur))) {
-            cc_st(parent + prev, next);
-            prev = cur;
-            cur = next;
-        }
-    }
-    return cur;
-}
-
-// hook the two trees together: the larger root onto the smaller, only while it still is a root (compare-and-swap)
-__device__ __forceinline__ void cc_union(int* parent, int a, int b) {
-    int ra = cc_find(parent, a), rb = cc_find(parent, b);
-    while (ra != rb) {
-        if (ra < rb) {
-            const int old = atomicCAS(parent + rb, rb, ra);
-            if (old == rb) break;
-            rb = old;
-        } else {
-            const int old = atomicCAS(parent + ra, ra, rb);
-            if (old == ra) break;
-            ra = old;
-        }
-    }
-}
+// cc_ld, cc_st, cc_find, cc_union, cc_count_runs: cc_union_find.h (shared with kernels_components.hip)
 
 // parent = i in the mask (src > thr), -1 outside; count = 0.  blockIdx.y: the plane / slot of this round
 __global__ void __launch_bounds__(PP_T) k_cc_init(const float* __restrict__ src, int64_t S, float thr, int* __restrict__ parent0,
@@ -210,45 +179,7 @@ __global__ void __launch_bounds__(PP_T) k_cc_flatten(int S, int* __restrict__ pa
 __global__ void __launch_bounds__(PP_T) k_cc_count(int S, int* __restrict__ parent0, size_t slot_words) {
     const int* parent = parent0 + blockIdx.y * slot_words;
     unsigned* count = (unsigned*)parent0 + blockIdx.y * slot_words + pp_align((size_t)S * 4) / 4;
-    const int lane = threadIdx.x & 63;
-    // block-uniform trip count: the ballots below span all 64 lanes
-    for (int64_t base = (int64_t)blockIdx.x * PP_T * CC_RUN; base < S; base += (int64_t)gridDim.x * PP_T * CC_RUN) {
-        const int64_t v0 = base + (int64_t)threadIdx.x * CC_RUN;
-        int r[CC_RUN];
-        if (v0 + CC_RUN <= S) {   // the slot is 256-B aligned and v0 a multiple of 16: four 16-B loads
-#pragma unroll
-            for (int q = 0; q < CC_RUN / 4; ++q) {
-                const int4 t = *(const int4*)(parent + v0 + 4 * q);
-                r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < CC_RUN; ++k) r[k] = v0 + k < S ? parent[v0 + k] : -1;
-        }
-        int cur = -1;
-        unsigned n = 0;
-#pragma unroll
-        for (int k = 0; k < CC_RUN; ++k) {
-            if (r[k] != cur) {
-                if (n) atomicAdd(count + cur, n);
-                cur = r[k];
-                n = 0;
-            }
-            n += r[k] >= 0 ? 1u : 0u;
-        }
-        const int key = n ? cur : -1;
-        unsigned long long todo = __ballot(key >= 0);
-        while (todo) {   // wave-uniform: one add per distinct root of the wave
-            const int leader = __ffsll((long long)todo) - 1;
-            const int lk = __shfl(key, leader);
-            const unsigned long long same = __ballot(key == lk);
-            unsigned t = key == lk ? n : 0u;
-            if (__popcll(same) > 1)
-                for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-            if (lane == leader) atomicAdd(count + lk, t);
-            todo &= ~same;
-        }
-    }
+    cc_count_runs<PP_T>(S, parent, count);
 }
 
 __device__ __forceinline__ unsigned block_max_u(unsigned v) {

@@ -21,10 +21,16 @@ With `preproc` / `orientation` (chain strings, or "model" for model.preproc / mo
 reference's full order (evaluate.cpp:201-204, 274): run_preproc on the device on its own grid, then the model -> image map of the
 preprocessed grid composed with the orientation's map (handle_orientation costs no pass in either direction), the forward, and
 the way back through the inverse of preproc geometry o model -> image o orientation, so the results land on the scan's ORIGINAL
-grid and orientation.  A plain array is already past the read stage: with a preproc or orientation in force it ends the run."""
+grid and orientation.  A plain array is already past the read stage: with a preproc or orientation in force it ends the run.
+
+With `single_component` (a list of classes, or "model" for model.single_component_label, which the reference hands to every
+evaluation set before the forward, evaluate.cpp:199; components.py) every listed class of the `label` output keeps its largest
+6-connected component, after the chain and on the grid the chain ran on (the scan's own for a NativeVolume).  It acts on the label
+output only: without a chain (logits) or without "label" among the outputs it changes nothing."""
 import numpy as np
 import torch
 
+from . import components as CMP
 from . import engine as E
 from . import postproc as P
 from . import preproc as PRE
@@ -32,11 +38,13 @@ from . import space as SP
 
 
 class EvaluateUNet:
-    def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None):
+    def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
+                 single_component=None):
         self.model = model
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
         self.orientation = orientation         # a flip / swap chain, "model" for model.orientation, None / "": none
+        self.single_component = single_component   # a list of classes, "model" for model.single_component_label, None: none
         self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
         self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
@@ -79,11 +87,14 @@ class EvaluateUNet:
                 pre = PRE.active(PRE.parse_chain(m.preproc if self.preproc == "model" else self.preproc))
                 ori = PRE.parse_orientation(m.orientation if self.orientation == "model" else self.orientation)
                 D0, vs0, M = PRE.orientation_map(ori, m.dim, m.voxel_size) if ori else (None, None, None)
+                listed = CMP.resolve(self.single_component, m)
             except E.UNetError as e:
                 self.error_msg, self.aborted, self.running = str(e), True, False
                 return out
             pre_scratch = None                             # normalize's reduction scratch, reused across volumes
             scratch = None                                 # the chain's scratch (defragment, per-plane commands), reused across volumes
+            cmp_scratch = None                             # the component labelling's scratch, reused across volumes
+            listed = listed if steps is not None and "label" in self.outputs else []
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
             with torch.no_grad():                          # evaluate.cpp:221
                 while self.cur_prog < len(out) and not self.aborted:
@@ -135,8 +146,13 @@ class EvaluateUNet:
                                 need = P.postproc_scratch_bytes(m.out_count, voxels)
                                 if scratch is None or scratch.numel() < need:
                                     scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                            if listed:
+                                need = CMP.components_scratch_bytes(voxels, m.out_count)
+                                if cmp_scratch is None or cmp_scratch.numel() < need:
+                                    cmp_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
                             results = P.run_postproc(result, steps, outputs=self.outputs, scratch=scratch,
-                                                     native=None if nv is None else (back, native))
+                                                     native=None if nv is None else (back, native),
+                                                     single_component=listed or None, component_scratch=cmp_scratch)
                             results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2]))
                                        for k, v in results.items()}
                         else:

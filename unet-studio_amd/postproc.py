@@ -171,14 +171,19 @@ def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
                                          _ptr(scratch), scratch.numel() * scratch.element_size() if scratch is not None else 0, st))
 
 
-def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None):
+def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
+                 component_scratch=None):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
     scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
     native: (map, (d, h, w)) runs the chain on that grid instead, map taking a native voxel to its position in the logits' grid
     (handle_fov_post before run_postproc, evaluate.cpp:274): every fused softmax / create_mask / argmax group interpolates the logits
     it reads (space.postproc_native), the other commands run unchanged on the native planes, and the scratch is the native grid's.
-    check_chain lets no command read the logits outside a fused group, so they are never stored on the native grid."""
+    check_chain lets no command read the logits outside a fused group, so they are never stored on the native grid.
+    single_component: a list of classes (a model's single_component_label, components.py): after the chain every listed class of
+    the `label` output keeps its largest 6-connected component, on the grid the chain ran on; fg_prob and label_prob are not
+    touched.  None or an empty list, or a chain whose wanted outputs hold no label, make no extra call.  component_scratch: a
+    uint8 device tensor of components.components_scratch_bytes(voxels, C) bytes to reuse."""
     steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
     check_chain(steps)
     outputs = tuple(outputs)
@@ -197,6 +202,10 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
         native_map, (D, H, W) = native[0], SP._shape3(native[1], "native shape")
     S = D * H * W
     postproc_scratch_bytes(out_c, S)   # the class / size checks, before any device work
+    listed = [int(v) for v in single_component] if single_component is not None else []
+    for v in listed:
+        if v <= 0 or v >= out_c:
+            raise UNetError("single_component: class %d is not in [1, %d]" % (v, out_c - 1))
     dev = logits.device
     names = [n for n, _ in steps]
     from_state = argmax_after_change(steps) and "label" in outputs
@@ -253,4 +262,7 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
             param = next(iter(p.values())) if p else 0.0
             plane_op_call(PLANE_OPS[name], param, (W, H, D), lp, out_c - 1, get_scratch())
         i += 1
+    if listed and "label" in outputs:
+        from . import components as CMP
+        CMP.keep_largest(res["label"], listed, out_c, scratch=component_scratch)
     return {k: v for k, v in res.items() if k in outputs}
