@@ -23,6 +23,7 @@ from .postproc import parse_chain, run_postproc  # noqa: F401
 from . import preproc  # noqa: F401  (the module: preproc.EXPORTS the symbols of include/unet_preproc.h)
 from .preproc import run_preproc  # noqa: F401
 from . import components  # noqa: F401  (the module: components.EXPORTS the symbols of include/unet_components.h)
+from . import atlas  # noqa: F401  (the module: atlas.EXPORTS the symbols of include/unet_atlas.h)
 
 
 def save_to_file(model, file_name):

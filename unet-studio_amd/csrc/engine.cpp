@@ -2116,4 +2116,58 @@ int unet_components_keep_largest(int w, int h, int d, uint16_t* label, int n_cla
     });
 }
 
+// ---- the atlas preparation of load_atlas (include/unet_atlas.h) ----
+static const char* atlas_size_error(int64_t voxels, int n_regions, int n_tissues, int max_rounds) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return "unet_atlas: voxels must be in [1, 2^31)";
+    if (n_regions < 0 || n_regions > 65535) return "unet_atlas: n_regions must be in [0, 65535]";
+    if (n_tissues < 1 || n_tissues > 256) return "unet_atlas: n_tissues must be in [1, 256]";
+    if (max_rounds < 0 || max_rounds > 65534) return "unet_atlas: max_rounds must be in [0, 65534]";
+    return nullptr;
+}
+int unet_atlas_scratch_bytes(int64_t voxels, int n_regions, int n_tissues, int max_rounds, size_t* bytes) {
+    if (const char* e = atlas_size_error(voxels, n_regions, n_tissues, max_rounds)) return fail(e);
+    if (!bytes) return fail("unet_atlas_scratch_bytes: null output");
+    *bytes = atlas_scratch_bytes(voxels, n_regions, n_tissues, max_rounds);
+    return 0;
+}
+int unet_atlas_reclassify(int64_t voxels, const void* tissue, int tissue_bytes, uint16_t* atlas, int n_regions, int n_tissues, int flags,
+                          uint32_t* votes, uint32_t* tissue_total, uint32_t* covered, uint8_t* majority, uint32_t* erased, int impl,
+                          void* scratch, size_t scratch_bytes, void* stream) {
+    if (const char* e = atlas_size_error(voxels, n_regions, n_tissues, 0)) return fail(e);
+    if (!tissue) return fail("unet_atlas_reclassify: null tissue");
+    if (tissue_bytes != 1 && tissue_bytes != 2) return fail("unet_atlas_reclassify: tissue_bytes must be 1 or 2, got " + std::to_string(tissue_bytes));
+    if (!atlas) return fail("unet_atlas_reclassify: null atlas");
+    if ((uintptr_t)atlas & 1) return fail("unet_atlas_reclassify: atlas must be 2-byte aligned");
+    if (flags & ~(UNET_ATLAS_CLAMP | UNET_ATLAS_PRESERVE | UNET_ATLAS_COUNT_ONLY))
+        return fail("unet_atlas_reclassify: unknown flags " + std::to_string(flags));
+    if (impl < UNET_ATLAS_IMPL_DEFAULT || impl > UNET_ATLAS_IMPL_GLOBAL) return fail("unet_atlas_reclassify: unknown impl " + std::to_string(impl));
+    if (!scratch) return fail("unet_atlas_reclassify: null scratch");
+    if (scratch_bytes < atlas_scratch_bytes(1, n_regions, n_tissues, 0))   // the tables only: no per-voxel scratch
+        return fail("unet_atlas_reclassify: scratch too small (see unet_atlas_scratch_bytes)");
+    return pp_run(atlas, stream, [&](hipStream_t s) {
+        launch_atlas_reclassify(voxels, tissue, tissue_bytes, atlas, n_regions, n_tissues, flags, votes, tissue_total, covered, majority,
+                                erased, impl, scratch, s);
+    });
+}
+int unet_atlas_grow(int w, int h, int d, const void* tissue, int tissue_bytes, uint16_t* atlas, int n_tissues, int flags,
+                    const uint8_t* grow, int max_rounds, int smooth_rounds, uint32_t* filled, uint32_t* relabelled, uint32_t* info,
+                    void* scratch, size_t scratch_bytes, void* stream) {
+    if (w <= 0 || h <= 0 || d <= 0) return fail("unet_atlas_grow: volume dimensions must be positive");
+    if (const char* e = atlas_size_error((int64_t)w * h * d, 0, n_tissues, max_rounds)) return fail(e);
+    if (smooth_rounds < 0 || smooth_rounds > 16) return fail("unet_atlas_grow: smooth_rounds must be in [0, 16]");
+    if (!tissue) return fail("unet_atlas_grow: null tissue");
+    if (tissue_bytes != 1 && tissue_bytes != 2) return fail("unet_atlas_grow: tissue_bytes must be 1 or 2, got " + std::to_string(tissue_bytes));
+    if (!atlas) return fail("unet_atlas_grow: null atlas");
+    if ((uintptr_t)atlas & 1) return fail("unet_atlas_grow: atlas must be 2-byte aligned");
+    if (flags & ~(UNET_ATLAS_CLAMP | UNET_ATLAS_PRESERVE)) return fail("unet_atlas_grow: unknown flags " + std::to_string(flags));
+    if (!grow) return fail("unet_atlas_grow: null grow list");
+    if (!scratch) return fail("unet_atlas_grow: null scratch");
+    if (scratch_bytes < atlas_scratch_bytes((int64_t)w * h * d, 0, n_tissues, max_rounds))
+        return fail("unet_atlas_grow: scratch too small (see unet_atlas_scratch_bytes)");
+    return pp_run(atlas, stream, [&](hipStream_t s) {   // grow is consumed inside the launcher, before this returns
+        launch_atlas_grow(w, h, d, tissue, tissue_bytes, atlas, n_tissues, flags, grow, max_rounds, smooth_rounds, filled, relabelled,
+                          info, scratch, s);
+    });
+}
+
 }  // extern "C"

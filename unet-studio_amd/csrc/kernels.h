@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "../../include/unet_atlas.h"
 #include "../../include/unet_augment.h"
 #include "../../include/unet_components.h"
 #include "../../include/unet_feed.h"
@@ -356,5 +357,15 @@ void launch_preproc_normalize(float* buf, int64_t values, void* scratch, hipStre
 size_t components_scratch_bytes(int64_t S, int n_classes);
 void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_classes, const uint32_t* classes, int n,
                                     uint32_t* removed, int impl, void* scratch, hipStream_t s);
+
+// kernels_atlas.hip: the atlas preparation of load_atlas (include/unet_atlas.h); grow: n_tissues host flags, read before the return.
+// reclassify uses the tables of the scratch only: atlas_scratch_bytes(1, R, T, 0) serves it
+size_t atlas_scratch_bytes(int64_t S, int n_regions, int n_tissues, int max_rounds);
+void launch_atlas_reclassify(int64_t S, const void* tissue, int tissue_bytes, uint16_t* atlas, int n_regions, int n_tissues, int flags,
+                             uint32_t* votes, uint32_t* total, uint32_t* covered, uint8_t* majority, uint32_t* erased, int impl,
+                             void* scratch, hipStream_t s);
+void launch_atlas_grow(int W, int H, int D, const void* tissue, int tissue_bytes, uint16_t* atlas, int n_tissues, int flags,
+                       const uint8_t* grow, int max_rounds, int smooth_rounds, uint32_t* filled, uint32_t* relabelled, uint32_t* info,
+                       void* scratch, hipStream_t s);
 
 }  // namespace unet
