@@ -10,6 +10,8 @@ from .train import SyntheticVolumes, Trainer, TrainingParam  # noqa: F401
 from . import augment  # noqa: F401
 from . import space  # noqa: F401  (the module: space.EXPORTS the symbols of include/unet_space.h)
 from .space import NativeVolume, model_to_image_map, to_model_space  # noqa: F401
+from . import tiles  # noqa: F401  (the module: tiles.EXPORTS the symbols of include/unet_tiles.h)
+from .tiles import canvas_dims, plan_tiles  # noqa: F401
 from .evaluate import EvaluateUNet  # noqa: F401
 from .augment import AugmentedVolumes, PrefetchedVolumes, visual_perception_augmentation  # noqa: F401
 from . import nz  # noqa: F401

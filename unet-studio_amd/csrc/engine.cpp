@@ -2036,6 +2036,54 @@ int unet_space_postproc(const float* logits, int out_c, int mw, int mh, int md, 
     });
 }
 
+// ---- a scan larger than the model's field of view, in blended tiles (include/unet_tiles.h) ----
+static std::string tiles_args_error(const char* who, const void* tiles, int out_c, int tw, int th, int td, const UnetTilePlan* plan, int cw,
+                                    int ch, int cd) {
+    const std::string w = std::string(who) + ": ";
+    if (!tiles) return w + "null tiles";
+    if (!plan) return w + "null plan";
+    if (out_c < 2) return w + "out_c must be at least 2 (channel 0 is the background)";
+    if (out_c > 65536) return w + "more than 65535 foreground classes do not fit a uint16 label";
+    if (tw <= 0 || th <= 0 || td <= 0) return w + "tile dimensions must be positive";
+    if (tw > UNET_TILES_MAX_DIM || th > UNET_TILES_MAX_DIM || td > UNET_TILES_MAX_DIM)
+        return w + "a tile dimension above " + std::to_string(UNET_TILES_MAX_DIM) + " (the weights must stay exact in fp32)";
+    if (cw <= 0 || ch <= 0 || cd <= 0) return w + "canvas dimensions must be positive";
+    if ((int64_t)cw * ch * cd >= ((int64_t)1 << 31) || space_bricks(cw, ch, cd) > ((int64_t)1 << 30))
+        return w + "the canvas must stay below 2^31 voxels (and 2^30 bricks of 16 x 4 x 4)";
+    const int t[3] = {tw, th, td}, c[3] = {cw, ch, cd};
+    for (int a = 0; a < 3; ++a) {
+        const std::string ax = w + "axis " + "xyz"[a] + ": ";
+        const int n = plan->n[a];
+        const int* o = plan->origin[a];
+        if (n < 1 || n > UNET_TILES_MAX_AXIS) return ax + "n must be in [1, " + std::to_string(UNET_TILES_MAX_AXIS) + "], got " + std::to_string(n);
+        if (o[0] != 0) return ax + "the first origin must be 0";
+        if (o[n - 1] != c[a] - t[a]) return ax + "the last origin must be canvas - tile = " + std::to_string(c[a] - t[a]);
+        for (int i = 1; i < n; ++i) {
+            if (o[i] <= o[i - 1]) return ax + "the origins must ascend";
+            if (o[i] - o[i - 1] > t[a]) return ax + "a gap between tiles " + std::to_string(i - 1) + " and " + std::to_string(i);
+        }
+    }
+    return std::string();
+}
+int unet_tiles_blend(const float* tiles, int out_c, int tw, int th, int td, const UnetTilePlan* plan, int cw, int ch, int cd,
+                     float* canvas, void* stream) {
+    const std::string e = tiles_args_error("unet_tiles_blend", tiles, out_c, tw, th, td, plan, cw, ch, cd);
+    if (!e.empty()) return fail(e);
+    if (!canvas) return fail("unet_tiles_blend: null canvas");
+    const UnetTilePlan p = *plan;
+    return pp_run(tiles, stream, [&](hipStream_t s) { launch_tiles_blend(tiles, out_c, tw, th, td, p, cw, ch, cd, canvas, s); });
+}
+int unet_tiles_postproc(const float* tiles, int out_c, int tw, int th, int td, const UnetTilePlan* plan, int cw, int ch, int cd,
+                        float threshold, float* label_prob, float* fg_prob, uint16_t* label, void* stream) {
+    const std::string e = tiles_args_error("unet_tiles_postproc", tiles, out_c, tw, th, td, plan, cw, ch, cd);
+    if (!e.empty()) return fail(e);
+    if (!label_prob && !fg_prob && !label) return fail("unet_tiles_postproc: no output wanted");
+    const UnetTilePlan p = *plan;
+    return pp_run(tiles, stream, [&](hipStream_t s) {
+        launch_tiles_postproc(tiles, out_c, tw, th, td, p, cw, ch, cd, threshold, label_prob, fg_prob, label, s);
+    });
+}
+
 // ---- the pre-processing commands of a model (include/unet_preproc.h) ----
 static const char* preproc_volume_error(const void* src, const void* dst, int w, int h, int d, int channels) {
     if (!src || !dst) return "unet_preproc: null device pointer";

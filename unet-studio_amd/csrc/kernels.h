@@ -14,6 +14,7 @@
 #include "../../include/unet_preproc.h"
 #include "../../include/unet_qc.h"
 #include "../../include/unet_space.h"
+#include "../../include/unet_tiles.h"
 
 namespace unet {
 
@@ -342,6 +343,12 @@ size_t space_scratch_bytes(int64_t dst_voxels, int channels);
 void launch_space_resample(const float* src, int sw, int sh, int sd, float* dst, int dw, int dh, int dd, int channels,
                            const UnetSpaceMap& map, int mode, int normalize, void* scratch, hipStream_t s);
 void launch_space_postproc(const float* logits, int C, int mw, int mh, int md, const UnetSpaceMap& map, int nw, int nh, int nd, float thr,
+                           float* lp, float* fg, uint16_t* lab, hipStream_t s);
+
+// kernels_tiles.hip: the blend of overlapping tiles onto the canvas, alone and inside the fused pass (include/unet_tiles.h)
+void launch_tiles_blend(const float* tiles, int C, int tw, int th, int td, const UnetTilePlan& plan, int cw, int ch, int cd, float* canvas,
+                        hipStream_t s);
+void launch_tiles_postproc(const float* tiles, int C, int tw, int th, int td, const UnetTilePlan& plan, int cw, int ch, int cd, float thr,
                            float* lp, float* fg, uint16_t* lab, hipStream_t s);
 
 // kernels_preproc.hip: the pre-processing commands of a model (include/unet_preproc.h); w, h, d are the source's dimensions

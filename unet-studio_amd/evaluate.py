@@ -26,7 +26,18 @@ grid and orientation.  A plain array is already past the read stage: with a prep
 With `single_component` (a list of classes, or "model" for model.single_component_label, which the reference hands to every
 evaluation set before the forward, evaluate.cpp:199; components.py) every listed class of the `label` output keeps its largest
 6-connected component, after the chain and on the grid the chain ran on (the scan's own for a NativeVolume).  It acts on the label
-output only: without a chain (logits) or without "label" among the outputs it changes nothing."""
+output only: without a chain (logits) or without "label" among the outputs it changes nothing.
+
+With `fov_strategy="tiles"` (or "model" for a model whose fov_strategy says so; None and "align_top" are the path above) a volume
+larger than the model's field of view is no longer cropped: it is covered by overlapping windows of model.dim whose logits are
+blended (tiles.py, include/unet_tiles.h; the definitions are this project's).  A NativeVolume is preprocessed as above, resampled
+ONCE, with normalize, to the canvas -- the grid at the model's voxel size that covers it -- so the normalisation is global over the
+scan; each tile is an integer crop of the canvas and one forward (the filter packs are reused from the second on); the blended
+canvas logits then take the way back exactly as if the model's grid were the canvas.  A plain array is its own canvas: every dim
+must be at least the model's, and a chain's leading softmax / create_mask / argmax group blends the logits it reads without
+storing them.  `tile_overlap` in [0, 0.5) is the fraction of a tile shared with its neighbour.  A volume that fits the model takes
+today's path bit for bit.  The stack of tile logits costs tiles * out_count * tile_voxels * 4 bytes on the device (27 tiles of
+6 x 128^3: 1.36 GB); the forwards run one tile at a time."""
 import numpy as np
 import torch
 
@@ -35,16 +46,19 @@ from . import engine as E
 from . import postproc as P
 from . import preproc as PRE
 from . import space as SP
+from . import tiles as TL
 
 
 class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
-                 single_component=None):
+                 single_component=None, fov_strategy=None, tile_overlap=0.25):
         self.model = model
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
         self.orientation = orientation         # a flip / swap chain, "model" for model.orientation, None / "": none
         self.single_component = single_component   # a list of classes, "model" for model.single_component_label, None: none
+        self.fov_strategy = fov_strategy       # None / "align_top": one window; "tiles": blended tiles; "model": model.fov_strategy
+        self.tile_overlap = tile_overlap       # the fraction of a tile shared with its neighbour, in [0, 0.5)
         self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
         self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
@@ -88,6 +102,11 @@ class EvaluateUNet:
                 ori = PRE.parse_orientation(m.orientation if self.orientation == "model" else self.orientation)
                 D0, vs0, M = PRE.orientation_map(ori, m.dim, m.voxel_size) if ori else (None, None, None)
                 listed = CMP.resolve(self.single_component, m)
+                fov = m.fov_strategy if self.fov_strategy == "model" else self.fov_strategy
+                if fov not in (None, "", "align_top", "tiles"):
+                    raise E.UNetError("unknown fov_strategy %s" % (fov,))
+                tiled = fov == "tiles"
+                overlap = TL.check_overlap(self.tile_overlap) if tiled else 0.0
             except E.UNetError as e:
                 self.error_msg, self.aborted, self.running = str(e), True, False
                 return out
@@ -96,6 +115,20 @@ class EvaluateUNet:
             cmp_scratch = None                             # the component labelling's scratch, reused across volumes
             listed = listed if steps is not None and "label" in self.outputs else []
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
+            mW, mH, mD = (int(v) for v in m.dim)
+
+            def forward_tiles(xc, plan):
+                """xc {in_count, cd, ch, cw} on the device -> the stack {tiles, out_count, D, H, W} of level-0 logits, one forward
+                per integer crop in tile-index order"""
+                origins = TL.tile_origins(plan)
+                stack = torch.empty((len(origins), m.out_count, mD, mH, mW), dtype=torch.float32, device=self.device)
+                for t, (ox, oy, oz) in enumerate(origins):
+                    crop = xc[:, oz:oz + mD, oy:oy + mH, ox:ox + mW].contiguous().unsqueeze(0)
+                    size = tuple(crop.shape[2:])
+                    stack[t].copy_(m.forward(crop, packs_current=size in packed_sizes)[0].view(m.out_count, mD, mH, mW))
+                    packed_sizes.add(size)
+                return stack
+
             with torch.no_grad():                          # evaluate.cpp:221
                 while self.cur_prog < len(out) and not self.aborted:
                     self.status = "inferencing"
@@ -111,9 +144,40 @@ class EvaluateUNet:
                         if io.ndim != 3 or io.shape[0] % m.in_count:
                             raise E.UNetError("model_io buffer must be (in_count*D, H, W), got %s" % (io.shape,))
                         d = io.shape[0] // m.in_count
-                        if nv is None:
+                        plan = canvas = None                                             # set when this entry runs in more than one tile
+                        if tiled and nv is None:                                         # the array is its own canvas
+                            canvas = (io.shape[2], io.shape[1], d)
+                            if canvas[0] < mW or canvas[1] < mH or canvas[2] < mD:
+                                raise E.UNetError("fov_strategy tiles: a model_io array (w, h, d) = %s is smaller than the model's %s"
+                                                  % (canvas, (mW, mH, mD)))
+                        elif tiled:                                                      # the grid at the model's voxel size that covers the scan
+                            if nv.map is not None:
+                                raise E.UNetError("a caller's map and tiles do not combine")
+                            pdims, pvs, G = PRE.geometry(pre, (io.shape[2], io.shape[1], d), nv.voxel_size)
+                            canvas = TL.canvas_dims(m.dim, m.voxel_size, pdims, pvs, orientation=ori)
+                        if tiled and canvas != (mW, mH, mD):                             # a volume that fits takes the paths below
+                            plan = TL.plan_tiles(canvas, (mW, mH, mD), overlap)
+                        if plan is not None and nv is None:
+                            x = torch.from_numpy(io).view(m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
+                            back = None
+                        elif nv is None:
                             x = torch.from_numpy(io).view(1, m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
                             back = None
+                        elif plan is not None:                                           # run_preproc, then ONE resample to the canvas
+                            native = (d, io.shape[1], io.shape[2])
+                            x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
+                            if pre:
+                                if PRE.needs_scratch(pre):
+                                    need = PRE.preproc_scratch_bytes(m.in_count * pdims[0] * pdims[1] * pdims[2])
+                                    if pre_scratch is None or pre_scratch.numel() < need:
+                                        pre_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                                x = PRE.run_preproc(x, pre, scratch=pre_scratch)
+                            cD0, cvs0, cM = PRE.orientation_map(ori, canvas, m.voxel_size) if ori else (canvas, m.voxel_size, None)
+                            fwd = SP.model_to_image_map(cD0, cvs0, pdims, pvs)           # canvas voxel -> preprocessed-grid position
+                            if ori:
+                                fwd = SP.compose_map(fwd, cM)
+                            back = SP.invert_map(SP.compose_map(G, fwd))                 # original native voxel -> canvas position
+                            x = SP.resample(x, canvas[::-1], fwd, "linear", normalize=True)   # one normalisation over the whole scan
                         elif pre or ori:                                                 # evaluate.cpp:201-204, on the compute stream
                             native = (d, io.shape[1], io.shape[2])
                             x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
@@ -137,11 +201,18 @@ class EvaluateUNet:
                             back = SP.invert_map(fwd)                                    # native voxel -> model position
                             x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
                             x = SP.to_model_space(m, x, nv.voxel_size, map=fwd)[0].unsqueeze(0)
-                        size = tuple(x.shape[2:])
-                        result = m.forward(x, packs_current=size in packed_sizes)[0]     # evaluate.cpp:226-227
-                        packed_sizes.add(size)
+                        stack = None
+                        if plan is not None:                                             # one forward per tile (evaluate.cpp:223-230)
+                            size = canvas[::-1]
+                            stack = forward_tiles(x, plan)
+                            if nv is not None or steps is None:                          # the canvas logits, as if the model's grid were the canvas
+                                result, stack = TL.blend(stack, plan, size), None
+                        else:
+                            size = tuple(x.shape[2:])
+                            result = m.forward(x, packs_current=size in packed_sizes)[0]     # evaluate.cpp:226-227
+                            packed_sizes.add(size)
                         if steps is not None:                                            # evaluate.cpp:274, on the compute stream
-                            voxels = result.numel() // m.out_count if nv is None else d * io.shape[1] * io.shape[2]
+                            voxels = d * io.shape[1] * io.shape[2] if nv is not None or plan is not None else result.numel() // m.out_count
                             if P.needs_scratch(steps):
                                 need = P.postproc_scratch_bytes(m.out_count, voxels)
                                 if scratch is None or scratch.numel() < need:
@@ -150,8 +221,9 @@ class EvaluateUNet:
                                 need = CMP.components_scratch_bytes(voxels, m.out_count)
                                 if cmp_scratch is None or cmp_scratch.numel() < need:
                                     cmp_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            results = P.run_postproc(result, steps, outputs=self.outputs, scratch=scratch,
+                            results = P.run_postproc(result if stack is None else None, steps, outputs=self.outputs, scratch=scratch,
                                                      native=None if nv is None else (back, native),
+                                                     tiles=None if stack is None else (stack, plan, size),
                                                      single_component=listed or None, component_scratch=cmp_scratch)
                             results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2]))
                                        for k, v in results.items()}

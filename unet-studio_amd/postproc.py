@@ -172,7 +172,7 @@ def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
 
 
 def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
-                 component_scratch=None):
+                 component_scratch=None, tiles=None):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
     scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
@@ -183,20 +183,34 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     single_component: a list of classes (a model's single_component_label, components.py): after the chain every listed class of
     the `label` output keeps its largest 6-connected component, on the grid the chain ran on; fg_prob and label_prob are not
     touched.  None or an empty list, or a chain whose wanted outputs hold no label, make no extra call.  component_scratch: a
-    uint8 device tensor of components.components_scratch_bytes(voxels, C) bytes to reuse."""
+    uint8 device tensor of components.components_scratch_bytes(voxels, C) bytes to reuse.
+    tiles: (stack, plan, (D, H, W)) in place of logits (pass None): the volume is the blend of a stack of tile logits (tiles.py,
+    include/unet_tiles.h).  A fused group that starts the chain blends the logits it reads and never stores them
+    (tiles.postproc_tiles); a later group reads the blended canvas logits, made once when first needed.  Not with native."""
     steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
     check_chain(steps)
     outputs = tuple(outputs)
     check_outputs(steps, outputs)
-    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
-        raise UNetError("run_postproc: logits must be a contiguous float32 device tensor")
-    if logits.dim() == 5:
-        if logits.shape[0] != 1:
-            raise UNetError("run_postproc: one volume at a time, got a batch of %d" % logits.shape[0])
-        logits = logits[0]
-    if logits.dim() != 4:
-        raise UNetError("run_postproc: logits must be {C, D, H, W}, got %s" % (tuple(logits.shape),))
-    out_c, D, H, W = (int(v) for v in logits.shape)
+    if tiles is not None:
+        from . import space as SP
+        from . import tiles as TL
+        if logits is not None or native is not None:
+            raise UNetError("run_postproc: tiles come in place of logits and do not combine with native")
+        stack, plan, canvas_shape = tiles
+        D, H, W = canvas_shape = SP._shape3(canvas_shape, "canvas shape")
+        out_c = TL._stack(stack, TL._plan_struct(plan))[0]
+        dev = stack.device
+    else:
+        if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
+            raise UNetError("run_postproc: logits must be a contiguous float32 device tensor")
+        if logits.dim() == 5:
+            if logits.shape[0] != 1:
+                raise UNetError("run_postproc: one volume at a time, got a batch of %d" % logits.shape[0])
+            logits = logits[0]
+        if logits.dim() != 4:
+            raise UNetError("run_postproc: logits must be {C, D, H, W}, got %s" % (tuple(logits.shape),))
+        out_c, D, H, W = (int(v) for v in logits.shape)
+        dev = logits.device
     if native is not None:
         from . import space as SP
         native_map, (D, H, W) = native[0], SP._shape3(native[1], "native shape")
@@ -206,7 +220,6 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     for v in listed:
         if v <= 0 or v >= out_c:
             raise UNetError("single_component: class %d is not in [1, %d]" % (v, out_c - 1))
-    dev = logits.device
     names = [n for n, _ in steps]
     from_state = argmax_after_change(steps) and "label" in outputs
     want_lp = ("label_prob" in outputs or from_state) and "softmax" in names
@@ -240,7 +253,13 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
             thr = run.get("argmax", {}).get("threshold", 0.5)
             fused_lab = lab if not changed else None      # after a change argmax reads the current planes, below
             if lp is not None or fg is not None or fused_lab is not None:
-                if native is None:
+                if tiles is not None and i == 0:
+                    wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
+                    wanted = {k: v for k, v in wanted.items() if v is not None}
+                    TL.postproc_tiles(stack, plan, canvas_shape, thr, tuple(wanted), out=wanted)
+                elif native is None:
+                    if logits is None:                        # a later group of a tiled volume: the canvas logits, made once
+                        logits = TL.blend(stack, plan, canvas_shape)
                     softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
                 else:
                     wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}

@@ -9,8 +9,9 @@ and never stores them.
 
 `model_to_image_map` is this project's stand-in for tipl::transformation_matrix(arg, model_dim, model_vs, image_dim, image_vs)
 (TIPL, not in the reference tree), with the convention augment.affine_matrix uses (centre = dim / 2).  The sampling rules are the
-augmentation's (oracle/augment_ref.py restates them).  Parity with TIPL is NOT pinned for either.  Only
-the model's default fov_strategy "align_top" (unet.cpp:110) is covered and reading files stays out of scope.  A model's preproc
+augmentation's (oracle/augment_ref.py restates them).  Parity with TIPL is NOT pinned for either.  These
+maps are the model's default fov_strategy "align_top" (unet.cpp:110): one window of model.dim, whatever lies outside it cropped.
+A scan larger than that window is tiles.py's (EvaluateUNet(fov_strategy="tiles")); reading files stays out of scope.  A model's preproc
 chain and orientation are preproc.py's: EvaluateUNet(preproc=, orientation=) folds them into these maps with `invert_map` /
 `compose_map`, which also let a caller fold a NIfTI transform into the map.
 
