@@ -2218,4 +2218,94 @@ int unet_atlas_grow(int w, int h, int d, const void* tissue, int tissue_bytes, u
     });
 }
 
+// ---- the parcellation of a subject (include/unet_register.h) ----
+static std::string reg_grids_error(const char* who, const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes,
+                                   int tw, int th, int td, int n_tissues) {
+    const std::string w = std::string(who) + ": ";
+    if (!subject) return w + "null subject";
+    if (!tmpl) return w + "null template";
+    if (sbytes != 1 && sbytes != 2) return w + "sbytes must be 1 or 2, got " + std::to_string(sbytes);
+    if (tbytes != 1 && tbytes != 2) return w + "tbytes must be 1 or 2, got " + std::to_string(tbytes);
+    if (sw <= 0 || sh <= 0 || sd <= 0) return w + "subject dimensions must be positive";
+    if (tw <= 0 || th <= 0 || td <= 0) return w + "template dimensions must be positive";
+    if ((int64_t)sw * sh * sd >= ((int64_t)1 << 31)) return w + "the subject grid must stay below 2^31 voxels";
+    if ((int64_t)tw * th * td >= ((int64_t)1 << 31)) return w + "the template grid must stay below 2^31 voxels";
+    if (n_tissues < 2 || n_tissues > UNET_REG_MAX_TISSUES) return w + "n_tissues must be in [2, 16], got " + std::to_string(n_tissues);
+    return std::string();
+}
+static bool reg_stride_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+int unet_reg_scratch_bytes(int64_t subject_voxels, int n_tissues, int max_iterations, size_t* bytes) {
+    if (subject_voxels <= 0 || subject_voxels >= ((int64_t)1 << 31)) return fail("unet_reg: subject_voxels must be in [1, 2^31)");
+    if (n_tissues < 2 || n_tissues > UNET_REG_MAX_TISSUES) return fail("unet_reg: n_tissues must be in [2, 16], got " + std::to_string(n_tissues));
+    if (max_iterations < 1 || max_iterations > UNET_REG_MAX_ITERATIONS) return fail("unet_reg: max_iterations must be in [1, 1024]");
+    if (!bytes) return fail("unet_reg_scratch_bytes: null output");
+    *bytes = reg_scratch_bytes(n_tissues);   // the state and the counters: nothing per voxel, nothing per iteration
+    return 0;
+}
+int unet_reg_hist(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                  int n_tissues, const float* maps, int K, int stride, uint32_t* hist, int impl, void* scratch, size_t scratch_bytes,
+                  void* stream) {
+    (void)scratch; (void)scratch_bytes;   // reserved
+    const std::string e = reg_grids_error("unet_reg_hist", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (!maps) return fail("unet_reg_hist: null maps");
+    if (K < 1 || K > UNET_REG_MAX_MAPS) return fail("unet_reg_hist: K must be in [1, 25], got " + std::to_string(K));
+    if (!reg_stride_ok(stride)) return fail("unet_reg_hist: stride must be 1, 2, 4 or 8, got " + std::to_string(stride));
+    if (!hist) return fail("unet_reg_hist: null hist");
+    if ((uintptr_t)hist & 3) return fail("unet_reg_hist: hist must be 4-byte aligned");
+    if (impl < UNET_REG_IMPL_DEFAULT || impl > UNET_REG_IMPL_GLOBAL) return fail("unet_reg_hist: unknown impl " + std::to_string(impl));
+    return pp_run(hist, stream, [&](hipStream_t s) {   // maps is consumed inside the launcher, before this returns
+        launch_reg_hist(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, maps, K, stride, hist, impl, s);
+    });
+}
+int unet_reg_search(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                    int n_tissues, const float* init, const float* step, const int* stages, int n_stages, int max_iterations,
+                    float* map_out, int64_t* trace, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string e = reg_grids_error("unet_reg_search", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (!init) return fail("unet_reg_search: null init");
+    if (!step) return fail("unet_reg_search: null step");
+    bool any = false;
+    for (int i = 0; i < 12; ++i) {
+        if (!std::isfinite(step[i]) || step[i] < 0.f) return fail("unet_reg_search: step[" + std::to_string(i) + "] must be finite and >= 0");
+        any |= step[i] > 0.f;
+    }
+    if (!any) return fail("unet_reg_search: at least one step must be > 0");
+    if (n_stages < 1 || n_stages > UNET_REG_MAX_STAGES) return fail("unet_reg_search: n_stages must be in [1, 4], got " + std::to_string(n_stages));
+    if (!stages) return fail("unet_reg_search: null stages");
+    for (int g = 0; g < n_stages; ++g) {
+        const std::string st = "unet_reg_search: stage " + std::to_string(g) + ": ";
+        if (!reg_stride_ok(stages[3 * g])) return fail(st + "stride must be 1, 2, 4 or 8, got " + std::to_string(stages[3 * g]));
+        if (stages[3 * g + 1] < 0 || stages[3 * g + 1] > stages[3 * g + 2] || stages[3 * g + 2] > UNET_REG_MAX_LEVEL)
+            return fail(st + "levels must satisfy 0 <= first_level <= last_level <= 20");
+    }
+    if (max_iterations < 1 || max_iterations > UNET_REG_MAX_ITERATIONS) return fail("unet_reg_search: max_iterations must be in [1, 1024]");
+    if (!map_out) return fail("unet_reg_search: null map_out");
+    if ((uintptr_t)map_out & 3) return fail("unet_reg_search: map_out must be 4-byte aligned");
+    if ((uintptr_t)trace & 7) return fail("unet_reg_search: trace must be 8-byte aligned");
+    if (!info) return fail("unet_reg_search: null info");
+    if ((uintptr_t)info & 7) return fail("unet_reg_search: info must be 8-byte aligned");
+    if (impl < UNET_REG_IMPL_DEFAULT || impl > UNET_REG_IMPL_GLOBAL) return fail("unet_reg_search: unknown impl " + std::to_string(impl));
+    if (!scratch) return fail("unet_reg_search: null scratch");
+    if (scratch_bytes < reg_scratch_bytes(n_tissues)) return fail("unet_reg_search: scratch too small (see unet_reg_scratch_bytes)");
+    return pp_run(map_out, stream, [&](hipStream_t s) {   // init, step and stages are consumed inside the launcher
+        launch_reg_search(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, init, step, stages, n_stages, max_iterations,
+                          map_out, trace, info, impl, scratch, s);
+    });
+}
+int unet_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                   const uint16_t* atlas, int n_tissues, const float* map, uint16_t* out, uint32_t* counts, void* stream) {
+    const std::string e = reg_grids_error("unet_reg_carry", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (!atlas) return fail("unet_reg_carry: null atlas");
+    if ((uintptr_t)atlas & 1) return fail("unet_reg_carry: atlas must be 2-byte aligned");
+    if (!map) return fail("unet_reg_carry: null map");
+    if (!out) return fail("unet_reg_carry: null out");
+    if ((uintptr_t)out & 1) return fail("unet_reg_carry: out must be 2-byte aligned");
+    if ((uintptr_t)counts & 3) return fail("unet_reg_carry: counts must be 4-byte aligned");
+    return pp_run(out, stream, [&](hipStream_t s) {   // map is consumed inside the launcher
+        launch_reg_carry(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, atlas, n_tissues, map, out, counts, s);
+    });
+}
+
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "../../include/unet_postproc.h"
 #include "../../include/unet_preproc.h"
 #include "../../include/unet_qc.h"
+#include "../../include/unet_register.h"
 #include "../../include/unet_space.h"
 #include "../../include/unet_tiles.h"
 
@@ -374,5 +375,16 @@ void launch_atlas_reclassify(int64_t S, const void* tissue, int tissue_bytes, ui
 void launch_atlas_grow(int W, int H, int D, const void* tissue, int tissue_bytes, uint16_t* atlas, int n_tissues, int flags,
                        const uint8_t* grow, int max_rounds, int smooth_rounds, uint32_t* filled, uint32_t* relabelled, uint32_t* info,
                        void* scratch, hipStream_t s);
+
+// kernels_register.hip: the parcellation of a subject (include/unet_register.h); maps, init, step, stages, map: host arrays, read
+// before the return.  Only the search uses scratch
+size_t reg_scratch_bytes(int n_tissues);
+void launch_reg_hist(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                     int n_tissues, const float* maps, int K, int stride, uint32_t* hist, int impl, hipStream_t s);
+void launch_reg_search(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                       int n_tissues, const float* init, const float* step, const int* stages, int n_stages, int max_iterations,
+                       float* map_out, int64_t* trace, int64_t* info, int impl, void* scratch, hipStream_t s);
+void launch_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                      const uint16_t* atlas, int n_tissues, const float* map, uint16_t* out, uint32_t* counts, hipStream_t s);
 
 }  // namespace unet
