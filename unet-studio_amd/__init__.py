@@ -27,6 +27,7 @@ from .preproc import run_preproc  # noqa: F401
 from . import components  # noqa: F401  (the module: components.EXPORTS the symbols of include/unet_components.h)
 from . import atlas  # noqa: F401  (the module: atlas.EXPORTS the symbols of include/unet_atlas.h)
 from . import register  # noqa: F401  (the module: register.EXPORTS the symbols of include/unet_register.h)
+from . import table  # noqa: F401  (the module: table.EXPORTS the symbols of include/unet_table.h)
 
 
 def save_to_file(model, file_name):

@@ -2308,4 +2308,50 @@ int unet_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, cons
     });
 }
 
+// ---- the tables of a label map (include/unet_table.h) ----
+static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
+                                      size_t scratch_bytes) {
+    if (voxels >= ((int64_t)1 << 31)) return w + "the grid must stay below 2^31 voxels";
+    if (n_labels < 1 || n_labels > UNET_TABLE_MAX_LABELS) return w + "n_labels must be in [1, 65535], got " + std::to_string(n_labels);
+    if (!rows) return w + "null rows";
+    if ((uintptr_t)rows & 7) return w + "rows must be 8-byte aligned";
+    if (impl < UNET_TABLE_IMPL_DEFAULT || impl > UNET_TABLE_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
+    if (!scratch) return w + "null scratch";
+    if (scratch_bytes < table_scratch_bytes(n_labels)) return w + "scratch too small (see unet_table_scratch_bytes)";
+    return std::string();
+}
+int unet_table_scratch_bytes(int64_t voxels, int n_labels, size_t* bytes) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail("unet_table: voxels must be in [1, 2^31)");
+    if (n_labels < 1 || n_labels > UNET_TABLE_MAX_LABELS) return fail("unet_table: n_labels must be in [1, 65535], got " + std::to_string(n_labels));
+    if (!bytes) return fail("unet_table_scratch_bytes: null output");
+    *bytes = table_scratch_bytes(n_labels);   // the running table: nothing per voxel
+    return 0;
+}
+int unet_table_regions(const void* labels, int label_bytes, int w, int h, int d, int n_labels, int64_t* rows, int impl, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_table_regions: ";
+    if (!labels) return fail(who + "null labels");
+    if (label_bytes != 1 && label_bytes != 2) return fail(who + "label_bytes must be 1 or 2, got " + std::to_string(label_bytes));
+    if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions must be positive");
+    const std::string e = table_common_error(who, (int64_t)w * h * d, n_labels, rows, impl, scratch, scratch_bytes);
+    if (!e.empty()) return fail(e);
+    return pp_run(labels, stream, [&](hipStream_t s) {
+        launch_table_regions(labels, label_bytes, w, h, d, n_labels, rows, impl, scratch, s);
+    });
+}
+int unet_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, int64_t voxels, int n_labels, int64_t* rows, int impl,
+                       void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_table_overlap: ";
+    if (!a) return fail(who + "null a");
+    if (!b) return fail(who + "null b");
+    if (a_bytes != 1 && a_bytes != 2) return fail(who + "a_bytes must be 1 or 2, got " + std::to_string(a_bytes));
+    if (b_bytes != 1 && b_bytes != 2) return fail(who + "b_bytes must be 1 or 2, got " + std::to_string(b_bytes));
+    if (voxels <= 0) return fail(who + "voxels must be positive");
+    const std::string e = table_common_error(who, voxels, n_labels, rows, impl, scratch, scratch_bytes);
+    if (!e.empty()) return fail(e);
+    return pp_run(a, stream, [&](hipStream_t s) {
+        launch_table_overlap(a, a_bytes, b, b_bytes, voxels, n_labels, rows, impl, scratch, s);
+    });
+}
+
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "../../include/unet_qc.h"
 #include "../../include/unet_register.h"
 #include "../../include/unet_space.h"
+#include "../../include/unet_table.h"
 #include "../../include/unet_tiles.h"
 
 namespace unet {
@@ -386,5 +387,12 @@ void launch_reg_search(const void* subject, int sbytes, int sw, int sh, int sd, 
                        float* map_out, int64_t* trace, int64_t* info, int impl, void* scratch, hipStream_t s);
 void launch_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
                       const uint16_t* atlas, int n_tissues, const float* map, uint16_t* out, uint32_t* counts, hipStream_t s);
+
+// kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
+size_t table_scratch_bytes(int n_labels);
+void launch_table_regions(const void* labels, int label_bytes, int w, int h, int d, int n_labels, int64_t* rows, int impl, void* scratch,
+                          hipStream_t s);
+void launch_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, int64_t voxels, int n_labels, int64_t* rows, int impl,
+                          void* scratch, hipStream_t s);
 
 }  // namespace unet

@@ -37,7 +37,18 @@ canvas logits then take the way back exactly as if the model's grid were the can
 must be at least the model's, and a chain's leading softmax / create_mask / argmax group blends the logits it reads without
 storing them.  `tile_overlap` in [0, 0.5) is the fraction of a tile shared with its neighbour.  A volume that fits the model takes
 today's path bit for bit.  The stack of tile logits costs tiles * out_count * tile_voxels * 4 bytes on the device (27 tiles of
-6 x 128^3: 1.36 GB); the forwards run one tile at a time."""
+6 x 128^3: 1.36 GB); the forwards run one tile at a time.
+
+With `atlas` (a register.Atlas: atlas.prepare_atlas's products on the device) the loop ends where `--template ... --atlas ...` is
+meant to (evaluate.cpp:488-496): `outputs` may also name "atlas" and "regions".  When one is wanted, for every buffer, after the chain and
+single_component and on the grid the chain ran on, register.parcellate carries the atlas onto the final label (the voxel size is
+the NativeVolume's, model.voxel_size for a plain array, tiled or not; `atlas_options` holds parcellate's keywords, `init` among
+them) and table.regions tabulates the result, in the stream the chain ran in.  "atlas" comes back uint16 (d, h, w); "regions" as a
+dict: table int64 {n_regions + 1, 10} (table.py's columns), volume_mm3 float64, report (parcellate's) and tissue_dice, float64
+2 * agree / (subject foreground + sampled template foreground) from one register.joint_hist at the map found, so that a failed
+registration is visible.  The label is produced for the stage whether or not it is among the wanted outputs and copied back only
+when it is.  parcellate synchronises with the host twice per buffer (the map, then its reports): the copy of the previous
+buffer's results still runs under the forward, but the host does not run ahead of this stage.  Without `atlas` nothing changes."""
 import numpy as np
 import torch
 
@@ -45,13 +56,15 @@ from . import components as CMP
 from . import engine as E
 from . import postproc as P
 from . import preproc as PRE
+from . import register as REG
 from . import space as SP
+from . import table as TAB
 from . import tiles as TL
 
 
 class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
-                 single_component=None, fov_strategy=None, tile_overlap=0.25):
+                 single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None):
         self.model = model
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
@@ -59,6 +72,8 @@ class EvaluateUNet:
         self.single_component = single_component   # a list of classes, "model" for model.single_component_label, None: none
         self.fov_strategy = fov_strategy       # None / "align_top": one window; "tiles": blended tiles; "model": model.fov_strategy
         self.tile_overlap = tile_overlap       # the fraction of a tile shared with its neighbour, in [0, 0.5)
+        self.atlas = atlas                     # a register.Atlas: the outputs "atlas" and "regions" become available
+        self.atlas_options = atlas_options     # register.parcellate's keywords (init, step, stages, max_iterations, ...)
         self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
         self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
@@ -79,21 +94,40 @@ class EvaluateUNet:
         copy_stream = torch.cuda.Stream(self.device)
 
         def land(p):
-            fi, bi, hosts, ev = p
+            fi, bi, hosts, ev, extra = p
             ev.synchronize()
             # views of the pinned buffers the copies landed in (owned by the arrays)
             res = {k: host.numpy().reshape(shape) for k, (host, shape) in hosts.items()}
+            if "regions" in res:                           # the host arithmetic on the table and on the histogram at the map found
+                hist = res.pop("tissue_hist").view(np.uint32)[0].astype(np.int64)
+                agree = int(np.trace(hist)) - int(hist[0, 0])
+                both = int(hist[1:].sum()) + int(hist[:, 1:].sum())
+                res["regions"] = dict(table=res["regions"], volume_mm3=TAB.volumes_mm3(res["regions"], extra["voxel_size"]),
+                                      report=extra["report"], tissue_dice=np.float64(2.0 * agree / both) if both else np.float64("nan"))
             out[fi][bi] = res[None] if None in res else res
 
         try:
             m = self.model
             chain = m.postproc if self.postproc == "model" else self.postproc
             steps = None
+            staged = tuple(o for o in self.outputs if o in ("atlas", "regions"))          # the atlas stage's outputs
+            chain_outputs = tuple(o for o in self.outputs if o not in staged)
+            atl = self.atlas
+            if atl is not None and "label" not in chain_outputs:
+                chain_outputs += ("label",)                # the stage reads it; it is copied back only when wanted
+            if staged and atl is None:
+                self.error_msg, self.aborted, self.running = "output %s needs an atlas" % staged[0], True, False
+                return out
+            if atl is not None and not chain:
+                self.error_msg, self.aborted, self.running = "an atlas needs a postproc chain that produces a label", True, False
+                return out
             if chain:
                 try:                                       # a bad chain ends the run as run_postproc's failure does (evaluate.cpp:274)
                     steps = P.parse_chain(chain, self.params)
                     P.check_chain(steps)
-                    P.check_outputs(steps, self.outputs)
+                    P.check_outputs(steps, chain_outputs)
+                    if atl is not None and not isinstance(atl, REG.Atlas):
+                        raise E.UNetError("atlas must be a register.Atlas")
                 except E.UNetError as e:
                     self.error_msg, self.aborted, self.running = str(e), True, False
                     return out
@@ -113,7 +147,8 @@ class EvaluateUNet:
             pre_scratch = None                             # normalize's reduction scratch, reused across volumes
             scratch = None                                 # the chain's scratch (defragment, per-plane commands), reused across volumes
             cmp_scratch = None                             # the component labelling's scratch, reused across volumes
-            listed = listed if steps is not None and "label" in self.outputs else []
+            listed = listed if steps is not None and "label" in chain_outputs else []
+            tab_scratch = None                             # the region table's scratch, reused across volumes
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
             mW, mH, mD = (int(v) for v in m.dim)
 
@@ -221,13 +256,31 @@ class EvaluateUNet:
                                 need = CMP.components_scratch_bytes(voxels, m.out_count)
                                 if cmp_scratch is None or cmp_scratch.numel() < need:
                                     cmp_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            results = P.run_postproc(result if stack is None else None, steps, outputs=self.outputs, scratch=scratch,
+                            results = P.run_postproc(result if stack is None else None, steps, outputs=chain_outputs, scratch=scratch,
                                                      native=None if nv is None else (back, native),
                                                      tiles=None if stack is None else (stack, plan, size),
                                                      single_component=listed or None, component_scratch=cmp_scratch)
-                            results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2]))
-                                       for k, v in results.items()}
+                            extra = {}
+                            if atl is not None and staged:                               # the atlas stage, on the compute stream
+                                label = results["label"].view(d, io.shape[1], io.shape[2])
+                                vs = nv.voxel_size if nv is not None else m.voxel_size
+                                parc, report = REG.parcellate(label, vs, atl.template, atl.template_vs, atl.regions, atl.n_tissues,
+                                                              **dict(self.atlas_options or {}))
+                                if "atlas" in staged:
+                                    results["atlas"] = parc
+                                if "regions" in staged:
+                                    need = TAB.table_scratch_bytes(voxels, atl.n_regions)
+                                    if tab_scratch is None or tab_scratch.numel() < need:
+                                        tab_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                                    results["regions"] = TAB.regions(parc, atl.n_regions, scratch=tab_scratch)
+                                    results["tissue_hist"] = REG.joint_hist(label, atl.template, atl.n_tissues,
+                                                                            [np.concatenate(report["map"])]).view(torch.int32)
+                                    extra = dict(report=report, voxel_size=tuple(float(v) for v in vs))
+                            results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2])
+                                           if k in P.OUTPUTS or k == "atlas" else tuple(v.shape))
+                                       for k, v in results.items() if k in self.outputs or k == "tissue_hist"}
                         else:
+                            extra = {}
                             if nv is not None:                                           # handle_fov_post alone: the logits on the native grid
                                 result = SP.resample(result.view(m.out_count, *size), native, back, "linear")
                             results = {None: (result, (m.out_count * d, io.shape[1], io.shape[2]))}
@@ -249,7 +302,7 @@ class EvaluateUNet:
                             ev.record(copy_stream)
                         if pending is not None:
                             land(pending)
-                        pending = (self.cur_prog, i, hosts, ev)
+                        pending = (self.cur_prog, i, hosts, ev, extra)
                     self.cur_prog += 1
                 if pending is not None:
                     land(pending)

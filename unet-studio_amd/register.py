@@ -165,6 +165,34 @@ def carry(subject, template, atlas, n_tissues, map, counts=True, out=None, strea
     return regions.view(subject.shape), (cnt.view(3, T) if counts else None)
 
 
+class Atlas:
+    """What atlas.prepare_atlas leaves for an evaluation (EvaluateUNet's `atlas`): the template's tissue map and the corrected atlas
+    on its grid, as device tensors, and the template's voxel size (x, y, z).  n_regions: the atlas's largest id; None reads it from
+    the atlas once, here (a host synchronisation)."""
+
+    def __init__(self, template, template_vs, regions, n_tissues=5, n_regions=None):
+        if not (torch.is_tensor(template) and template.is_cuda and template.dtype in (torch.uint8, torch.uint16) and template.dim() == 3
+                and template.is_contiguous() and template.numel() > 0):
+            raise UNetError("register.Atlas: template must be a contiguous (D, H, W) uint8 or uint16 device tensor")
+        if not (torch.is_tensor(regions) and regions.is_cuda and regions.device == template.device and regions.dtype == torch.uint16
+                and regions.is_contiguous() and tuple(regions.shape) == tuple(template.shape)):
+            raise UNetError("register.Atlas: regions must be a contiguous uint16 device tensor of the template's shape, on its device")
+        try:
+            vs = tuple(float(v) for v in template_vs)
+        except (TypeError, ValueError):
+            vs = ()
+        if len(vs) != 3 or not all(np.isfinite(v) and v > 0 for v in vs):
+            raise UNetError("register.Atlas: template_vs must be three positive finite numbers")
+        if isinstance(n_tissues, bool) or int(n_tissues) != n_tissues or not 2 <= int(n_tissues) <= MAX_TISSUES:
+            raise UNetError("register.Atlas: n_tissues must be in [2, %d], got %r" % (MAX_TISSUES, n_tissues))
+        if n_regions is None:
+            n_regions = max(int(regions.to(torch.int32).max().item()), 1)
+        if isinstance(n_regions, bool) or int(n_regions) != n_regions or not 1 <= int(n_regions) <= 65535:
+            raise UNetError("register.Atlas: n_regions must be in [1, 65535], got %r" % (n_regions,))
+        self.template, self.template_vs, self.regions = template, vs, regions
+        self.n_tissues, self.n_regions = int(n_tissues), int(n_regions)
+
+
 def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissues=5, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES,
                max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT):
     """The atlas's regions on the subject's grid.  subject_tissue: the subject's tissue map (an evaluation's label output), template:
