@@ -28,6 +28,7 @@ from . import components  # noqa: F401  (the module: components.EXPORTS the symb
 from . import atlas  # noqa: F401  (the module: atlas.EXPORTS the symbols of include/unet_atlas.h)
 from . import register  # noqa: F401  (the module: register.EXPORTS the symbols of include/unet_register.h)
 from . import table  # noqa: F401  (the module: table.EXPORTS the symbols of include/unet_table.h)
+from . import distance  # noqa: F401  (the module: distance.EXPORTS the symbols of include/unet_distance.h)
 
 
 def save_to_file(model, file_name):

@@ -2354,4 +2354,73 @@ int unet_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, i
     });
 }
 
+// ---- the boundary distances of label maps (include/unet_distance.h) ----
+static std::string dist_grid_error(const std::string& w_, const void* map, const char* name, int bytes, int w, int h, int d) {
+    if (!map) return w_ + "null " + name;
+    if (bytes != 1 && bytes != 2) return w_ + name + "_bytes must be 1 or 2, got " + std::to_string(bytes);
+    if (w <= 0 || h <= 0 || d <= 0) return w_ + "dimensions (w, h, d) must be positive";
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return w_ + "the grid (w, h, d) must stay below 2^31 voxels";
+    return std::string();
+}
+static std::string dist_label_error(const std::string& w_, const char* name, int label) {
+    if (label < 1 || label > UNET_DIST_MAX_LABEL) return w_ + name + " must be in [1, 65535], got " + std::to_string(label);
+    return std::string();
+}
+int unet_dist_scratch_bytes(int w, int h, int d, size_t* bytes) {
+    if (w <= 0 || h <= 0 || d <= 0) return fail("unet_dist_scratch_bytes: dimensions (w, h, d) must be positive");
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return fail("unet_dist_scratch_bytes: the grid (w, h, d) must stay below 2^31 voxels");
+    if (!bytes) return fail("unet_dist_scratch_bytes: null bytes");
+    *bytes = dist_scratch_bytes((int64_t)w * h * d);   // one int32 per voxel between the passes
+    return 0;
+}
+int unet_dist_transform(const void* labels, int label_bytes, int w, int h, int d, int label, int of, int wx, int wy, int wz, int32_t* out,
+                        int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_dist_transform: ";
+    std::string e = dist_grid_error(who, labels, "label", label_bytes, w, h, d);
+    if (!labels) e = who + "null labels";
+    if (e.empty()) e = dist_label_error(who, "label", label);
+    if (!e.empty()) return fail(e);
+    if (of != UNET_DIST_OF_SURFACE && of != UNET_DIST_OF_LABEL) return fail(who + "unknown of " + std::to_string(of));
+    if (wx <= 0 || wy <= 0 || wz <= 0)
+        return fail(who + "weights (wx, wy, wz) must be positive, got " + std::to_string(wx) + ", " + std::to_string(wy) + ", " + std::to_string(wz));
+    // the largest squared distance of the grid, in 128 bits: each term stays below 2^31 * 2^62
+    const auto sq = [](int n) { return (unsigned __int128)((uint64_t)(n - 1) * (uint64_t)(n - 1)); };
+    if (sq(w) * (unsigned)wx + sq(h) * (unsigned)wy + sq(d) * (unsigned)wz >= (unsigned __int128)UNET_DIST_INF)
+        return fail(who + "weights (wx, wy, wz): wx (w-1)^2 + wy (h-1)^2 + wz (d-1)^2 must stay below 2^31 - 1");
+    if (!out) return fail(who + "null out");
+    if ((uintptr_t)out & 3) return fail(who + "out must be 4-byte aligned");
+    if (impl < UNET_DIST_IMPL_DEFAULT || impl > UNET_DIST_IMPL_GLOBAL) return fail(who + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(who + "null scratch");
+    if (scratch_bytes < dist_scratch_bytes((int64_t)w * h * d)) return fail(who + "scratch too small (see unet_dist_scratch_bytes)");
+    return pp_run(labels, stream, [&](hipStream_t s) {
+        launch_dist_transform(labels, label_bytes, w, h, d, label, of, wx, wy, wz, out, impl, scratch, s);
+    });
+}
+int unet_dist_surface_counts(const void* a, int a_bytes, const void* b, int b_bytes, int w, int h, int d, int n_labels, int64_t* rows,
+                             void* stream) {
+    const std::string who = "unet_dist_surface_counts: ";
+    std::string e = dist_grid_error(who, a, "a", a_bytes, w, h, d);
+    if (e.empty()) e = dist_grid_error(who, b, "b", b_bytes, w, h, d);
+    if (e.empty()) e = dist_label_error(who, "n_labels", n_labels);
+    if (!e.empty()) return fail(e);
+    if (!rows) return fail(who + "null rows");
+    if ((uintptr_t)rows & 7) return fail(who + "rows must be 8-byte aligned");
+    return pp_run(a, stream, [&](hipStream_t s) { launch_dist_surface_counts(a, a_bytes, b, b_bytes, w, h, d, n_labels, rows, s); });
+}
+int unet_dist_gather(const void* at, int at_bytes, int w, int h, int d, int label, const int32_t* dist, int32_t* values, int64_t capacity,
+                     unsigned long long* cursor, void* stream) {
+    const std::string who = "unet_dist_gather: ";
+    std::string e = dist_grid_error(who, at, "at", at_bytes, w, h, d);
+    if (e.empty()) e = dist_label_error(who, "label", label);
+    if (!e.empty()) return fail(e);
+    if (!dist) return fail(who + "null dist");
+    if ((uintptr_t)dist & 3) return fail(who + "dist must be 4-byte aligned");
+    if (!values) return fail(who + "null values");
+    if ((uintptr_t)values & 3) return fail(who + "values must be 4-byte aligned");
+    if (capacity < 0) return fail(who + "capacity must not be negative, got " + std::to_string(capacity));
+    if (!cursor) return fail(who + "null cursor");
+    if ((uintptr_t)cursor & 7) return fail(who + "cursor must be 8-byte aligned");
+    return pp_run(at, stream, [&](hipStream_t s) { launch_dist_gather(at, at_bytes, w, h, d, label, dist, values, capacity, cursor, s); });
+}
+
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "../../include/unet_atlas.h"
 #include "../../include/unet_augment.h"
 #include "../../include/unet_components.h"
+#include "../../include/unet_distance.h"
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
 #include "../../include/unet_postproc.h"
@@ -394,5 +395,15 @@ void launch_table_regions(const void* labels, int label_bytes, int w, int h, int
                           hipStream_t s);
 void launch_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, int64_t voxels, int n_labels, int64_t* rows, int impl,
                           void* scratch, hipStream_t s);
+
+// kernels_distance.hip: the exact squared distance transform and the surface lists (include/unet_distance.h); the volume between
+// the passes lives in the scratch
+size_t dist_scratch_bytes(int64_t voxels);
+void launch_dist_transform(const void* labels, int label_bytes, int w, int h, int d, int label, int of, int wx, int wy, int wz, int32_t* out,
+                           int impl, void* scratch, hipStream_t s);
+void launch_dist_surface_counts(const void* a, int a_bytes, const void* b, int b_bytes, int w, int h, int d, int n_labels, int64_t* rows,
+                                hipStream_t s);
+void launch_dist_gather(const void* at, int at_bytes, int w, int h, int d, int label, const int32_t* dist, int32_t* values, int64_t capacity,
+                        unsigned long long* cursor, hipStream_t s);
 
 }  // namespace unet

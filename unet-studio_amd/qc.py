@@ -255,6 +255,77 @@ def run_qc(model, model_path, cases, thread_count=4):
     return write_report(model_path, model.out_count, rows)
 
 
+# ---- boundary distances per class (this project's: the reference's QC stops at the wrong-voxel ratios) ------------------------------
+def surface_report_path(model_path):
+    d, f = os.path.split(model_path)
+    return os.path.join(d, os.path.splitext(f)[0] + ".surface_report.tsv")
+
+
+def format_surface_report(out_count, rows):
+    """the report text; rows: (image, label, summary) with summary the float64 {out_count, 3} of distance.summary (hd, hd95, assd in
+    mm per class), or None for a case whose classes are not the model's (a shifted label): N/A in every column"""
+    lines = ["image\tground_truth" + "".join("\thd%d\thd95%d\tassd%d" % (c, c, c) for c in range(1, out_count))]
+    for image, label, summary in rows:
+        cols = [os.path.basename(image), os.path.basename(label)]
+        for c in range(1, out_count):
+            cols += ["N/A"] * 3 if summary is None else ["%.9g" % v for v in summary[c]]
+        lines.append("\t".join(cols))
+    return "\n".join(lines) + "\n"
+
+
+def surface_qc(model, model_path, cases, labels=None):
+    """Per case and class 1..out_count-1, the Hausdorff distance, its 95th percentile and the average symmetric surface distance in mm
+    between the argmax of the model's output and the label (distance.py, include/unet_distance.h), written to
+    `<model stem>.surface_report.tsv` beside the model -> (0, report path) or (1, message).  labels: the classes to measure (None:
+    all; the others read nan).  A case that label_plan marks as shifted gets N/A in every column: its classes are not the model's."""
+    from . import distance as DS
+    cases = list(cases)
+    if not cases:
+        return 1, "no image/label pairs found"
+    if model.out_count < 2:
+        return 1, "QC requires a categorical model"
+    W, H, D = (int(v) for v in model.dim)
+    S = D * H * W
+    dev = model.device()
+    rows = []
+    try:
+        _, shift = label_plan(cases, model.out_count)
+        weights, unit_mm2 = DS.metric(model.voxel_size, (W, H, D))
+        scratch = torch.empty(DS.distance_scratch_bytes((W, H, D)), dtype=torch.uint8, device=dev)
+        for case, shifted in zip(cases, shift):
+            summary = None
+            if not shifted:
+                image, label = case[2], case[3]
+                if int(np.prod(image.shape)) != S * model.in_count or int(np.prod(label.shape)) != S:
+                    raise UNetError("%s: training data dimension mismatch" % case[0])
+                x = _to_device(image, dev).view(1, model.in_count, D, H, W)
+                with torch.no_grad():
+                    logits = model._forward_level0(x)
+                if logits is None or tuple(logits.shape) != (1, model.out_count, D, H, W):
+                    raise UNetError("%s: model output dimension mismatch" % case[0])
+                got = torch.argmax(logits[0], dim=0).to(torch.int32).to(torch.uint16).contiguous()
+                want = torch.trunc(_to_device(label, dev)).clamp_(0, 65535).to(torch.int32).to(torch.uint16).view(D, H, W).contiguous()
+                res = DS.surface_distances(got, want, model.out_count - 1, weights, labels=labels, scratch=scratch)
+                summary = DS.summary(res, unit_mm2)
+            rows.append((case[0], case[1], summary))
+    except UNetError as e:
+        return 1, str(e)
+    report = surface_report_path(model_path)
+    tmp = report + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(format_surface_report(model.out_count, rows).encode())
+    except OSError as e:
+        return 1, "failed writing %s: %s" % (tmp, e)
+    try:
+        if os.path.lexists(report):
+            os.remove(report)
+        os.rename(tmp, report)
+    except OSError as e:
+        return 1, "cannot create %s: %s" % (report, e)
+    return 0, report
+
+
 def qc(model_path, cases, device="cuda:0", dtype="bf16", thread_count=4):
     """int qc(void) (qc.cpp:164-376) for cases already read -> (0, report path) or (1, message)"""
     from .unet3d import UNet3d
