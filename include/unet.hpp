@@ -114,6 +114,11 @@ public: // ---- engine side (not in the reference) ----
     // fused micro-step pieces (train.cpp:634-706 and 759-766 without autograd), optional for callers
     torch::Tensor loss_and_backward(torch::Tensor input, torch::Tensor target_int64, bool ce, bool dice, bool mse, int collapse_before = 0);
     void sgd_step(float lr, float grad_scale, float clip_norm = 12.0f);
+    // sgd_step also writes the filter packs of the last loss_and_backward's workspace, in the same pass (unet_sgd_step_packed); the next
+    // loss_and_backward at that size runs on that workspace with UNET_MODE_PACKS_CURRENT.  Anything that touches the parameters in
+    // between (load_from_file, copy_from, optimizer->step(), broadcast_parameters, any in-place torch op on them, a device move)
+    // makes that forward repack as before.  false: the plain unet_sgd_step.
+    bool pack_in_update = true;
     // Resume path (train.cpp:787, :945-957).  The momentum of the fused update and the momentum_buffer tensors in *optimizer's state
     // are the same memory once bind_optimizer_state() has run (sgd_step / save_optimizer / load_optimizer call it), so
     // torch::save(*optimizer, path) and torch::load(*optimizer, path) + bind_optimizer_state() work as train.cpp writes them;
@@ -142,6 +147,15 @@ private:
     std::shared_ptr<WorkspacePool> ws_pool_;
     std::mutex plans_mutex_;
     torch::Tensor trigger_, momentum_, scratch_;
+    // the workspace of the last loss_and_backward (kept leased for sgd_step), and the one whose packs sgd_step made with the
+    // parameters' stamp at that moment (params_stamp: storage address + torch version counters of flat_params and every parameter)
+    unet_plan* last_plan_ = nullptr;
+    unet_plan* packed_plan_ = nullptr;
+    torch::Tensor last_ws_, packed_ws_;
+    uint64_t packed_stamp_ = 0;
+    uint64_t params_stamp(void) const;
+    torch::Tensor training_workspace(unet_plan* plan, int* mode);
+    void drop_packs(void);
     struct unet_comm* comm_ = nullptr;
     int64_t reduced_from_ = -1;            // flat gradient elements [reduced_from_, end) are already being all-reduced (this step)
     unet_plan* plan_for(int64_t d,int64_t h,int64_t w);

@@ -178,6 +178,16 @@ int unet_sgd_step(const unet_plan* plan, float* params_flat, float* grads_flat, 
                   float momentum, int nesterov, float weight_decay, float clip_norm, float grad_scale, float* norm_out,
                   void* scratch, void* stream);
 
+/* unet_sgd_step that also writes the filter packs of `workspace` from the updated values, in the same pass over the parameters: the
+ * effect of unet_sgd_step followed by unet_pack_filters(plan, params, workspace, with_dgrad, made, stream), bit for bit, the
+ * arrival-counter clear included.  The parameters change nowhere else in training, so the next mode-1 forward on this workspace may be
+ * given UNET_MODE_PACKS_CURRENT when *made = 1.  *made = 0: this plan has no batched pack (fp32 engine) or workspace is NULL; the plain
+ * unet_sgd_step has run and the caller must NOT claim UNET_MODE_PACKS_CURRENT.  params_flat is the one flat buffer the forward's
+ * parameter pointers point into; all three buffers 16-byte aligned. */
+int unet_sgd_step_packed(const unet_plan* plan, float* params_flat, float* grads_flat, float* momentum_flat, float lr,
+                         float momentum, int nesterov, float weight_decay, float clip_norm, float grad_scale, float* norm_out,
+                         void* workspace, int with_dgrad, int* made, void* scratch, void* stream);
+
 /* ---- single-op surface (unit tests, parity per kernel).  Activations are channels-last [D][H][W][C]
  * in the element type of `dtype`; weights/bias/grads fp32 in torch layout ([Cout,Cin,k,k,k]; conv_trans
  * [Cin,Cout,2,2,2]).  impl: UNET_IMPL_*.  scratch: at least unet_op_scratch_bytes() bytes. ---- */

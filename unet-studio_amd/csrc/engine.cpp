@@ -112,6 +112,10 @@ struct unet_plan {
     std::vector<PackJob> pack_jobs;
     int64_t pack_blocks = 0;
     PackJob* jobs_dev = nullptr;
+    // update tiles of unet_sgd_step_packed (kernels_sgd_pack.hip): a partition of the flat parameter buffer in which every pack unit of
+    // pack_jobs lies inside one tile; empty when there is no batched pack (then that entry point runs the plain update)
+    std::vector<SgdTile> sgd_tiles;
+    SgdTile* tiles_dev = nullptr;
     // sgd
     SgdSeg* segs_dev = nullptr;
     int nseg = 0;
@@ -138,6 +142,7 @@ struct unet_plan {
         if (segs_dev) (void)hipFree(segs_dev);
         if (wz_jobs_dev) (void)hipFree(wz_jobs_dev);
         if (jobs_dev) (void)hipFree(jobs_dev);
+        if (tiles_dev) (void)hipFree(tiles_dev);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_pack) (void)hipEventDestroy(ev_pack);
@@ -373,6 +378,64 @@ struct unet_plan {
             }
             if (which == 0) pack_fwd_blocks = pack_blocks;
         }
+        build_sgd_tiles();
+    }
+
+    // The tile table is derived from pack_jobs (job indices, not copies of their offsets), next to it: filter tiles of up to 32 x 32
+    // channels x all taps for every weight with pack jobs, plain ranges for everything else.  Largest first: the launch has one block
+    // per tile, so the short ones fill the tail.
+    void build_sgd_tiles() {
+        sgd_tiles.clear();
+        if (pack_jobs.empty()) return;
+        const size_t np = g.params.size();
+        std::vector<int> jf(np, -1), jd(np, -1), d0(np, 0), d1(np, 0), taps(np, 0);
+        {
+            size_t j = 0;
+            for (int which = 0; which < 2; ++which)
+                for (size_t i = 0; i < g.ops.size(); ++i) {
+                    const Op& op = g.ops[i];
+                    if (!conv[i].mfma_fwd()) continue;
+                    const bool convt = op.kind != OP_CONV;
+                    if (which >= (convt ? 2 : (conv[i].dgrad == Dgrad::mfma ? 2 : 1))) continue;
+                    const ConvGeom cg = op_geom_of(op);
+                    int& slot = which == 0 ? jf[op.weight] : jd[op.weight];
+                    if (j >= pack_jobs.size() || pack_jobs[j].src_off != p_off[op.weight] || slot >= 0) return;   // (a weight two ops share: no table)
+                    slot = (int)j++;
+                    d0[op.weight] = convt ? cg.Cin : cg.Cout; d1[op.weight] = convt ? cg.Cout : cg.Cin; taps[op.weight] = convt ? 8 : 27;
+                }
+            if (j != pack_jobs.size()) return;
+        }
+        std::vector<int64_t> units(pack_jobs.size(), 0);
+        bool ok = true;
+        for (size_t i = 0; i < np && ok; ++i) {
+            SgdTile t{};
+            t.wd = g.params[i].decay ? 1.f : 0.f;
+            t.job_fwd = jf[i]; t.job_dgrad = jd[i];
+            const int64_t n = p_off[i + 1] - p_off[i];
+            if (jf[i] < 0) {
+                if (jd[i] >= 0) { ok = false; break; }
+                constexpr int64_t chunk = 8192;
+                for (int64_t o = 0; o < n; o += chunk) { t.off = p_off[i] + o; t.count = std::min(chunk, n - o); sgd_tiles.push_back(t); }
+                continue;
+            }
+            if ((int64_t)d0[i] * d1[i] * taps[i] != n) { ok = false; break; }
+            t.off = p_off[i]; t.D1 = d1[i]; t.T = taps[i];
+            for (int a = 0; a < d0[i] && ok; a += SGD_TILE_MAX)
+                for (int b = 0; b < d1[i] && ok; b += SGD_TILE_MAX) {
+                    t.d0 = a; t.n0 = std::min(SGD_TILE_MAX, d0[i] - a); t.d1 = b; t.n1 = std::min(SGD_TILE_MAX, d1[i] - b);
+                    t.count = (int64_t)t.n0 * t.n1 * t.T;
+                    for (int j : {jf[i], jd[i]}) {
+                        if (j < 0) continue;
+                        const int64_t u = sgd_tile_units(t, pack_jobs[j]);
+                        if (u < 0) ok = false; else units[j] += u;
+                    }
+                    sgd_tiles.push_back(t);
+                }
+        }
+        // every unit of every job exactly once (the tiles of a tensor are disjoint): else the forward would read fragments nobody wrote
+        for (size_t j = 0; j < pack_jobs.size() && ok; ++j) ok = units[j] == pack_jobs[j].total;
+        if (!ok) { sgd_tiles.clear(); return; }
+        std::stable_sort(sgd_tiles.begin(), sgd_tiles.end(), [](const SgdTile& a, const SgdTile& b) { return a.count > b.count; });
     }
 };
 
@@ -1047,6 +1110,10 @@ int unet_plan_create(const char* arch, int in_c, int out_c, int D, int H, int W,
                 HIP_OK(hipMalloc((void**)&p->jobs_dev, p->pack_jobs.size() * sizeof(PackJob)));
                 HIP_OK(hipMemcpy(p->jobs_dev, p->pack_jobs.data(), p->pack_jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
             }
+            if (!p->sgd_tiles.empty()) {
+                HIP_OK(hipMalloc((void**)&p->tiles_dev, p->sgd_tiles.size() * sizeof(SgdTile)));
+                HIP_OK(hipMemcpy(p->tiles_dev, p->sgd_tiles.data(), p->sgd_tiles.size() * sizeof(SgdTile), hipMemcpyHostToDevice));
+            }
         }
         *out = p;
         return 0;
@@ -1460,6 +1527,30 @@ int unet_sgd_step(const unet_plan* p, float* params, float* grads, float* mom, f
         launch_sgd(params, grads, mom, p->n_param_elems, p->segs_dev, p->nseg, partial, nblk, lr, momentum, nesterov, wd, clip_norm,
                    grad_scale, norm_out, s);
         check_launch();
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int unet_sgd_step_packed(const unet_plan* p, float* params, float* grads, float* mom, float lr, float momentum, int nesterov, float wd,
+                         float clip_norm, float grad_scale, float* norm_out, void* workspace, int with_dgrad, int* made, void* scratch,
+                         void* stream) {
+    try {
+        if (!p || !params || !grads || !mom || !scratch || !made) throw std::runtime_error("unet_sgd_step_packed: null argument");
+        *made = 0;
+        if (!p->tiles_dev || !p->jobs_dev || !workspace)   // no batched pack (the fp32 engine, ...): the plain update
+            return unet_sgd_step(p, params, grads, mom, lr, momentum, nesterov, wd, clip_norm, grad_scale, norm_out, scratch, stream);
+        if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(mom)) & 15)
+            throw std::runtime_error("unet_sgd_step_packed: misaligned buffer");
+        DeviceGuard dg(p->device);
+        hipStream_t s = (hipStream_t)stream;
+        const int nblk = 1024;           // as unet_sgd_step
+        float* partial = (float*)scratch;
+        launch_sumsq_partial(grads, p->n_param_elems, grad_scale, partial, nblk, s);
+        launch_sgd_pack(params, grads, mom, p->tiles_dev, (int)p->sgd_tiles.size(), p->jobs_dev, workspace, with_dgrad,
+                        p->deep_part_bytes ? (int*)((char*)workspace + p->deep_cnt_off) : nullptr, p->deep_ncnt, partial, nblk, lr, momentum,
+                        nesterov, wd, clip_norm, grad_scale, norm_out, s);
+        check_launch();
+        *made = 1;
         return 0;
     } catch (const std::exception& e) { return fail(e.what()); }
 }

@@ -145,10 +145,34 @@ void launch_sgd(float* p, float* g, float* m, int64_t n, const SgdSeg* segs_dev,
                 float lr, float momentum, int nesterov, float weight_decay, float clip_norm, float grad_scale, float* norm_out,
                 hipStream_t s);
 
+// ---- update + filter packs in one pass (kernels_sgd_pack.hip) ----
+// One block's share of the flat parameter buffer.  A filter tile (job_fwd >= 0) is the sub-block [d0, d0 + n0) x [d1, d1 + n1) x T of a
+// weight tensor w[D0][D1][T] at `off` (conv: Cout, Cin, 27; conv_trans: Cin, Cout, 8); n0, n1 <= 32 and both starts are multiples of 32,
+// so every pack unit of the tensor's forward job and of its dgrad job (job_dgrad, -1: none) draws its values from inside one tile.
+// A plain range (job_fwd < 0) is `count` elements at `off` that no pack job reads.  wd as in SgdSeg.
+struct PackJob;
+struct SgdTile { int64_t off, count; float wd; int job_fwd, job_dgrad, D1, T, d0, n0, d1, n1, pad; };
+constexpr int SGD_TILE_MAX = 32;
+// the pack units of `job` that tile `t` holds (host side: the plan checks that its tiles hold every unit of every job exactly once)
+int64_t sgd_tile_units(const SgdTile& t, const PackJob& job);
+// the effect of launch_sgd followed by launch_mfma_pack_batched over the jobs [0, with_dgrad ? all : the forward jobs) of the table
+void launch_sgd_pack(float* p, float* g, float* m, const SgdTile* tiles_dev, int ntiles, const PackJob* jobs_dev, void* ws, int with_dgrad,
+                     int* zero, int nzero, const float* partial, int nblk, float lr, float momentum, int nesterov, float weight_decay,
+                     float clip_norm, float grad_scale, float* norm_out, hipStream_t s);
+
 // ---- MFMA implicit-GEMM family (kernels_mfma_conv.hip, kernels_mfma_wgrad.hip), bf16 only ----
 // one filter pack of the batched pack kernel: fp32 parameter (src_off floats from the flat parameter base) ->
 // bf16 fragments at dst_off bytes into the workspace; blk0 = first 256-thread block of the job in the launch
 struct PackJob { int64_t src_off, dst_off, total, blk0; int Ci, Co, CK, T, mode, A, B, pad; };
+// PackJob::mode: how a pack unit (16 rows o x CK k-channels i x T taps t) draws its values from the fp32 torch-layout filter w
+enum PackMode {
+    PK_CONV_FWD = 0,    // rows o = cout, k-channel i = cin, T taps:           w[(o*A + i)*T + t]              A = Cin
+    PK_CONV_DGRAD = 1,  // rows o = cin,  i = cout, 27 taps flipped:           w[(i*A + o)*27 + 26 - t]        A = Cin
+    PK_CONVT_DGRAD = 2, // rows o = cin,  i = cout, 8 taps:                    w[(o*B + i)*8 + t]              B = Cout
+    PK_CONVT_FWD = 3,   // rows o = t*B + co, i = cin, 1 tap:                  w[(i*B + co)*8 + t]             B = Cout
+    PK_CONV_S2_DGRAD = 4 // rows o = p*A + ci (p = output parity), i = cout, 8 taps k in {0,1}^3 over dy[m+k]:
+                        //   per dim  p=0: k=0 -> filter tap 1 ;  p=1: k=0 -> tap 2, k=1 -> tap 0 ; else zero     A = Cin
+};
 int mfma_conv_pack_jobs(const ConvGeom& g, bool want_dgrad, PackJob* out2);
 int mfma_convt_pack_jobs(const ConvGeom& g, PackJob* out2);
 // one launch serves the pack units [blk_base, blk_base + nblocks) of the table (njobs = the whole table); max_grid > 0 bounds the

@@ -3,6 +3,7 @@
 // train.cpp:759-766.  All reductions are two-stage (per-block partials, then a finalize kernel that
 // sums the partials in a fixed order in fp64): deterministic, no float atomics.
 #include "device_util.h"
+#include "sgd_update.h"
 
 namespace unet {
 
@@ -1196,7 +1197,7 @@ void launch_sumsq_partial(const float* g, int64_t n, float scale, float* partial
 
 // One fused pass: total gradient norm from the partials, clip coefficient, weight decay (per parameter segment), Nesterov
 // momentum, parameter update and zero_grad.  Four consecutive elements per thread (16-B accesses); the segment table and the
-// partials are reduced through LDS once per block.
+// partials are reduced through LDS once per block.  The arithmetic is sgd_update.h's, shared with k_sgd_pack.
 constexpr int SGD_MAXSEG = 1024;
 __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, int64_t n,
                                              const SgdSeg* __restrict__ segs, int nseg, const float* __restrict__ partial, int nblk,
@@ -1205,24 +1206,9 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, float* __res
     __shared__ float s_coef;
     __shared__ int64_t s_off[SGD_MAXSEG];
     __shared__ float s_wd[SGD_MAXSEG];
-    double part = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 256) part += partial[b];
-    red[threadIdx.x] = part;
     const int ns = nseg < SGD_MAXSEG ? nseg : SGD_MAXSEG;
     for (int k = threadIdx.x; k < ns; k += 256) { s_off[k] = segs[k].offset; s_wd[k] = segs[k].wd; }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float norm = (float)sqrt(red[0]);
-        float coef = clip_norm / (norm + 1e-6f);
-        s_coef = coef > 1.f ? 1.f : coef;
-        if (blockIdx.x == 0 && norm_out) *norm_out = norm;
-    }
-    __syncthreads();
-    const float coef = s_coef * grad_scale;
+    const SgdUpdate upd{sgd_clip_coef(partial, nblk, clip_norm, norm_out, red, &s_coef) * grad_scale, lr, momentum, nesterov};
     auto seg_of = [&](int64_t i) {          // last segment with offset <= i
         int lo = 0, hi = nseg - 1;
         while (lo < hi) {
@@ -1233,13 +1219,6 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, float* __res
         return lo;
     };
     auto wd_of = [&](int sg) { return (sg < SGD_MAXSEG ? s_wd[sg] : segs[sg].wd) * wdecay; };
-    auto upd = [&](float& pv, float& gv, float& mv, float wd) {
-        float d = fmaf(wd, pv, gv * coef);
-        float b = fmaf(momentum, mv, d);
-        mv = b;
-        pv = pv - lr * (nesterov ? fmaf(momentum, b, d) : b);
-        gv = 0.f;
-    };
     const int64_t n4 = n >> 2;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
         const int64_t i = q * 4;

@@ -28,14 +28,7 @@
 namespace unet {
 
 // ---- filter packing: fp32 torch layout -> bf16 fragments [chunk][kstep][row tile][lane][8] ----
-enum PackMode {
-    PK_CONV_FWD = 0,    // rows o = cout, k-channel i = cin, T taps:           w[(o*A + i)*T + t]              A = Cin
-    PK_CONV_DGRAD = 1,  // rows o = cin,  i = cout, 27 taps flipped:           w[(i*A + o)*27 + 26 - t]        A = Cin
-    PK_CONVT_DGRAD = 2, // rows o = cin,  i = cout, 8 taps:                    w[(o*B + i)*8 + t]              B = Cout
-    PK_CONVT_FWD = 3,   // rows o = t*B + co, i = cin, 1 tap:                  w[(i*B + co)*8 + t]             B = Cout
-    PK_CONV_S2_DGRAD = 4 // rows o = p*A + ci (p = output parity), i = cout, 8 taps k in {0,1}^3 over dy[m+k]:
-                        //   per dim  p=0: k=0 -> filter tap 1 ;  p=1: k=0 -> tap 2, k=1 -> tap 0 ; else zero     A = Cin
-};
+// (PackMode: kernels.h)
 // One pack unit = (channel chunk q, row tile nt): the 16 x CK x T filter values are gathered into LDS in the order that is
 // contiguous in the SOURCE (the element-per-thread version read 4 B at a 108-B stride: 0.15 ms per step for 60 MB), then the
 // KSTEPS fragments [lane][8] of the unit are written with 16-B stores.

@@ -181,6 +181,9 @@ void UNet3dImpl::ensure_flat(void)
         }
         scratch_ = torch::Tensor();
         std::scoped_lock<std::mutex> lock(plans_mutex_);
+        last_plan_ = packed_plan_ = nullptr;
+        last_ws_ = torch::Tensor();
+        packed_ws_ = torch::Tensor();
         for (auto& kv : plans_) unet_plan_destroy(kv.second);   // plans are bound to a device
         plans_.clear();
         if (ws_pool_) ws_pool_->clear();
@@ -274,6 +277,40 @@ torch::Tensor UNet3dImpl::workspace_for(unet_plan* plan)
         if (e.ev) (void)hipEventDestroy(e.ev);   // pool gone or full: the buffer goes back to torch's allocator with `e`
     };
     return torch::from_blob(e.buf.data_ptr(), e.buf.sizes(), back, e.buf.options());
+}
+
+uint64_t UNet3dImpl::params_stamp(void) const
+{
+    uint64_t s = (uint64_t)reinterpret_cast<uintptr_t>(flat_params.data_ptr()) * 1000003u + flat_params._version();
+    for (auto& p : params_) s = s * 1000003u + p._version();
+    return s;
+}
+
+void UNet3dImpl::drop_packs(void)
+{
+    std::scoped_lock<std::mutex> lock(plans_mutex_);
+    last_plan_ = packed_plan_ = nullptr;
+    last_ws_ = torch::Tensor();
+    packed_ws_ = torch::Tensor();
+}
+
+// the workspace of a training micro-step: the one sgd_step wrote the filter packs into, when the parameters are untouched since
+// (*mode gets UNET_MODE_PACKS_CURRENT; one caller takes it), else a lease from the pool
+torch::Tensor UNet3dImpl::training_workspace(unet_plan* plan, int* mode)
+{
+    {
+        std::scoped_lock<std::mutex> lock(plans_mutex_);
+        if (packed_plan_ == plan && packed_ws_.defined() && packed_stamp_ == params_stamp()) {
+            torch::Tensor ws = std::move(packed_ws_);
+            packed_plan_ = nullptr;
+            packed_ws_ = torch::Tensor();
+            *mode |= UNET_MODE_PACKS_CURRENT;
+            return ws;
+        }
+        packed_plan_ = nullptr;
+        packed_ws_ = torch::Tensor();
+    }
+    return workspace_for(plan);
 }
 
 std::vector<torch::Tensor> UNet3dImpl::run_forward(unet_plan* plan, torch::Tensor ws, torch::Tensor x, int mode)
@@ -440,8 +477,9 @@ torch::Tensor UNet3dImpl::loss_and_backward(torch::Tensor input, torch::Tensor t
     ensure_flat();
     auto x = input.to(torch::kFloat32).contiguous();
     unet_plan* plan = plan_for(x.size(2), x.size(3), x.size(4));
-    auto ws = workspace_for(plan);
-    auto outs = run_forward(plan, ws, x, 1);
+    int mode = 1;
+    auto ws = training_workspace(plan, &mode);
+    auto outs = run_forward(plan, ws, x, mode);
     size_t sb = 0;
     unet_loss_scratch_bytes(plan, &sb);
     auto sc = torch::empty({(int64_t)sb}, torch::TensorOptions().dtype(torch::kUInt8).device(x.device()));
@@ -459,6 +497,10 @@ torch::Tensor UNet3dImpl::loss_and_backward(torch::Tensor input, torch::Tensor t
     check(unet_loss(plan, op.data(), t.data_ptr<int64_t>(), mask, collapse_before, gp.data(), losses.data_ptr<float>(), sc.data_ptr(),
                     stream_of(x.device())));
     run_backward(plan, ws, gouts);
+    {
+        std::scoped_lock<std::mutex> lock(plans_mutex_);
+        last_plan_ = plan; last_ws_ = ws;
+    }
     return losses;
 }
 
@@ -468,6 +510,7 @@ void UNet3dImpl::broadcast_parameters(int root)
     if (!comm_) throw std::runtime_error("broadcast_parameters: no communicator attached");
     ensure_flat();
     void* st = stream_of(flat_params.device());
+    drop_packs();   // the parameters change under the version counters
     check(unet_comm_broadcast(comm_, flat_params.data_ptr<float>(), flat_params.numel(), root, st));
     for (auto& b : buffers_) check(unet_comm_broadcast(comm_, b.data_ptr<float>(), b.numel(), root, st));   // unet.cpp:207-215
     check(unet_comm_join(comm_, st));
@@ -508,8 +551,9 @@ torch::Tensor UNet3dImpl::loss_and_backward_overlapped(torch::Tensor input, torc
     rebind_grads();
     auto x = input.to(torch::kFloat32).contiguous();
     unet_plan* plan = plan_for(x.size(2), x.size(3), x.size(4));
-    auto ws = workspace_for(plan);
-    auto outs = run_forward(plan, ws, x, 1);
+    int mode = 1;
+    auto ws = training_workspace(plan, &mode);
+    auto outs = run_forward(plan, ws, x, mode);
     size_t sb = 0;
     unet_loss_scratch_bytes(plan, &sb);
     auto sc = torch::empty({(int64_t)sb}, torch::TensorOptions().dtype(torch::kUInt8).device(x.device()));
@@ -543,6 +587,10 @@ torch::Tensor UNet3dImpl::loss_and_backward_overlapped(torch::Tensor input, torc
             reduced_from_ = elem_lo[k];
         }
         op_hi = op_lo[k]; elem_hi = elem_lo[k];
+    }
+    {
+        std::scoped_lock<std::mutex> lock(plans_mutex_);
+        last_plan_ = plan; last_ws_ = ws;
     }
     return losses;
 }
@@ -608,7 +656,26 @@ void UNet3dImpl::sgd_step(float lr, float grad_scale, float clip_norm)
     bind_optimizer_state();
     if (!scratch_.defined()) scratch_ = torch::empty({65536 + 16}, torch::TensorOptions().dtype(torch::kUInt8).device(flat_params.device()));
     if (plans_.empty()) throw std::runtime_error("sgd_step before any forward");
-    check(unet_sgd_step(plans_.begin()->second, flat_params.data_ptr<float>(), flat_grads.data_ptr<float>(), momentum_.data_ptr<float>(), lr,
-                        0.99f, 1, 3e-5f, clip_norm, grad_scale, (float*)((char*)scratch_.data_ptr() + 65536), scratch_.data_ptr(),
-                        stream_of(flat_params.device())));
+    unet_plan* plan = nullptr;
+    torch::Tensor ws;
+    {   // the last micro-step's workspace receives the packs; whatever was packed before is stale after this update
+        std::scoped_lock<std::mutex> lock(plans_mutex_);
+        if (pack_in_update && last_plan_ && last_ws_.defined()) { plan = last_plan_; ws = std::move(last_ws_); }
+        last_plan_ = packed_plan_ = nullptr;
+        last_ws_ = torch::Tensor();
+        packed_ws_ = torch::Tensor();
+    }
+    int made = 0;
+    if (plan)
+        check(unet_sgd_step_packed(plan, flat_params.data_ptr<float>(), flat_grads.data_ptr<float>(), momentum_.data_ptr<float>(), lr, 0.99f, 1,
+                                   3e-5f, clip_norm, grad_scale, (float*)((char*)scratch_.data_ptr() + 65536), ws.data_ptr(), 1, &made,
+                                   scratch_.data_ptr(), stream_of(flat_params.device())));
+    else
+        check(unet_sgd_step(plans_.begin()->second, flat_params.data_ptr<float>(), flat_grads.data_ptr<float>(), momentum_.data_ptr<float>(), lr,
+                            0.99f, 1, 3e-5f, clip_norm, grad_scale, (float*)((char*)scratch_.data_ptr() + 65536), scratch_.data_ptr(),
+                            stream_of(flat_params.device())));
+    if (made) {
+        std::scoped_lock<std::mutex> lock(plans_mutex_);
+        packed_plan_ = plan; packed_ws_ = ws; packed_stamp_ = params_stamp();
+    }
 }

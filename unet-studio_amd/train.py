@@ -65,6 +65,9 @@ class Trainer:
         # pack_after_update (attribute, default off: measured neutral): the filter packs are made right behind the update, on the caller's
         # stream, instead of by the next step's forward on the side stream beside its first kernels
         self.pack_after_update = False
+        # pack_in_update (attribute, default on): the update kernel itself writes the filter packs of the last micro-step's workspace
+        # (unet_sgd_step_packed): the next step's first forward has no pack launches beside its first kernels.  Off: the forward repacks.
+        self.pack_in_update = True
         self._packed_size, self._packed_version = None, None
         self.stats_direct = hasattr(model, "_run_forward_loss")
         self._lanes, self._gbufs, self._gptrs = None, [], []
@@ -132,7 +135,7 @@ class Trainer:
             mine = []
             overlap = False
         # workspaces (and the filter packs they hold) are keyed by the sample's spatial size: a micro-step may only skip the repack when a
-        # micro-step of THIS optimizer step (or unet_pack_filters behind the last update) already packed for its size
+        # micro-step of THIS optimizer step (or the last update, or unet_pack_filters behind it) already packed for its size
         packed_sizes = set()
         if self._packed_size is not None and self._packed_version == getattr(m, "_params_version", None):
             packed_sizes.add(self._packed_size)
@@ -172,9 +175,13 @@ class Trainer:
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=self.group)  # loss-stat gather, train.cpp:732-741
             for w in works:
                 w.wait()
-        m.optimizer.step(grad_scale=1.0 / p.batch_size, clip_norm=12.0)  # train.cpp:759-766
         self._packed_size = None
-        if self.pack_after_update and mine and not lanes_on and m.pack_filters(last_size):
+        if self.pack_in_update and self.packs_reuse and mine and not lanes_on:
+            made = m.optimizer.step(grad_scale=1.0 / p.batch_size, clip_norm=12.0, pack_size=last_size)  # train.cpp:759-766
+        else:
+            made = False
+            m.optimizer.step(grad_scale=1.0 / p.batch_size, clip_norm=12.0)
+        if made or (self.pack_after_update and mine and not lanes_on and m.pack_filters(last_size)):
             self._packed_size, self._packed_version = last_size, m._params_version
         if self.comm is not None and self.world_size > 1:
             for b in m.buffers():

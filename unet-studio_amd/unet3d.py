@@ -4,6 +4,7 @@ Same names, argument meaning and error behaviour as `UNet3dImpl`; torch is used 
 streams and (in train.py) torch.distributed.  All arithmetic happens in libunet_hip.so through the
 C ABI of include/unet_hip.h.
 """
+import ctypes
 import math
 import threading
 
@@ -34,16 +35,28 @@ class SGD:
         self.last_grad_norm = torch.zeros(1, device=model.flat_params.device, dtype=torch.float32)
         self._scratch = torch.empty(65536, dtype=torch.uint8, device=model.flat_params.device)
 
-    def step(self, grad_scale=1.0, clip_norm=12.0):
-        """grad /= batch_size (grad_scale), clip_grad_norm_(12.0), SGD step, zero_grad -- train.cpp:759-766 in one pass."""
+    def step(self, grad_scale=1.0, clip_norm=12.0, pack_size=None):
+        """grad /= batch_size (grad_scale), clip_grad_norm_(12.0), SGD step, zero_grad -- train.cpp:759-766 in one pass.
+        pack_size: the update also writes the filter packs of this thread's workspace for volumes of that size, in the same pass
+        (unet_sgd_step_packed); True when it did, and the next training forward at that size may be given packs_current."""
         m = self.model
         lr = self.param_groups[0]["lr"]
-        plan = m._any_plan()
-        E.check(E.lib.unet_sgd_step(plan.handle, m.flat_params.data_ptr(), m.flat_grads.data_ptr(),
-                                    self.momentum_buffer.data_ptr(), lr, self.momentum, int(self.nesterov),
-                                    self.weight_decay, clip_norm, grad_scale, self.last_grad_norm.data_ptr(),
-                                    self._scratch.data_ptr(), _stream_ptr(m.device())))
+        made = ctypes.c_int(0)
+        if pack_size is not None:
+            plan = m.plan_for(tuple(pack_size))
+            E.check(E.lib.unet_sgd_step_packed(plan.handle, m.flat_params.data_ptr(), m.flat_grads.data_ptr(),
+                                               self.momentum_buffer.data_ptr(), lr, self.momentum, int(self.nesterov),
+                                               self.weight_decay, clip_norm, grad_scale, self.last_grad_norm.data_ptr(),
+                                               m._workspace(plan).data_ptr(), 1, ctypes.byref(made), self._scratch.data_ptr(),
+                                               _stream_ptr(m.device())))
+        else:
+            plan = m._any_plan()
+            E.check(E.lib.unet_sgd_step(plan.handle, m.flat_params.data_ptr(), m.flat_grads.data_ptr(),
+                                        self.momentum_buffer.data_ptr(), lr, self.momentum, int(self.nesterov),
+                                        self.weight_decay, clip_norm, grad_scale, self.last_grad_norm.data_ptr(),
+                                        self._scratch.data_ptr(), _stream_ptr(m.device())))
         m._params_version += 1
+        return bool(made.value)
 
     def zero_grad(self):
         self.model.flat_grads.zero_()
