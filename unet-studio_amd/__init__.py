@@ -29,6 +29,7 @@ from . import atlas  # noqa: F401  (the module: atlas.EXPORTS the symbols of inc
 from . import register  # noqa: F401  (the module: register.EXPORTS the symbols of include/unet_register.h)
 from . import table  # noqa: F401  (the module: table.EXPORTS the symbols of include/unet_table.h)
 from . import distance  # noqa: F401  (the module: distance.EXPORTS the symbols of include/unet_distance.h)
+from . import instances  # noqa: F401  (the module: instances.EXPORTS the symbols of include/unet_instances.h)
 
 
 def save_to_file(model, file_name):

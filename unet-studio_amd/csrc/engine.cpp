@@ -2514,4 +2514,97 @@ int unet_dist_gather(const void* at, int at_bytes, int w, int h, int d, int labe
     return pp_run(at, stream, [&](hipStream_t s) { launch_dist_gather(at, at_bytes, w, h, d, label, dist, values, capacity, cursor, s); });
 }
 
+// ---- the instances of a label map (include/unet_instances.h) ----
+static std::string inst_out_error(const std::string& w, const void* p, const char* name, int align) {
+    if (!p) return w + "null " + name;
+    if ((uintptr_t)p & (uintptr_t)(align - 1)) return w + name + " must be " + std::to_string(align) + "-byte aligned";
+    return std::string();
+}
+static std::string inst_size_error(const std::string& w, int64_t voxels, int n_classes, int64_t max_instances) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
+    if (n_classes < 1 || n_classes > 65536) return w + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
+    if (max_instances < 0 || max_instances > UNET_INST_MAX_INSTANCES)
+        return w + "max_instances must be in [0, 2147483646], got " + std::to_string(max_instances);
+    return std::string();
+}
+int unet_inst_scratch_bytes(int64_t voxels, int n_classes, int64_t max_instances, size_t* bytes) {
+    const std::string e = inst_size_error("unet_inst_scratch_bytes: ", voxels, n_classes, max_instances);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_inst_scratch_bytes: null bytes");
+    *bytes = inst_scratch_bytes(voxels, n_classes, max_instances);
+    return 0;
+}
+int unet_inst_label(int w, int h, int d, const uint16_t* label, int n_classes, const uint32_t* listed, int n_listed, int32_t* inst,
+                    int64_t* rows, int64_t max_instances, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_inst_label: ";
+    if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions (w, h, d) must be positive");
+    std::string e = inst_size_error(who, (int64_t)w * h * d, n_classes, max_instances);
+    if (e.empty() && !label) e = who + "null label";
+    if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
+    if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
+    if (e.empty()) e = inst_out_error(who, inst, "inst", 4);
+    if (e.empty()) e = inst_out_error(who, rows, "rows", 8);
+    if (e.empty()) e = inst_out_error(who, info, "info", 8);
+    if (!e.empty()) return fail(e);
+    if (impl < UNET_INST_LABEL_DEFAULT || impl > UNET_INST_LABEL_GLOBAL) return fail(who + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(who + "null scratch");
+    if (scratch_bytes < inst_scratch_bytes((int64_t)w * h * d, n_classes, max_instances))
+        return fail(who + "scratch too small (see unet_inst_scratch_bytes)");
+    for (int i = 0; i < n_listed; ++i)
+        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
+            return fail(who + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]");
+    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
+    std::sort(classes.begin(), classes.end());
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    return pp_run(label, stream, [&](hipStream_t s) {
+        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, scratch, s);
+    });
+}
+int unet_inst_match_scratch_bytes(int64_t max_pairs, size_t* bytes) {
+    if (max_pairs < 0 || max_pairs > UNET_INST_MAX_PAIRS)
+        return fail("unet_inst_match_scratch_bytes: max_pairs must be in [0, 2^30], got " + std::to_string(max_pairs));
+    if (!bytes) return fail("unet_inst_match_scratch_bytes: null bytes");
+    *bytes = inst_match_scratch_bytes(max_pairs);
+    return 0;
+}
+int unet_inst_match(const int32_t* ia, const int32_t* ib, int64_t voxels, uint64_t* keys, int64_t* counts, int64_t max_pairs, int64_t* info,
+                    int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_inst_match: ";
+    std::string e = inst_out_error(who, ia, "ia", 4);
+    if (e.empty()) e = inst_out_error(who, ib, "ib", 4);
+    if (!e.empty()) return fail(e);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail(who + "voxels must be in [1, 2^31), got " + std::to_string(voxels));
+    if (max_pairs < 0 || max_pairs > UNET_INST_MAX_PAIRS) return fail(who + "max_pairs must be in [0, 2^30], got " + std::to_string(max_pairs));
+    // keys and counts may be null only when they hold nothing
+    if (max_pairs > 0 || keys) e = inst_out_error(who, keys, "keys", 8);
+    if (e.empty() && (max_pairs > 0 || counts)) e = inst_out_error(who, counts, "counts", 8);
+    if (e.empty()) e = inst_out_error(who, info, "info", 8);
+    if (!e.empty()) return fail(e);
+    if (impl < UNET_INST_IMPL_DEFAULT || impl > UNET_INST_IMPL_GLOBAL) return fail(who + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(who + "null scratch");
+    if (scratch_bytes < inst_match_scratch_bytes(max_pairs)) return fail(who + "scratch too small (see unet_inst_match_scratch_bytes)");
+    return pp_run(ia, stream, [&](hipStream_t s) {
+        launch_inst_match(ia, ib, voxels, (unsigned long long*)keys, counts, max_pairs, info, impl, scratch, s);
+    });
+}
+int unet_inst_remove_small(uint16_t* label, const int32_t* inst, int64_t voxels, const int64_t* rows, int64_t max_instances,
+                           int64_t min_voxels, uint32_t* removed, int n_classes, void* stream) {
+    const std::string who = "unet_inst_remove_small: ";
+    if (!label) return fail(who + "null label");
+    if ((uintptr_t)label & 1) return fail(who + "label must be 2-byte aligned");
+    std::string e = inst_out_error(who, inst, "inst", 4);
+    if (e.empty()) e = inst_out_error(who, rows, "rows", 8);
+    if (!e.empty()) return fail(e);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail(who + "voxels must be in [1, 2^31), got " + std::to_string(voxels));
+    if (max_instances < 0 || max_instances > UNET_INST_MAX_INSTANCES)
+        return fail(who + "max_instances must be in [0, 2147483646], got " + std::to_string(max_instances));
+    if (removed) {
+        if ((uintptr_t)removed & 3) return fail(who + "removed must be 4-byte aligned");
+        if (n_classes < 1 || n_classes > 65536) return fail(who + "n_classes must be in [1, 65536], got " + std::to_string(n_classes));
+    }
+    return pp_run(label, stream, [&](hipStream_t s) {
+        launch_inst_remove_small(label, inst, voxels, rows, max_instances, min_voxels, removed, n_classes, s);
+    });
+}
+
 }  // extern "C"

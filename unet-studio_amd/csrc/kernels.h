@@ -11,6 +11,7 @@
 #include "../../include/unet_distance.h"
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
+#include "../../include/unet_instances.h"
 #include "../../include/unet_postproc.h"
 #include "../../include/unet_preproc.h"
 #include "../../include/unet_qc.h"
@@ -391,6 +392,27 @@ void launch_preproc_normalize(float* buf, int64_t values, void* scratch, hipStre
 size_t components_scratch_bytes(int64_t S, int n_classes);
 void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_classes, const uint32_t* classes, int n,
                                     uint32_t* removed, int impl, void* scratch, hipStream_t s);
+// the labelling stage alone (shared with kernels_instances.hip): parent[v] = the smallest linear index of v's component or -1,
+// count[r] = the component's voxels at a root r; both live in the scratch.  end: the first byte behind what
+// components_scratch_bytes covers from the scratch's 256-B aligned base (itself 256-B aligned); best: keep_largest's per-class table
+struct ComponentsForest {
+    int* parent;
+    unsigned* count;
+    char* end;
+    unsigned long long* best;
+};
+ComponentsForest launch_components_label(int W, int H, int D, const uint16_t* label, int n_classes, const uint32_t* classes, int n,
+                                         int impl, void* scratch, hipStream_t s);
+
+// kernels_instances.hip: the instances of a label map (include/unet_instances.h); classes as above
+size_t inst_scratch_bytes(int64_t S, int n_classes, int64_t max_instances);
+void launch_inst_label(int W, int H, int D, const uint16_t* label, int n_classes, const uint32_t* classes, int n, int32_t* inst,
+                       int64_t* rows, int64_t max_instances, int64_t* info, int impl, void* scratch, hipStream_t s);
+size_t inst_match_scratch_bytes(int64_t max_pairs);
+void launch_inst_match(const int32_t* ia, const int32_t* ib, int64_t voxels, unsigned long long* keys, int64_t* counts, int64_t max_pairs,
+                       int64_t* info, int impl, void* scratch, hipStream_t s);
+void launch_inst_remove_small(uint16_t* label, const int32_t* inst, int64_t voxels, const int64_t* rows, int64_t max_instances,
+                              int64_t min_voxels, uint32_t* removed, int n_classes, hipStream_t s);
 
 // kernels_atlas.hip: the atlas preparation of load_atlas (include/unet_atlas.h); grow: n_tissues host flags, read before the return.
 // reclassify uses the tables of the scratch only: atlas_scratch_bytes(1, R, T, 0) serves it

@@ -23,6 +23,7 @@
 //   k_cmp_zero      a member whose root is not its class's best becomes 0; removed[class] counts them (block histogram in LDS for
 //                   the classes below CMP_HIST, global adds above)
 // Every atomic is an integer compare-and-swap, add or maximum: the result does not depend on the schedule.
+// Everything up to and including the flatten passes is launch_components_label, which kernels_instances.hip shares.
 //
 // Scratch: parent int32[S], count uint32[S], best uint64[n_classes], flags uint8[n_classes], each 256-B aligned.
 #include <stdexcept>
@@ -273,18 +274,21 @@ size_t components_scratch_bytes(int64_t S, int n_classes) {
     return 256 + 2 * cmp_align((size_t)S * 4) + cmp_align((size_t)n_classes * 8) + cmp_align((size_t)n_classes);
 }
 
-// classes: n sorted distinct entries in (0, n_classes), host memory; read before this returns
-void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_classes, const uint32_t* classes, int n,
-                                    uint32_t* removed, int impl, void* scratch, hipStream_t s) {
-    auto zero = [&](void* p, size_t bytes) {
-        if (hipError_t e = hipMemsetAsync(p, 0, bytes, s); e != hipSuccess)
-            throw std::runtime_error(std::string("unet_components: hipMemsetAsync: ") + hipGetErrorString(e));
-    };
-    if (removed) zero(removed, (size_t)n_classes * 4);
-    if (n == 0) return;
+// The labelling stage, shared with kernels_instances.hip: after it parent[v] is the smallest linear index of v's component (-1 for a
+// voxel that is no member) and count[r] the component's voxels at every root r (elsewhere count is not meaningful).
+// classes: n sorted distinct entries in (0, n_classes), host memory; read before this returns.  n == 0: nothing is a member
+ComponentsForest launch_components_label(int W, int H, int D, const uint16_t* label, int n_classes, const uint32_t* classes, int n,
+                                         int impl, void* scratch, hipStream_t s) {
     const int S = W * H * D;   // < 2^31 (checked by the caller)
     const Scratch sc = cmp_scratch(scratch, S, n_classes);
-    zero(sc.best, sc.table_bytes);
+    ComponentsForest forest = {sc.parent, sc.count, (char*)sc.best + sc.table_bytes, sc.best};
+    if (n == 0) {
+        if (hipError_t e = hipMemsetAsync(sc.parent, 0xFF, (size_t)S * 4, s); e != hipSuccess)
+            throw std::runtime_error(std::string("unet_components: hipMemsetAsync: ") + hipGetErrorString(e));
+        return forest;
+    }
+    if (hipError_t e = hipMemsetAsync(sc.best, 0, sc.table_bytes, s); e != hipSuccess)
+        throw std::runtime_error(std::string("unet_components: hipMemsetAsync: ") + hipGetErrorString(e));
     for (int c0 = 0; c0 < n; c0 += CMP_CHUNK) {
         ListChunk chunk;
         const int m = n - c0 < CMP_CHUNK ? n - c0 : CMP_CHUNK;
@@ -307,8 +311,21 @@ void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_
         k_cmp_flatten<false, false><<<nb, CMP_T, 0, s>>>(S, sc.parent, sc.count);
         k_cmp_flatten<true, true><<<nb, CMP_T, 0, s>>>(S, sc.parent, sc.count);
     }
-    k_cmp_best<<<nb, CMP_T, 0, s>>>(S, label, sc.parent, sc.count, sc.best);
-    k_cmp_zero<<<nb, CMP_T, 0, s>>>(S, n_classes, label, sc.parent, sc.best, removed);
+    return forest;
+}
+
+// classes: as above
+void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_classes, const uint32_t* classes, int n,
+                                    uint32_t* removed, int impl, void* scratch, hipStream_t s) {
+    if (removed)
+        if (hipError_t e = hipMemsetAsync(removed, 0, (size_t)n_classes * 4, s); e != hipSuccess)
+            throw std::runtime_error(std::string("unet_components: hipMemsetAsync: ") + hipGetErrorString(e));
+    if (n == 0) return;
+    const int S = W * H * D;   // < 2^31 (checked by the caller)
+    const ComponentsForest f = launch_components_label(W, H, D, label, n_classes, classes, n, impl, scratch, s);
+    const int nb = cmp_blocks(S, CMP_T);
+    k_cmp_best<<<nb, CMP_T, 0, s>>>(S, label, f.parent, f.count, f.best);
+    k_cmp_zero<<<nb, CMP_T, 0, s>>>(S, n_classes, label, f.parent, f.best, removed);
 }
 
 }  // namespace unet

@@ -326,6 +326,81 @@ def surface_qc(model, model_path, cases, labels=None):
     return 0, report
 
 
+# ---- lesion-wise detection per class (this project's: the reference's QC stops at the wrong-voxel ratios) ----------------------------
+LESION_COLUMNS = ("n_ref", "n_pred", "detected", "false_pos", "sensitivity", "precision", "f1")
+
+
+def lesion_report_path(model_path):
+    d, f = os.path.split(model_path)
+    return os.path.join(d, os.path.splitext(f)[0] + ".lesion_report.tsv")
+
+
+def format_lesion_report(out_count, rows):
+    """the report text; rows: (image, label, scores) with scores the dict of instances.detection (arrays of out_count entries), or
+    None for a case whose classes are not the model's (a shifted label): N/A in every column"""
+    lines = ["image\tground_truth" + "".join("\t%s%d" % (k, c) for c in range(1, out_count) for k in LESION_COLUMNS)]
+    for image, label, scores in rows:
+        cols = [os.path.basename(image), os.path.basename(label)]
+        for c in range(1, out_count):
+            cols += ["N/A"] * len(LESION_COLUMNS) if scores is None else [
+                "%d" % scores[k][c] if scores[k].dtype.kind == "i" else "%.9g" % scores[k][c] for k in LESION_COLUMNS]
+        lines.append("\t".join(cols))
+    return "\n".join(lines) + "\n"
+
+
+def lesion_qc(model, model_path, cases, labels=None, rule="any", threshold=0.0, min_voxels=1):
+    """Per case and class 1..out_count-1, the lesion-wise detection scores (instances.py, include/unet_instances.h) of the argmax of
+    the model's output against the label: the 6-connected instances of both maps with at least min_voxels voxels, a reference
+    instance detected and a predicted one true when a pair of one class overlaps (rule "any") or reaches the IoU `threshold` (rule
+    "iou").  Written to `<model stem>.lesion_report.tsv` beside the model -> (0, report path) or (1, message).  labels: the classes
+    to score (None: all; the others count nothing and read nan).  A case that label_plan marks as shifted gets N/A in every column."""
+    from . import instances as IN
+    cases = list(cases)
+    if not cases:
+        return 1, "no image/label pairs found"
+    if model.out_count < 2:
+        return 1, "QC requires a categorical model"
+    W, H, D = (int(v) for v in model.dim)
+    S = D * H * W
+    dev = model.device()
+    rows = []
+    try:
+        _, shift = label_plan(cases, model.out_count)
+        scratch = torch.empty(IN.inst_scratch_bytes(S, model.out_count, IN.DEFAULT_MAX_INSTANCES), dtype=torch.uint8, device=dev)
+        for case, shifted in zip(cases, shift):
+            scores = None
+            if not shifted:
+                image, label = case[2], case[3]
+                if int(np.prod(image.shape)) != S * model.in_count or int(np.prod(label.shape)) != S:
+                    raise UNetError("%s: training data dimension mismatch" % case[0])
+                x = _to_device(image, dev).view(1, model.in_count, D, H, W)
+                with torch.no_grad():
+                    logits = model._forward_level0(x)
+                if logits is None or tuple(logits.shape) != (1, model.out_count, D, H, W):
+                    raise UNetError("%s: model output dimension mismatch" % case[0])
+                got = torch.argmax(logits[0], dim=0).to(torch.int32).to(torch.uint16).contiguous()
+                want = torch.trunc(_to_device(label, dev)).clamp_(0, 65535).to(torch.int32).to(torch.uint16).view(D, H, W).contiguous()
+                scores = IN.lesion_scores(got, want, model.out_count, classes=labels, rule=rule, threshold=threshold,
+                                          min_voxels=min_voxels, scratch=scratch)
+            rows.append((case[0], case[1], scores))
+    except UNetError as e:
+        return 1, str(e)
+    report = lesion_report_path(model_path)
+    tmp = report + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(format_lesion_report(model.out_count, rows).encode())
+    except OSError as e:
+        return 1, "failed writing %s: %s" % (tmp, e)
+    try:
+        if os.path.lexists(report):
+            os.remove(report)
+        os.rename(tmp, report)
+    except OSError as e:
+        return 1, "cannot create %s: %s" % (report, e)
+    return 0, report
+
+
 def qc(model_path, cases, device="cuda:0", dtype="bf16", thread_count=4):
     """int qc(void) (qc.cpp:164-376) for cases already read -> (0, report path) or (1, message)"""
     from .unet3d import UNet3d
