@@ -30,6 +30,7 @@ from . import register  # noqa: F401  (the module: register.EXPORTS the symbols 
 from . import table  # noqa: F401  (the module: table.EXPORTS the symbols of include/unet_table.h)
 from . import distance  # noqa: F401  (the module: distance.EXPORTS the symbols of include/unet_distance.h)
 from . import instances  # noqa: F401  (the module: instances.EXPORTS the symbols of include/unet_instances.h)
+from . import morph  # noqa: F401  (the module: morph.EXPORTS the symbols of include/unet_morph.h)
 
 
 def save_to_file(model, file_name):

@@ -2607,4 +2607,110 @@ int unet_inst_remove_small(uint16_t* label, const int32_t* inst, int64_t voxels,
     });
 }
 
+// ---- binary morphology on bit-packed masks (include/unet_morph.h) ----
+static std::string morph_grid_error(const std::string& w_, int w, int h, int d) {
+    if (w <= 0 || h <= 0 || d <= 0) return w_ + "dimensions (w, h, d) must be positive";
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return w_ + "voxels must be in [1, 2^31), got " + std::to_string((int64_t)w * h * d);
+    return std::string();
+}
+static std::string morph_ptr_error(const std::string& w, const void* p, const char* name, int align) {
+    if (!p) return w + "null " + name;
+    if ((uintptr_t)p & (uintptr_t)(align - 1)) return w + name + " must be " + std::to_string(align) + "-byte aligned";
+    return std::string();
+}
+static std::string morph_scratch_error(const std::string& w_, int w, int h, int d, const void* scratch, size_t scratch_bytes) {
+    if (!scratch) return w_ + "null scratch";
+    if (scratch_bytes < morph_scratch_bytes(w, h, d)) return w_ + "scratch too small (see unet_morph_scratch_bytes)";
+    return std::string();
+}
+int unet_morph_scratch_bytes(int w, int h, int d, size_t* bytes) {
+    const std::string e = morph_grid_error("unet_morph_scratch_bytes: ", w, h, d);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_morph_scratch_bytes: null bytes");
+    *bytes = morph_scratch_bytes(w, h, d);
+    return 0;
+}
+int unet_morph_pack(int w, int h, int d, const void* labels, int label_bytes, int n_classes, const uint32_t* listed, int n_listed,
+                    uint64_t* bits, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_morph_pack: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty() && !labels) e = who + "null labels";
+    if (e.empty() && label_bytes != 1 && label_bytes != 2) e = who + "label_bytes must be 1 or 2, got " + std::to_string(label_bytes);
+    if (e.empty() && (n_classes < 1 || n_classes > 65536)) e = who + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
+    if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
+    if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
+    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty()) e = morph_scratch_error(who, w, h, d, scratch, scratch_bytes);
+    if (!e.empty()) return fail(e);
+    for (int i = 0; i < n_listed; ++i)
+        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
+            return fail(who + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]");
+    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
+    return pp_run(labels, stream, [&](hipStream_t s) {
+        launch_morph_pack(w, h, d, labels, label_bytes, n_classes, classes.data(), (int)classes.size(), bits, scratch, s);
+    });
+}
+int unet_morph_unpack(int w, int h, int d, const uint64_t* bits, uint8_t* mask, void* stream) {
+    const std::string who = "unet_morph_unpack: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty() && !mask) e = who + "null mask";
+    if (!e.empty()) return fail(e);
+    return pp_run(bits, stream, [&](hipStream_t s) { launch_morph_unpack(w, h, d, bits, mask, s); });
+}
+int unet_morph_count(int w, int h, int d, const uint64_t* bits, int64_t* count, void* stream) {
+    const std::string who = "unet_morph_count: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty()) e = morph_ptr_error(who, count, "count", 8);
+    if (!e.empty()) return fail(e);
+    return pp_run(bits, stream, [&](hipStream_t s) { launch_morph_count(w, h, d, bits, count, s); });
+}
+int unet_morph_step(int w, int h, int d, const uint64_t* in, uint64_t* out, int op, int connectivity, int iterations, int border, int impl,
+                    void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_morph_step: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = morph_ptr_error(who, in, "in", 8);
+    if (e.empty()) e = morph_ptr_error(who, out, "out", 8);
+    if (e.empty() && in == out) e = who + "in and out must not be the same mask";
+    if (e.empty() && op != UNET_MORPH_DILATE && op != UNET_MORPH_ERODE) e = who + "unknown op " + std::to_string(op);
+    if (e.empty() && connectivity != 6 && connectivity != 18 && connectivity != 26)
+        e = who + "connectivity must be 6, 18 or 26, got " + std::to_string(connectivity);
+    if (e.empty() && (iterations < 0 || iterations > UNET_MORPH_MAX_ITERATIONS))
+        e = who + "iterations must be in [0, 255], got " + std::to_string(iterations);
+    if (e.empty() && border != 0 && border != 1) e = who + "border must be 0 or 1, got " + std::to_string(border);
+    if (e.empty() && (impl < UNET_MORPH_IMPL_DEFAULT || impl > UNET_MORPH_IMPL_GLOBAL)) e = who + "unknown impl " + std::to_string(impl);
+    if (e.empty()) e = morph_scratch_error(who, w, h, d, scratch, scratch_bytes);
+    if (!e.empty()) return fail(e);
+    if (impl == UNET_MORPH_IMPL_DEFAULT) impl = UNET_MORPH_IMPL_GLOBAL;   // the faster as measured
+    return pp_run(in, stream, [&](hipStream_t s) {
+        launch_morph_step(w, h, d, in, out, op, connectivity, iterations, border, impl, scratch, s);
+    });
+}
+int unet_morph_holes(int w, int h, int d, const uint64_t* in, uint64_t* out, int64_t* info, int impl, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+    const std::string who = "unet_morph_holes: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = morph_ptr_error(who, in, "in", 8);
+    if (e.empty()) e = morph_ptr_error(who, out, "out", 8);
+    if (e.empty() && info) e = morph_ptr_error(who, info, "info", 8);
+    if (e.empty() && (impl < UNET_MORPH_IMPL_DEFAULT || impl > UNET_MORPH_IMPL_GLOBAL)) e = who + "unknown impl " + std::to_string(impl);
+    if (e.empty()) e = morph_scratch_error(who, w, h, d, scratch, scratch_bytes);
+    if (!e.empty()) return fail(e);
+    // this header's impls onto the labelling's: the tiled union-find in LDS, or every voxel hooked in global memory
+    const int labelling = impl == UNET_MORPH_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED;
+    return pp_run(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, scratch, s); });
+}
+int unet_morph_apply(int w, int h, int d, uint16_t* labels, const uint64_t* bits, int value, int mode, int64_t* changed, void* stream) {
+    const std::string who = "unet_morph_apply: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = morph_ptr_error(who, labels, "labels", 2);
+    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty() && (value < 1 || value > 65535)) e = who + "value must be in [1, 65535], got " + std::to_string(value);
+    if (e.empty() && mode != UNET_MORPH_SET && mode != UNET_MORPH_KEEP) e = who + "unknown mode " + std::to_string(mode);
+    if (e.empty() && changed) e = morph_ptr_error(who, changed, "changed", 8);
+    if (!e.empty()) return fail(e);
+    return pp_run(labels, stream, [&](hipStream_t s) { launch_morph_apply(w, h, d, labels, bits, value, mode, changed, s); });
+}
+
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
 #include "../../include/unet_instances.h"
+#include "../../include/unet_morph.h"
 #include "../../include/unet_postproc.h"
 #include "../../include/unet_preproc.h"
 #include "../../include/unet_qc.h"
@@ -413,6 +414,19 @@ void launch_inst_match(const int32_t* ia, const int32_t* ib, int64_t voxels, uns
                        int64_t* info, int impl, void* scratch, hipStream_t s);
 void launch_inst_remove_small(uint16_t* label, const int32_t* inst, int64_t voxels, const int64_t* rows, int64_t max_instances,
                               int64_t min_voxels, uint32_t* removed, int n_classes, hipStream_t s);
+
+// kernels_morph.hip: binary morphology on bit-packed masks (include/unet_morph.h); a mask is uint64[D][H][ceil(W / 64)].  classes: host
+// entries in (0, n_classes), read before the return; step's impl is LDS or GLOBAL, holes' labelling one of UNET_COMPONENTS_IMPL_*
+size_t morph_scratch_bytes(int W, int H, int D);
+void launch_morph_pack(int W, int H, int D, const void* labels, int label_bytes, int n_classes, const uint32_t* classes, int n,
+                       uint64_t* bits, void* scratch, hipStream_t s);
+void launch_morph_unpack(int W, int H, int D, const uint64_t* bits, uint8_t* mask, hipStream_t s);
+void launch_morph_count(int W, int H, int D, const uint64_t* bits, int64_t* count, hipStream_t s);
+void launch_morph_step(int W, int H, int D, const uint64_t* in, uint64_t* out, int op, int connectivity, int iterations, int border,
+                       int impl, void* scratch, hipStream_t s);
+void launch_morph_holes(int W, int H, int D, const uint64_t* in, uint64_t* out, int64_t* info, int labelling, void* scratch,
+                        hipStream_t s);
+void launch_morph_apply(int W, int H, int D, uint16_t* labels, const uint64_t* bits, int value, int mode, int64_t* changed, hipStream_t s);
 
 // kernels_atlas.hip: the atlas preparation of load_atlas (include/unet_atlas.h); grow: n_tissues host flags, read before the return.
 // reclassify uses the tables of the scratch only: atlas_scratch_bytes(1, R, T, 0) serves it

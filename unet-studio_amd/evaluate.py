@@ -28,6 +28,10 @@ evaluation set before the forward, evaluate.cpp:199; components.py) every listed
 6-connected component, after the chain and on the grid the chain ran on (the scan's own for a NativeVolume).  It acts on the label
 output only: without a chain (logits) or without "label" among the outputs it changes nothing.
 
+With `morphology` (a list of morph.run's ops: ("dilate" | "erode" | "open" | "close", value, connectivity, iterations) and
+("fill_holes", classes, value); morph.py) the `label` output is repaired on the device after single_component, on the grid the chain
+ran on and before the atlas stage.  A bad op ends the run before any forward, like a bad chain.  Without it nothing changes.
+
 With `fov_strategy="tiles"` (or "model" for a model whose fov_strategy says so; None and "align_top" are the path above) a volume
 larger than the model's field of view is no longer cropped: it is covered by overlapping windows of model.dim whose logits are
 blended (tiles.py, include/unet_tiles.h; the definitions are this project's).  A NativeVolume is preprocessed as above, resampled
@@ -54,6 +58,7 @@ import torch
 
 from . import components as CMP
 from . import engine as E
+from . import morph as MO
 from . import postproc as P
 from . import preproc as PRE
 from . import register as REG
@@ -64,7 +69,7 @@ from . import tiles as TL
 
 class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
-                 single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None):
+                 single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None, morphology=None):
         self.model = model
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
@@ -74,6 +79,7 @@ class EvaluateUNet:
         self.tile_overlap = tile_overlap       # the fraction of a tile shared with its neighbour, in [0, 0.5)
         self.atlas = atlas                     # a register.Atlas: the outputs "atlas" and "regions" become available
         self.atlas_options = atlas_options     # register.parcellate's keywords (init, step, stages, max_iterations, ...)
+        self.morphology = morphology           # a list of morph.run's ops on the label output, None / []: none
         self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
         self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
@@ -141,6 +147,7 @@ class EvaluateUNet:
                     raise E.UNetError("unknown fov_strategy %s" % (fov,))
                 tiled = fov == "tiles"
                 overlap = TL.check_overlap(self.tile_overlap) if tiled else 0.0
+                ops = MO.check_ops(self.morphology, m.out_count) if self.morphology else []
             except E.UNetError as e:
                 self.error_msg, self.aborted, self.running = str(e), True, False
                 return out
@@ -148,6 +155,8 @@ class EvaluateUNet:
             scratch = None                                 # the chain's scratch (defragment, per-plane commands), reused across volumes
             cmp_scratch = None                             # the component labelling's scratch, reused across volumes
             listed = listed if steps is not None and "label" in chain_outputs else []
+            ops = ops if steps is not None and "label" in chain_outputs else []
+            morph_scratch = None                           # the morphology's scratch, reused across volumes
             tab_scratch = None                             # the region table's scratch, reused across volumes
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
             mW, mH, mD = (int(v) for v in m.dim)
@@ -256,10 +265,15 @@ class EvaluateUNet:
                                 need = CMP.components_scratch_bytes(voxels, m.out_count)
                                 if cmp_scratch is None or cmp_scratch.numel() < need:
                                     cmp_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+                            if ops:
+                                need = MO.morph_scratch_bytes((d, io.shape[1], io.shape[2]))
+                                if morph_scratch is None or morph_scratch.numel() < need:
+                                    morph_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
                             results = P.run_postproc(result if stack is None else None, steps, outputs=chain_outputs, scratch=scratch,
                                                      native=None if nv is None else (back, native),
                                                      tiles=None if stack is None else (stack, plan, size),
-                                                     single_component=listed or None, component_scratch=cmp_scratch)
+                                                     single_component=listed or None, component_scratch=cmp_scratch,
+                                                     morphology=ops or None, morphology_scratch=morph_scratch)
                             extra = {}
                             if atl is not None and staged:                               # the atlas stage, on the compute stream
                                 label = results["label"].view(d, io.shape[1], io.shape[2])

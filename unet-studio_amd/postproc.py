@@ -12,7 +12,8 @@ label_prob or fg_prob (defragment, defragment_each, a per-plane command) it is l
 argmax needs a create_mask before it.  create_mask always sums the exponentials of the logits, so it may not follow such a command.
 The per-plane commands and defragment_each act on label_prob.  A wanted output the chain does not produce is refused.
 Adjacent softmax / create_mask / argmax run as one fused kernel, and an output nobody asked for and no later command reads is
-never written (the default chain with outputs=("label",) reads the logits once and writes 2 bytes per voxel)."""
+never written (the default chain with outputs=("label",) reads the logits once and writes 2 bytes per voxel).
+run_postproc(morphology=...) repairs the `label` output afterwards (morph.py: dilate / erode / open / close / fill_holes)."""
 import ctypes as C
 
 import torch
@@ -172,7 +173,7 @@ def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
 
 
 def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
-                 component_scratch=None, tiles=None):
+                 component_scratch=None, tiles=None, morphology=None, morphology_scratch=None):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
     scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
@@ -186,7 +187,10 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     uint8 device tensor of components.components_scratch_bytes(voxels, C) bytes to reuse.
     tiles: (stack, plan, (D, H, W)) in place of logits (pass None): the volume is the blend of a stack of tile logits (tiles.py,
     include/unet_tiles.h).  A fused group that starts the chain blends the logits it reads and never stores them
-    (tiles.postproc_tiles); a later group reads the blended canvas logits, made once when first needed.  Not with native."""
+    (tiles.postproc_tiles); a later group reads the blended canvas logits, made once when first needed.  Not with native.
+    morphology: a list of morph.run's ops, run in place on the `label` output after single_component, on the grid the chain ran on;
+    fg_prob and label_prob are not touched.  None or an empty list, or a chain whose wanted outputs hold no label, make no extra
+    call.  morphology_scratch: a uint8 device tensor of morph.morph_scratch_bytes((D, H, W)) bytes to reuse."""
     steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
     check_chain(steps)
     outputs = tuple(outputs)
@@ -220,6 +224,9 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     for v in listed:
         if v <= 0 or v >= out_c:
             raise UNetError("single_component: class %d is not in [1, %d]" % (v, out_c - 1))
+    if morphology:
+        from . import morph as MO
+        morphology = MO.check_ops(morphology, out_c)   # a bad op is refused before any device work
     names = [n for n, _ in steps]
     from_state = argmax_after_change(steps) and "label" in outputs
     want_lp = ("label_prob" in outputs or from_state) and "softmax" in names
@@ -284,4 +291,6 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     if listed and "label" in outputs:
         from . import components as CMP
         CMP.keep_largest(res["label"], listed, out_c, scratch=component_scratch)
+    if morphology and "label" in outputs:
+        MO.run(res["label"], morphology, out_c, scratch=morphology_scratch)
     return {k: v for k, v in res.items() if k in outputs}
