@@ -57,7 +57,8 @@
  * (a null pointer, a misaligned output, a size out of range, a grid of 2^31 voxels or more, a scratch that is too small, an unknown
  * impl, a bad list entry) are found before any device call, with a message naming the argument.
  *
- * Out of scope: 18- and 26-connectivity; an optimal one-to-one assignment between instances.
+ * Out of scope: 18- and 26-connectivity here (unet_connectivity.h has the labelling call with a connectivity argument); an optimal
+ * one-to-one assignment between instances.
  *
  * Status codes / errors as in unet_hip.h (0 = ok, the message is read with unet_last_error).
  */

@@ -53,7 +53,7 @@
  * in == out, a scratch that is too small, a bad list entry) are found before any device call, with a message naming the argument.
  *
  * Out of scope: grey-scale morphology; structuring elements other than the three; hole filling with an 18- or 26-connected
- * background; geodesic reconstruction.
+ * background here (unet_connectivity.h has the hole filling call with a connectivity argument); geodesic reconstruction.
  *
  * Status codes / errors as in unet_hip.h (0 = ok, the message is read with unet_last_error).
  */

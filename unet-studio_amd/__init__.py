@@ -31,6 +31,7 @@ from . import table  # noqa: F401  (the module: table.EXPORTS the symbols of inc
 from . import distance  # noqa: F401  (the module: distance.EXPORTS the symbols of include/unet_distance.h)
 from . import instances  # noqa: F401  (the module: instances.EXPORTS the symbols of include/unet_instances.h)
 from . import morph  # noqa: F401  (the module: morph.EXPORTS the symbols of include/unet_morph.h)
+from . import connectivity  # noqa: F401  (the module: connectivity.EXPORTS the symbols of include/unet_connectivity.h)
 
 
 def save_to_file(model, file_name):

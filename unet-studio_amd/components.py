@@ -4,11 +4,13 @@ smallest linear index among equal counts, and every other voxel of that class be
 
 The definition is this project's; parity with TIPL's evalution_set is not pinned.  All listed classes are labelled
 in one pass over the uint16 label map: IMPL_TILED builds each TILE's union-find in LDS and hooks the tiles together across their
-faces, IMPL_GLOBAL hooks every voxel in global memory (the measured baseline and a second witness of the bits)."""
+faces, IMPL_GLOBAL hooks every voxel in global memory (the measured baseline and a second witness of the bits).
+keep_largest(connectivity=18 | 26) goes through connectivity.py (include/unet_connectivity.h)."""
 import ctypes as C
 
 import torch
 
+from . import connectivity as CN
 from . import engine as E
 from .engine import UNetError
 
@@ -48,11 +50,14 @@ def components_scratch_bytes(voxels, n_classes):
     return n.value
 
 
-def keep_largest(label, classes, n_classes, removed=None, scratch=None, impl=IMPL_DEFAULT, stream=None):
+def keep_largest(label, classes, n_classes, removed=None, scratch=None, impl=IMPL_DEFAULT, stream=None, connectivity=6):
     """In place on label, a (D, H, W) uint16 device tensor, on the current stream (or the raw `stream`); returns label.
     classes: the listed classes (an empty list changes nothing).  removed: a uint32 / int32 device tensor of n_classes entries that
     receives the voxels zeroed per class.  scratch: a uint8 device tensor of components_scratch_bytes(D*H*W, n_classes) bytes to
-    reuse (one is made when needed)."""
+    reuse (one is made when needed).  connectivity: 6 (this header's call), 18 or 26 (connectivity.keep_largest: the same scratch
+    size and impl values serve it)."""
+    if CN.check(connectivity, "components.keep_largest") != 6:
+        return CN.keep_largest(label, classes, n_classes, connectivity, removed=removed, scratch=scratch, impl=impl, stream=stream)
     if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.uint16 and label.is_contiguous() and label.dim() == 3):
         raise UNetError("components: label must be a contiguous uint16 (D, H, W) device tensor")
     D, H, W = (int(v) for v in label.shape)

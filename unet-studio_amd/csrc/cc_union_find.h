@@ -1,5 +1,5 @@
-// Union-find label equivalence for 6-connected components, shared by kernels_postproc.hip (defragment: one binary mask) and
-// kernels_components.hip (single_component_label: equal values of a label map).  parent[j] <= j always: a tree's root is the
+// Union-find label equivalence for connected components, shared by kernels_postproc.hip (defragment: one binary mask, 6-connected)
+// and kernels_components.hip (equal values of a label map, 6-, 18- or 26-connected).  parent[j] <= j always: a tree's root is the
 // smallest index hooked into it so far, and when all hooking is done the component's smallest linear index, whatever the schedule.
 // The functions take global or LDS arrays alike (they are inlined; the compiler resolves the address space).
 #pragma once
@@ -11,6 +11,26 @@ constexpr int CC_RUN = 16;         // consecutive voxels per thread in the size 
 
 __device__ __forceinline__ int cc_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void cc_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The backward half N-(CONN) of a 6-, 18- or 26-neighbourhood: the offsets (dx, dy, dz) in {-1, 0, 1}^3 with
+// 1 <= |dx| + |dy| + |dz| <= 1, 2, 3 whose neighbour has the smaller linear index (dz = -1, or dz = 0 and dy = -1, or dz = dy = 0
+// and dx = -1): 3, 9, 13 offsets.  A voxel that hooks to every neighbour of N- is hooked from every neighbour of the other half.
+// f(dx, dy, dz) is called once per offset; the loops unroll, so f sees constants
+template <int CONN, class F>
+__device__ __forceinline__ void cc_for_backward(F&& f) {
+    static_assert(CONN == 6 || CONN == 18 || CONN == 26, "connectivity is 6, 18 or 26");
+    constexpr int reach = CONN == 6 ? 1 : CONN == 18 ? 2 : 3;
+#pragma unroll
+    for (int dz = -1; dz <= 0; ++dz)
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int n1 = (dx ? 1 : 0) + (dy ? 1 : 0) + (dz ? 1 : 0);
+                const bool back = dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0)));
+                if (back && n1 >= 1 && n1 <= reach) f(dx, dy, dz);
+            }
+}
 
 // root of i, halving the path on the way.  parent[j] <= j always, so every store points j at one of its ancestors.
 // Terminates: cur strictly decreases with every step and is bounded below by 0

@@ -2251,7 +2251,7 @@ int unet_components_keep_largest(int w, int h, int d, uint16_t* label, int n_cla
     std::sort(classes.begin(), classes.end());
     classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
     return pp_run(label, stream, [&](hipStream_t s) {
-        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, scratch, s);
+        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, 6, scratch, s);
     });
 }
 
@@ -2557,7 +2557,7 @@ int unet_inst_label(int w, int h, int d, const uint16_t* label, int n_classes, c
     std::sort(classes.begin(), classes.end());
     classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
     return pp_run(label, stream, [&](hipStream_t s) {
-        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, scratch, s);
+        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, 6, scratch, s);
     });
 }
 int unet_inst_match_scratch_bytes(int64_t max_pairs, size_t* bytes) {
@@ -2699,7 +2699,7 @@ int unet_morph_holes(int w, int h, int d, const uint64_t* in, uint64_t* out, int
     if (!e.empty()) return fail(e);
     // this header's impls onto the labelling's: the tiled union-find in LDS, or every voxel hooked in global memory
     const int labelling = impl == UNET_MORPH_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED;
-    return pp_run(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, scratch, s); });
+    return pp_run(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, 6, scratch, s); });
 }
 int unet_morph_apply(int w, int h, int d, uint16_t* labels, const uint64_t* bits, int value, int mode, int64_t* changed, void* stream) {
     const std::string who = "unet_morph_apply: ";
@@ -2711,6 +2711,109 @@ int unet_morph_apply(int w, int h, int d, uint16_t* labels, const uint64_t* bits
     if (e.empty() && changed) e = morph_ptr_error(who, changed, "changed", 8);
     if (!e.empty()) return fail(e);
     return pp_run(labels, stream, [&](hipStream_t s) { launch_morph_apply(w, h, d, labels, bits, value, mode, changed, s); });
+}
+
+// ---- connected components with a chosen connectivity (include/unet_connectivity.h) ----
+// the siblings of the keep-largest, instance labelling and hole filling calls above with a connectivity of 6, 18 or 26; the impl
+// values are those of the labelling stage (DEFAULT and TILED: the tile's union-find in LDS, GLOBAL: every voxel in global memory)
+static std::string conn_error(const std::string& w, int connectivity, int impl) {
+    if (connectivity != UNET_CONN_6 && connectivity != UNET_CONN_18 && connectivity != UNET_CONN_26)
+        return w + "connectivity must be 6, 18 or 26, got " + std::to_string(connectivity);
+    if (impl < UNET_CONN_IMPL_DEFAULT || impl > UNET_CONN_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
+    return std::string();
+}
+static std::string conn_size_error(const std::string& w, int64_t voxels, int n_classes) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
+    if (n_classes < 1 || n_classes > 65536) return w + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
+    return std::string();
+}
+static std::string conn_list_error(const std::string& w, const uint32_t* listed, int n_listed, int n_classes) {
+    for (int i = 0; i < n_listed; ++i)
+        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
+            return w + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]";
+    return std::string();
+}
+int unet_conn_scratch_bytes(int64_t voxels, int n_classes, size_t* bytes) {
+    const std::string e = conn_size_error("unet_conn_scratch_bytes: ", voxels, n_classes);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_conn_scratch_bytes: null bytes");
+    *bytes = components_scratch_bytes(voxels, n_classes);
+    return 0;
+}
+int unet_conn_keep_largest(int w, int h, int d, uint16_t* label, int n_classes, const uint32_t* listed, int n_listed, uint32_t* removed,
+                           int connectivity, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_conn_keep_largest: ";
+    if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions (w, h, d) must be positive");
+    std::string e = conn_size_error(who, (int64_t)w * h * d, n_classes);
+    if (e.empty() && !label) e = who + "null label";
+    if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
+    if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
+    if (e.empty()) e = conn_error(who, connectivity, impl);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < components_scratch_bytes((int64_t)w * h * d, n_classes))
+        e = who + "scratch too small (see unet_conn_scratch_bytes)";
+    if (e.empty()) e = conn_list_error(who, listed, n_listed, n_classes);
+    if (!e.empty()) return fail(e);
+    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
+    std::sort(classes.begin(), classes.end());
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    return pp_run(label, stream, [&](hipStream_t s) {
+        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, connectivity, scratch, s);
+    });
+}
+int unet_conn_label_scratch_bytes(int64_t voxels, int n_classes, int64_t max_instances, size_t* bytes) {
+    const std::string e = inst_size_error("unet_conn_label_scratch_bytes: ", voxels, n_classes, max_instances);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_conn_label_scratch_bytes: null bytes");
+    *bytes = inst_scratch_bytes(voxels, n_classes, max_instances);
+    return 0;
+}
+int unet_conn_label(int w, int h, int d, const uint16_t* label, int n_classes, const uint32_t* listed, int n_listed, int32_t* inst,
+                    int64_t* rows, int64_t max_instances, int64_t* info, int connectivity, int impl, void* scratch, size_t scratch_bytes,
+                    void* stream) {
+    const std::string who = "unet_conn_label: ";
+    if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions (w, h, d) must be positive");
+    std::string e = inst_size_error(who, (int64_t)w * h * d, n_classes, max_instances);
+    if (e.empty() && !label) e = who + "null label";
+    if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
+    if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
+    if (e.empty()) e = inst_out_error(who, inst, "inst", 4);
+    if (e.empty()) e = inst_out_error(who, rows, "rows", 8);
+    if (e.empty()) e = inst_out_error(who, info, "info", 8);
+    if (e.empty()) e = conn_error(who, connectivity, impl);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < inst_scratch_bytes((int64_t)w * h * d, n_classes, max_instances))
+        e = who + "scratch too small (see unet_conn_label_scratch_bytes)";
+    if (e.empty()) e = conn_list_error(who, listed, n_listed, n_classes);
+    if (!e.empty()) return fail(e);
+    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
+    std::sort(classes.begin(), classes.end());
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    return pp_run(label, stream, [&](hipStream_t s) {
+        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, connectivity,
+                          scratch, s);
+    });
+}
+int unet_conn_holes_scratch_bytes(int w, int h, int d, size_t* bytes) {
+    const std::string e = morph_grid_error("unet_conn_holes_scratch_bytes: ", w, h, d);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_conn_holes_scratch_bytes: null bytes");
+    *bytes = morph_scratch_bytes(w, h, d);
+    return 0;
+}
+int unet_conn_holes(int w, int h, int d, const uint64_t* in, uint64_t* out, int64_t* info, int connectivity, int impl, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_conn_holes: ";
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = morph_ptr_error(who, in, "in", 8);
+    if (e.empty()) e = morph_ptr_error(who, out, "out", 8);
+    if (e.empty() && info) e = morph_ptr_error(who, info, "info", 8);
+    if (e.empty()) e = conn_error(who, connectivity, impl);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < morph_scratch_bytes(w, h, d)) e = who + "scratch too small (see unet_conn_holes_scratch_bytes)";
+    if (!e.empty()) return fail(e);
+    const int labelling = impl == UNET_CONN_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED;
+    return pp_run(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, connectivity, scratch, s); });
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "../../include/unet_atlas.h"
 #include "../../include/unet_augment.h"
 #include "../../include/unet_components.h"
+#include "../../include/unet_connectivity.h"
 #include "../../include/unet_distance.h"
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
@@ -389,11 +390,12 @@ void launch_preproc_upsample(const float* src, float* dst, int w, int h, int d, 
 void launch_preproc_permute(const float* src, float* dst, int w, int h, int d, int channels, int op, hipStream_t s);
 void launch_preproc_normalize(float* buf, int64_t values, void* scratch, hipStream_t s);
 
-// kernels_components.hip: a model's single_component_label (include/unet_components.h); classes: sorted distinct host entries
+// kernels_components.hip: a model's single_component_label (include/unet_components.h); classes: sorted distinct host entries;
+// connectivity: 6, 18 or 26 (include/unet_connectivity.h), here and in the launches below that take one
 size_t components_scratch_bytes(int64_t S, int n_classes);
 void launch_components_keep_largest(int W, int H, int D, uint16_t* label, int n_classes, const uint32_t* classes, int n,
-                                    uint32_t* removed, int impl, void* scratch, hipStream_t s);
-// the labelling stage alone (shared with kernels_instances.hip): parent[v] = the smallest linear index of v's component or -1,
+                                    uint32_t* removed, int impl, int connectivity, void* scratch, hipStream_t s);
+// the labelling stage alone (shared with kernels_instances.hip and kernels_morph.hip): parent[v] = the smallest linear index of v's component or -1,
 // count[r] = the component's voxels at a root r; both live in the scratch.  end: the first byte behind what
 // components_scratch_bytes covers from the scratch's 256-B aligned base (itself 256-B aligned); best: keep_largest's per-class table
 struct ComponentsForest {
@@ -403,12 +405,12 @@ struct ComponentsForest {
     unsigned long long* best;
 };
 ComponentsForest launch_components_label(int W, int H, int D, const uint16_t* label, int n_classes, const uint32_t* classes, int n,
-                                         int impl, void* scratch, hipStream_t s);
+                                         int impl, int connectivity, void* scratch, hipStream_t s);
 
 // kernels_instances.hip: the instances of a label map (include/unet_instances.h); classes as above
 size_t inst_scratch_bytes(int64_t S, int n_classes, int64_t max_instances);
 void launch_inst_label(int W, int H, int D, const uint16_t* label, int n_classes, const uint32_t* classes, int n, int32_t* inst,
-                       int64_t* rows, int64_t max_instances, int64_t* info, int impl, void* scratch, hipStream_t s);
+                       int64_t* rows, int64_t max_instances, int64_t* info, int impl, int connectivity, void* scratch, hipStream_t s);
 size_t inst_match_scratch_bytes(int64_t max_pairs);
 void launch_inst_match(const int32_t* ia, const int32_t* ib, int64_t voxels, unsigned long long* keys, int64_t* counts, int64_t max_pairs,
                        int64_t* info, int impl, void* scratch, hipStream_t s);
@@ -424,8 +426,8 @@ void launch_morph_unpack(int W, int H, int D, const uint64_t* bits, uint8_t* mas
 void launch_morph_count(int W, int H, int D, const uint64_t* bits, int64_t* count, hipStream_t s);
 void launch_morph_step(int W, int H, int D, const uint64_t* in, uint64_t* out, int op, int connectivity, int iterations, int border,
                        int impl, void* scratch, hipStream_t s);
-void launch_morph_holes(int W, int H, int D, const uint64_t* in, uint64_t* out, int64_t* info, int labelling, void* scratch,
-                        hipStream_t s);
+void launch_morph_holes(int W, int H, int D, const uint64_t* in, uint64_t* out, int64_t* info, int labelling, int connectivity,
+                        void* scratch, hipStream_t s);
 void launch_morph_apply(int W, int H, int D, uint16_t* labels, const uint64_t* bits, int value, int mode, int64_t* changed, hipStream_t s);
 
 // kernels_atlas.hip: the atlas preparation of load_atlas (include/unet_atlas.h); grow: n_tissues host flags, read before the return.

@@ -504,10 +504,10 @@ size_t inst_scratch_bytes(int64_t S, int n_classes, int64_t max_instances) {
 
 // classes: n sorted distinct entries in (0, n_classes), host memory; read before this returns
 void launch_inst_label(int W, int H, int D, const uint16_t* label, int n_classes, const uint32_t* classes, int n, int32_t* inst,
-                       int64_t* rows, int64_t M, int64_t* info, int impl, void* scratch, hipStream_t s) {
+                       int64_t* rows, int64_t M, int64_t* info, int impl, int connectivity, void* scratch, hipStream_t s) {
     const int S = W * H * D;   // < 2^31 (checked by the caller)
     const int cmp_impl = impl == UNET_INST_LABEL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED;   // DEFAULT: TILED
-    const ComponentsForest f = launch_components_label(W, H, D, label, n_classes, classes, n, cmp_impl, scratch, s);
+    const ComponentsForest f = launch_components_label(W, H, D, label, n_classes, classes, n, cmp_impl, connectivity, scratch, s);
     const Extras x = inst_extras(f.end, S, M);
     const unsigned nblk = inst_blocks(S);
     k_inst_sums<<<nblk, INST_T, 0, s>>>(S, f.parent, x.bsum);

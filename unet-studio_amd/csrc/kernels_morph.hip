@@ -432,16 +432,16 @@ void launch_morph_step(int W, int H, int D, const uint64_t* in, uint64_t* out, i
     }
 }
 
-// labelling: UNET_COMPONENTS_IMPL_*
-void launch_morph_holes(int W, int H, int D, const uint64_t* in, uint64_t* out, int64_t* info, int labelling, void* scratch,
-                        hipStream_t s) {
+// labelling: UNET_COMPONENTS_IMPL_*; connectivity: the background's, 6, 18 or 26
+void launch_morph_holes(int W, int H, int D, const uint64_t* in, uint64_t* out, int64_t* info, int labelling, int connectivity,
+                        void* scratch, hipStream_t s) {
     const int64_t wpl = morph_wpl(W), words = wpl * H * D, S = (int64_t)W * H * D;
     const Scratch sc = morph_scratch(scratch, words, S);
     if (info) morph_check(hipMemsetAsync(info, 0, 16, s), "hipMemsetAsync");
     const unsigned nb = morph_word_blocks(words);
     k_morph_background<<<nb, MORPH_T, 0, s>>>(W, (int)wpl, words, (const u64*)in, sc.background);
     const uint32_t one = 1;
-    const ComponentsForest f = launch_components_label(W, H, D, sc.background, 2, &one, 1, labelling, sc.labelling, s);
+    const ComponentsForest f = launch_components_label(W, H, D, sc.background, 2, &one, 1, labelling, connectivity, sc.labelling, s);
     const int64_t faces = 2 * ((int64_t)H * D + (int64_t)W * D + (int64_t)W * H);
     k_morph_faces<<<morph_capped(faces, MORPH_T), MORPH_T, 0, s>>>(W, H, D, f.parent, f.count);
     k_morph_holes<<<nb, MORPH_T, 0, s>>>(W, (int)wpl, words, morph_tail(W), (const u64*)in, f.parent, f.count, (u64*)out, (u64*)info);

@@ -25,11 +25,12 @@ grid and orientation.  A plain array is already past the read stage: with a prep
 
 With `single_component` (a list of classes, or "model" for model.single_component_label, which the reference hands to every
 evaluation set before the forward, evaluate.cpp:199; components.py) every listed class of the `label` output keeps its largest
-6-connected component, after the chain and on the grid the chain ran on (the scan's own for a NativeVolume).  It acts on the label
-output only: without a chain (logits) or without "label" among the outputs it changes nothing.
+connected component, after the chain and on the grid the chain ran on (the scan's own for a NativeVolume).  It acts on the label
+output only: without a chain (logits) or without "label" among the outputs it changes nothing.  `single_component_connectivity` (6,
+18 or 26; connectivity.py) says what joins the voxels of a component; any other value ends the run before any forward.
 
 With `morphology` (a list of morph.run's ops: ("dilate" | "erode" | "open" | "close", value, connectivity, iterations) and
-("fill_holes", classes, value); morph.py) the `label` output is repaired on the device after single_component, on the grid the chain
+("fill_holes", classes, value[, connectivity]); morph.py) the `label` output is repaired on the device after single_component, on the grid the chain
 ran on and before the atlas stage.  A bad op ends the run before any forward, like a bad chain.  Without it nothing changes.
 
 With `fov_strategy="tiles"` (or "model" for a model whose fov_strategy says so; None and "align_top" are the path above) a volume
@@ -57,6 +58,7 @@ import numpy as np
 import torch
 
 from . import components as CMP
+from . import connectivity as CN
 from . import engine as E
 from . import morph as MO
 from . import postproc as P
@@ -69,12 +71,14 @@ from . import tiles as TL
 
 class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
-                 single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None, morphology=None):
+                 single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None, morphology=None,
+                 single_component_connectivity=6):
         self.model = model
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
         self.orientation = orientation         # a flip / swap chain, "model" for model.orientation, None / "": none
         self.single_component = single_component   # a list of classes, "model" for model.single_component_label, None: none
+        self.single_component_connectivity = single_component_connectivity   # 6, 18 or 26: what joins a component's voxels
         self.fov_strategy = fov_strategy       # None / "align_top": one window; "tiles": blended tiles; "model": model.fov_strategy
         self.tile_overlap = tile_overlap       # the fraction of a tile shared with its neighbour, in [0, 0.5)
         self.atlas = atlas                     # a register.Atlas: the outputs "atlas" and "regions" become available
@@ -142,6 +146,7 @@ class EvaluateUNet:
                 ori = PRE.parse_orientation(m.orientation if self.orientation == "model" else self.orientation)
                 D0, vs0, M = PRE.orientation_map(ori, m.dim, m.voxel_size) if ori else (None, None, None)
                 listed = CMP.resolve(self.single_component, m)
+                cmp_conn = CN.check(self.single_component_connectivity, "single_component")
                 fov = m.fov_strategy if self.fov_strategy == "model" else self.fov_strategy
                 if fov not in (None, "", "align_top", "tiles"):
                     raise E.UNetError("unknown fov_strategy %s" % (fov,))
@@ -273,6 +278,7 @@ class EvaluateUNet:
                                                      native=None if nv is None else (back, native),
                                                      tiles=None if stack is None else (stack, plan, size),
                                                      single_component=listed or None, component_scratch=cmp_scratch,
+                                                     single_component_connectivity=cmp_conn,
                                                      morphology=ops or None, morphology_scratch=morph_scratch)
                             extra = {}
                             if atl is not None and staged:                               # the atlas stage, on the compute stream

@@ -7,14 +7,15 @@
   detection, lesion_scores   lesion-wise scores per class, host arithmetic in float64 on those tables
 
 The reference stops at voxel counts (evaluate.cpp, qc.cpp), so these are this project's definitions (parity NOT pinned).  Every
-device value is an integer: the device is pinned to the numpy restatements of tests/test_instances_host.py bit for bit.  Out of scope:
-18- and 26-connectivity, an optimal one-to-one assignment between instances, and wiring either call into EvaluateUNet or the
-post-processing chain."""
+device value is an integer: the device is pinned to the numpy restatements of tests/test_instances_host.py bit for bit.
+label(connectivity=18 | 26) and lesion_scores(connectivity=...) go through connectivity.py (include/unet_connectivity.h).  Out of
+scope: an optimal one-to-one assignment between instances, and wiring either call into EvaluateUNet or the post-processing chain."""
 import ctypes as C
 
 import numpy as np
 import torch
 
+from . import connectivity as CN
 from . import engine as E
 from .engine import UNetError
 
@@ -77,12 +78,16 @@ def _label_map(labels, who):
     return labels if labels.dtype == torch.uint16 else labels.to(torch.int32).to(torch.uint16)
 
 
-def label(labels, n_classes, classes=None, max_instances=DEFAULT_MAX_INSTANCES, impl=LABEL_DEFAULT, scratch=None, out=None, stream=None):
+def label(labels, n_classes, classes=None, max_instances=DEFAULT_MAX_INSTANCES, impl=LABEL_DEFAULT, scratch=None, out=None, stream=None,
+          connectivity=6):
     """unet_inst_label on the current stream (or the raw `stream`).  labels: a (D, H, W) uint16 device tensor (uint8 is cast).
     classes: the listed classes, None for 1..n_classes-1.  Returns (inst, rows, info) on the device: inst int32 (D, H, W), 0 or the
     dense id of the voxel's 6-connected component; rows int64 {max_instances + 1, 12}: class, voxels, sums of x, y, z, minima, maxima,
     smallest linear index (row 0 and the rows above N are empty: 0, 0, 0, 0, 0, (W, H, D), -1, -1, -1, -1); info int64[2] = (N,
-    min(N, max_instances)).  out: (inst, rows, info) to write into.  No host synchronisation."""
+    min(N, max_instances)).  out: (inst, rows, info) to write into.  No host synchronisation.  connectivity: 6 (this header's
+    call), 18 or 26 (connectivity.label: the same outputs, scratch size and impl values)."""
+    if CN.check(connectivity, "instances.label") != 6:
+        return CN.label(labels, n_classes, classes, connectivity, max_instances, impl=impl, scratch=scratch, out=out, stream=stream)
     lab = _label_map(labels, "label")
     D, H, W = (int(v) for v in lab.shape)
     nc, M = int(n_classes), int(max_instances)
@@ -250,22 +255,24 @@ def detection(rows_ref, rows_pred, pairs, n_classes, rule="any", threshold=0.0, 
             "false_pos": n_pred - true_pred, "sensitivity": sens, "precision": prec, "f1": f1, "instances": inst, "instance_dice": dice}
 
 
-def _label_all(labels, n_classes, classes, max_instances, impl, scratch):
+def _label_all(labels, n_classes, classes, max_instances, impl, scratch, connectivity=6):
     """label with rows for every instance: called again with N rows when N exceeds max_instances (reads info back)"""
-    inst, rows, info = label(labels, n_classes, classes, max_instances, impl=impl, scratch=scratch)
+    inst, rows, info = label(labels, n_classes, classes, max_instances, impl=impl, scratch=scratch, connectivity=connectivity)
     n = int(info[0].item())
     if n > int(max_instances):
-        inst, rows, info = label(labels, n_classes, classes, n, impl=impl, scratch=None)
+        inst, rows, info = label(labels, n_classes, classes, n, impl=impl, scratch=None, connectivity=connectivity)
     return inst, rows[:n + 1]
 
 
 def lesion_scores(pred, ref, n_classes, classes=None, rule="any", threshold=0.0, min_voxels=1, max_instances=DEFAULT_MAX_INSTANCES,
-                  max_pairs=DEFAULT_MAX_PAIRS, impl=LABEL_DEFAULT, match_impl=IMPL_DEFAULT, scratch=None):
+                  max_pairs=DEFAULT_MAX_PAIRS, impl=LABEL_DEFAULT, match_impl=IMPL_DEFAULT, scratch=None, connectivity=6):
     """`detection` of a predicted label map against a reference one, both (D, H, W) uint8 / uint16 device tensors of one shape: two
-    `label` calls, one `match`, then the host arithmetic.  Returns detection's dict."""
+    `label` calls, one `match`, then the host arithmetic.  Returns detection's dict.  connectivity: 6, 18 or 26, what joins the
+    voxels of one lesion in both maps (26 is what lesion-wise scores in the literature count)."""
+    CN.check(connectivity, "instances.lesion_scores")
     if not (torch.is_tensor(pred) and torch.is_tensor(ref) and tuple(pred.shape) == tuple(ref.shape)):
         raise UNetError("instances.lesion_scores: pred and ref must be device tensors of one shape")
-    inst_r, rows_r = _label_all(ref, n_classes, classes, max_instances, impl, scratch)
-    inst_p, rows_p = _label_all(pred, n_classes, classes, max_instances, impl, scratch)
+    inst_r, rows_r = _label_all(ref, n_classes, classes, max_instances, impl, scratch, connectivity)
+    inst_p, rows_p = _label_all(pred, n_classes, classes, max_instances, impl, scratch, connectivity)
     pairs = match(inst_r.view(-1), inst_p.view(-1), max_pairs, impl=match_impl)
     return detection(rows_r, rows_p, pairs, n_classes, rule=rule, threshold=threshold, min_voxels=min_voxels)

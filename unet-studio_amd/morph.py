@@ -5,7 +5,8 @@
   open, close                host chains: open = dilate n of (erode n, border 1), close = erode n, border 1, of (dilate n); with
                              border 1 a closing never removes a voxel and an opening never adds one
   fill_holes                 the 6-connected components of the complement that touch no face of the volume are set
-                             (scipy.ndimage.binary_fill_holes with its default structure), through the exact labelling of components.py
+                             (scipy.ndimage.binary_fill_holes with its default structure), through the exact labelling of components.py;
+                             connectivity=18 | 26 chooses the background's connectivity through connectivity.py
   dilate_label, erode_label, open_label, close_label, fill_holes_label     the same on one value of a uint16 label map, in place
   run                        a list of such ops on a label map; postproc.run_postproc(morphology=...) and EvaluateUNet(morphology=...)
                              run it on the `label` output after single_component
@@ -13,12 +14,12 @@
 The reference leaves this to TIPL (defragment_smoothing, fill_and_smooth_labels), so these are this project's definitions (parity NOT
 pinned).  Every device value is a bit or an integer count: the device is pinned to the numpy restatements of
 tests/test_morph_host.py bit for bit.  No function here synchronises with the host.  Out of scope: grey-scale morphology, structuring
-elements other than the three, hole filling with an 18- or 26-connected background, geodesic reconstruction, acting on fg_prob /
-label_prob, the C++ host, and 18- / 26-connectivity for components / instances, which stay as their headers say."""
+elements other than the three, geodesic reconstruction, acting on fg_prob / label_prob, and the C++ host."""
 import ctypes as C
 
 import torch
 
+from . import connectivity as CN
 from . import engine as E
 from .engine import UNetError
 
@@ -181,8 +182,12 @@ def close(m, connectivity=6, iterations=1, impl=IMPL_DEFAULT, scratch=None):
     return erode(dilate(m, connectivity, iterations, impl, scratch), connectivity, iterations, impl, scratch, border=1)
 
 
-def fill_holes(m, impl=IMPL_DEFAULT, scratch=None, out=None):
-    """unet_morph_holes: (Mask, info); info a device int64[2] tensor: the voxels filled, the holes.  out may be m"""
+def fill_holes(m, impl=IMPL_DEFAULT, scratch=None, out=None, connectivity=6):
+    """unet_morph_holes: (Mask, info); info a device int64[2] tensor: the voxels filled, the holes.  out may be m.  connectivity: the
+    background's, 6 (this header's call), 18 or 26 (connectivity.fill_holes: the same scratch size and impl values)"""
+    _mask(m, "fill_holes")
+    if CN.check(connectivity, "morph.fill_holes") != 6:
+        return CN.fill_holes(m, connectivity, impl=impl, scratch=scratch, out=out)
     D, H, W = _mask(m, "fill_holes").shape
     out = _out_mask(out, m, "fill_holes")
     scratch, sbytes = _scratch(scratch, m.shape, m.bits.device)
@@ -254,20 +259,22 @@ def open_label(labels, value, connectivity=6, iterations=1, impl=IMPL_DEFAULT, s
     return _label_op("open", labels, value, connectivity, iterations, 0, impl, scratch, changed)
 
 
-def fill_holes_label(labels, classes, value, n_classes, impl=IMPL_DEFAULT, scratch=None, changed=None):
+def fill_holes_label(labels, classes, value, n_classes, impl=IMPL_DEFAULT, scratch=None, changed=None, connectivity=6):
     """the holes of the voxels of the listed classes: a hole voxel that reads 0 becomes value; one that holds an unlisted class is
-    left alone"""
+    left alone.  connectivity: the background's, 6, 18 or 26"""
+    CN.check(connectivity, "morph.fill_holes_label")
     lab = _label_map(labels, "fill_holes_label", (torch.uint16,))
     v = _value(value, "fill_holes_label")
     scratch, _ = _scratch(scratch, lab.shape, lab.device)
     m = pack(lab, n_classes, classes, scratch=scratch)
-    fill_holes(m, impl, scratch, out=m)
+    fill_holes(m, impl, scratch, out=m, connectivity=connectivity)
     return apply(lab, m, v, SET, changed)
 
 
 def check_ops(ops, n_classes):
     """The ops of `run`, validated on the host: ("dilate" | "erode" | "open" | "close", value, connectivity, iterations) and
-    ("fill_holes", classes, value).  Returns them as a list of tuples; a bad op raises UNetError naming it."""
+    ("fill_holes", classes, value) or ("fill_holes", classes, value, connectivity), the background's connectivity (6 without it).
+    Returns them as a list of tuples, a fill_holes op with as many elements as it came with; a bad op raises UNetError naming it."""
     nc = int(n_classes)
     if nc < 2 or nc > 65536:
         raise UNetError("morphology: n_classes must be in [2, 65536], got %d" % nc)
@@ -296,9 +303,9 @@ def check_ops(ops, n_classes):
                 raise bad("iterations must be an integer in [0, %d]" % MAX_ITERATIONS)
             checked.append((name, value, c, n))
         elif name == "fill_holes":
-            if len(op) != 3:
-                raise bad("fill_holes takes (classes, value)")
-            classes, value = op[1:]
+            if len(op) not in (3, 4):
+                raise bad("fill_holes takes (classes, value) or (classes, value, connectivity)")
+            classes, value = op[1:3]
             if isinstance(classes, (str, bytes)) or not hasattr(classes, "__iter__"):
                 raise bad("classes must be a list")
             classes = list(classes)
@@ -307,7 +314,9 @@ def check_ops(ops, n_classes):
                     raise bad("class %r is not an integer in [1, %d]" % (v, nc - 1))
             if not integer(value) or not 1 <= value < nc:
                 raise bad("value must be an integer in [1, %d]" % (nc - 1))
-            checked.append((name, classes, value))
+            if len(op) == 4 and (not integer(op[3]) or op[3] not in CONNECTIVITIES):
+                raise bad("connectivity must be 6, 18 or 26")
+            checked.append((name, classes, value) + tuple(op[3:]))
         else:
             raise bad("unknown op (one of %s, fill_holes)" % ", ".join(STEP_OPS))
     return checked
@@ -323,7 +332,8 @@ def run(labels, ops, n_classes, scratch=None):
         scratch, _ = _scratch(scratch, lab.shape, lab.device)
     for i, op in enumerate(ops):
         if op[0] == "fill_holes":
-            fill_holes_label(lab, op[1], op[2], n_classes, scratch=scratch, changed=changed[i:i + 1])
+            fill_holes_label(lab, op[1], op[2], n_classes, scratch=scratch, changed=changed[i:i + 1],
+                             connectivity=op[3] if len(op) == 4 else 6)
         else:
             _label_op(op[0], lab, op[1], op[2], op[3], 0, IMPL_DEFAULT, scratch, changed[i:i + 1])
     return changed

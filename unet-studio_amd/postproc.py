@@ -173,7 +173,7 @@ def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
 
 
 def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
-                 component_scratch=None, tiles=None, morphology=None, morphology_scratch=None):
+                 component_scratch=None, tiles=None, morphology=None, morphology_scratch=None, single_component_connectivity=6):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
     scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
@@ -182,8 +182,8 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     it reads (space.postproc_native), the other commands run unchanged on the native planes, and the scratch is the native grid's.
     check_chain lets no command read the logits outside a fused group, so they are never stored on the native grid.
     single_component: a list of classes (a model's single_component_label, components.py): after the chain every listed class of
-    the `label` output keeps its largest 6-connected component, on the grid the chain ran on; fg_prob and label_prob are not
-    touched.  None or an empty list, or a chain whose wanted outputs hold no label, make no extra call.  component_scratch: a
+    the `label` output keeps its largest connected component, on the grid the chain ran on; fg_prob and label_prob are not
+    touched.  single_component_connectivity: 6, 18 or 26, what joins the voxels of a component (connectivity.py).  None or an empty list, or a chain whose wanted outputs hold no label, make no extra call.  component_scratch: a
     uint8 device tensor of components.components_scratch_bytes(voxels, C) bytes to reuse.
     tiles: (stack, plan, (D, H, W)) in place of logits (pass None): the volume is the blend of a stack of tile logits (tiles.py,
     include/unet_tiles.h).  A fused group that starts the chain blends the logits it reads and never stores them
@@ -195,6 +195,8 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     check_chain(steps)
     outputs = tuple(outputs)
     check_outputs(steps, outputs)
+    from . import connectivity as CN
+    CN.check(single_component_connectivity, "single_component")   # refused before any device work
     if tiles is not None:
         from . import space as SP
         from . import tiles as TL
@@ -290,7 +292,7 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
         i += 1
     if listed and "label" in outputs:
         from . import components as CMP
-        CMP.keep_largest(res["label"], listed, out_c, scratch=component_scratch)
+        CMP.keep_largest(res["label"], listed, out_c, scratch=component_scratch, connectivity=single_component_connectivity)
     if morphology and "label" in outputs:
         MO.run(res["label"], morphology, out_c, scratch=morphology_scratch)
     return {k: v for k, v in res.items() if k in outputs}

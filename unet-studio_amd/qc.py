@@ -348,13 +348,19 @@ def format_lesion_report(out_count, rows):
     return "\n".join(lines) + "\n"
 
 
-def lesion_qc(model, model_path, cases, labels=None, rule="any", threshold=0.0, min_voxels=1):
+def lesion_qc(model, model_path, cases, labels=None, rule="any", threshold=0.0, min_voxels=1, connectivity=6):
     """Per case and class 1..out_count-1, the lesion-wise detection scores (instances.py, include/unet_instances.h) of the argmax of
-    the model's output against the label: the 6-connected instances of both maps with at least min_voxels voxels, a reference
+    the model's output against the label: the `connectivity`-connected (6, 18 or 26) instances of both maps with at least min_voxels voxels, a reference
     instance detected and a predicted one true when a pair of one class overlaps (rule "any") or reaches the IoU `threshold` (rule
     "iou").  Written to `<model stem>.lesion_report.tsv` beside the model -> (0, report path) or (1, message).  labels: the classes
-    to score (None: all; the others count nothing and read nan).  A case that label_plan marks as shifted gets N/A in every column."""
+    to score (None: all; the others count nothing and read nan).  A case that label_plan marks as shifted gets N/A in every column.
+    The report's format does not depend on the connectivity; a bad one gives (1, message)."""
+    from . import connectivity as CN
     from . import instances as IN
+    try:
+        CN.check(connectivity, "lesion_qc")
+    except UNetError as e:
+        return 1, str(e)
     cases = list(cases)
     if not cases:
         return 1, "no image/label pairs found"
@@ -381,7 +387,7 @@ def lesion_qc(model, model_path, cases, labels=None, rule="any", threshold=0.0, 
                 got = torch.argmax(logits[0], dim=0).to(torch.int32).to(torch.uint16).contiguous()
                 want = torch.trunc(_to_device(label, dev)).clamp_(0, 65535).to(torch.int32).to(torch.uint16).view(D, H, W).contiguous()
                 scores = IN.lesion_scores(got, want, model.out_count, classes=labels, rule=rule, threshold=threshold,
-                                          min_voxels=min_voxels, scratch=scratch)
+                                          min_voxels=min_voxels, scratch=scratch, connectivity=connectivity)
             rows.append((case[0], case[1], scores))
     except UNetError as e:
         return 1, str(e)
