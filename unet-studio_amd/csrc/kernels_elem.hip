@@ -1054,7 +1054,9 @@ __global__ void __launch_bounds__(256) k_loss_grad(const float* __restrict__ log
     }
 }
 // four consecutive voxels per thread (see k_loss_partial_v4): 16-B loads and stores per class plane, the per-class dice terms
-// computed once per thread; per voxel the same expressions in the same order as k_loss_grad (bit-identical gradients)
+// computed once per thread; per voxel the same expressions in the same order as k_loss_grad: bit-identical gradients from the same
+// level sums (tests/test_gpu_loss_step.py).  The sums themselves are added in another order by k_loss_partial_v4 than by
+// k_loss_partial_reg, so a level that falls back to both generic kernels may see the dice part move in its last bits.
 template <int OCMAX>
 __global__ void __launch_bounds__(256) k_loss_grad_v4(const float* __restrict__ logits, const int64_t* __restrict__ target, int C, int64_t S,
                                                       const float* __restrict__ level_out, float weight, int cost_mask,
