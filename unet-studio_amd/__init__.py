@@ -12,6 +12,7 @@ from . import space  # noqa: F401  (the module: space.EXPORTS the symbols of inc
 from .space import NativeVolume, model_to_image_map, to_model_space  # noqa: F401
 from . import tiles  # noqa: F401  (the module: tiles.EXPORTS the symbols of include/unet_tiles.h)
 from .tiles import canvas_dims, plan_tiles  # noqa: F401
+from . import mirror  # noqa: F401  (the module: mirror.EXPORTS the symbols of include/unet_mirror.h)
 from .evaluate import EvaluateUNet  # noqa: F401
 from .augment import AugmentedVolumes, PrefetchedVolumes, visual_perception_augmentation  # noqa: F401
 from . import nz  # noqa: F401

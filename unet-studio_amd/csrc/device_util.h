@@ -169,6 +169,70 @@ __device__ __forceinline__ void pp_acc(float x, float& m, float& s, float& sf, f
     }
 }
 
+template <int VEC> __device__ __forceinline__ void ldv(const float* __restrict__ p, int64_t i, float (&x)[VEC]) {
+    if constexpr (VEC == 4) {
+        const float4 q = *(const float4*)(p + i);
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+    } else {
+        x[0] = p[i];
+    }
+}
+template <int VEC> __device__ __forceinline__ void stv(float* __restrict__ p, int64_t i, const float (&x)[VEC]) {
+    if constexpr (VEC == 4) *(float4*)(p + i) = make_float4(x[0], x[1], x[2], x[3]);
+    else p[i] = x[0];
+}
+
+// The softmax / create_mask / argmax of VEC consecutive voxels from v (include/unet_postproc.h), the body of k_pp_softmax
+// (kernels_postproc.hip) and of the passes that form each logit on the fly (kernels_mirror.hip).  first(c, x) yields channel c's
+// logits, called once per channel in ascending c; again(c, x) yields the same values a second time, for label_prob only.
+template <int VEC, typename First, typename Again>
+__device__ __forceinline__ void pp_voxels(int C, int64_t S, int64_t v, float thr, float* __restrict__ lp, float* __restrict__ fg,
+                                          uint16_t* __restrict__ lab, First first, Again again) {
+    float m[VEC], s[VEC], sf[VEC], best[VEC], x[VEC];
+    int arg[VEC];
+    first(0, x);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        m[j] = -INFINITY; s[j] = 0.f; sf[j] = 0.f; best[j] = 0.f; arg[j] = 1;
+        pp_acc(x[j], m[j], s[j], sf[j], 0.f);
+    }
+#pragma unroll 4
+    for (int c = 1; c < C; ++c) {
+        first(c, x);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            pp_acc(x[j], m[j], s[j], sf[j], 1.f);
+            if (c == 1 || x[j] > best[j]) { best[j] = x[j]; arg[j] = c; }   // torch.argmax: the first index wins a tie
+        }
+    }
+    bool bad[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) bad[j] = !(fabsf(m[j]) < INFINITY) || s[j] != s[j];
+    if (fg || lab) {
+        float f[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) f[j] = bad[j] ? NAN : sf[j] / s[j];
+        if (fg) stv<VEC>(fg, v, f);
+        if (lab) {
+            uint16_t l[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) l[j] = f[j] > thr ? (uint16_t)arg[j] : (uint16_t)0;   // NaN > thr is false
+            if constexpr (VEC == 4) *(ushort4*)(lab + v) = make_ushort4(l[0], l[1], l[2], l[3]);
+            else lab[v] = l[0];
+        }
+    }
+    if (lp) {
+#pragma unroll 4
+        for (int c = 1; c < C; ++c) {
+            again(c, x);
+            float p[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) p[j] = bad[j] ? NAN : expf(x[j] - m[j]) / s[j];
+            stv<VEC>(lp, (int64_t)(c - 1) * S + v, p);
+        }
+    }
+}
+
 static inline unsigned cdiv64(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace unet

@@ -2175,6 +2175,59 @@ int unet_tiles_postproc(const float* tiles, int out_c, int tw, int th, int td, c
     });
 }
 
+// ---- test-time mirroring: the members' logits flipped back, swapped back and averaged (include/unet_mirror.h) ----
+static std::string mirror_args_error(const char* who, const void* stack, int out_c, int w, int h, int d, int n_members, const int* masks,
+                                     int swap_axis, const int* pairs, int n_pairs) {
+    const std::string e = std::string(who) + ": ";
+    if (!stack) return e + "null stack";
+    if (out_c < 2) return e + "out_c must be at least 2 (channel 0 is the background)";
+    if (out_c > 65536) return e + "more than 65535 foreground classes do not fit a uint16 label";
+    if (w <= 0 || h <= 0 || d <= 0) return e + "volume dimensions (w, h, d) must be positive";
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return e + "a volume must stay below 2^31 voxels";
+    if (n_members != 1 && n_members != 2 && n_members != 4 && n_members != 8)
+        return e + "n_members must be 1, 2, 4 or 8, got " + std::to_string(n_members);
+    if (!masks) return e + "null masks";
+    if (masks[0] != 0) return e + "masks must start at 0 (member 0 is the identity)";
+    int bits = 0;
+    for (int k = 0; k < n_members; ++k) {
+        if (masks[k] < 0 || masks[k] > 7) return e + "a mask must be in [0, 7], got " + std::to_string(masks[k]);
+        if (k && masks[k] <= masks[k - 1]) return e + "masks must strictly ascend";
+        bits |= masks[k];
+    }
+    if (swap_axis < -1 || swap_axis > 2) return e + "swap_axis must be -1 (none), 0, 1 or 2, got " + std::to_string(swap_axis);
+    if (n_pairs < 0 || n_pairs > UNET_MIRROR_MAX_PAIRS)
+        return e + "n_pairs must be in [0, " + std::to_string(UNET_MIRROR_MAX_PAIRS) + "], got " + std::to_string(n_pairs);
+    if (n_pairs && !pairs) return e + "null pairs";
+    if (n_pairs && swap_axis < 0) return e + "pairs given without a swap_axis";
+    if (swap_axis >= 0 && !((bits >> swap_axis) & 1)) return e + "swap_axis " + "xyz"[swap_axis] + " is not mirrored by any member";
+    for (int i = 0; i < 2 * n_pairs; ++i) {
+        if (pairs[i] < 0 || pairs[i] >= out_c) return e + "pairs: class " + std::to_string(pairs[i]) + " is not in [0, out_c)";
+        for (int j = 0; j < i; ++j)
+            if (pairs[j] == pairs[i]) return e + "pairs: class " + std::to_string(pairs[i]) + " appears twice (the pairs must be disjoint, a != b)";
+    }
+    return std::string();
+}
+int unet_mirror_combine(const float* stack, int out_c, int w, int h, int d, int n_members, const int* masks, int swap_axis,
+                        const int* pairs, int n_pairs, float* mean, uint8_t* agreement, void* stream) {
+    const std::string e = mirror_args_error("unet_mirror_combine", stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs);
+    if (!e.empty()) return fail(e);
+    if (!mean && !agreement) return fail("unet_mirror_combine: no output wanted");
+    return pp_run(stack, stream, [&](hipStream_t s) {
+        launch_mirror_combine(stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs, mean, agreement, s);
+    });
+}
+int unet_mirror_postproc(const float* stack, int out_c, int w, int h, int d, int n_members, const int* masks, int swap_axis,
+                         const int* pairs, int n_pairs, float threshold, float* label_prob, float* fg_prob, uint16_t* label,
+                         uint8_t* agreement, void* stream) {
+    const std::string e = mirror_args_error("unet_mirror_postproc", stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs);
+    if (!e.empty()) return fail(e);
+    if (!label_prob && !fg_prob && !label && !agreement) return fail("unet_mirror_postproc: no output wanted");
+    return pp_run(stack, stream, [&](hipStream_t s) {
+        launch_mirror_postproc(stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs, threshold, label_prob, fg_prob, label,
+                               agreement, s);
+    });
+}
+
 // ---- the pre-processing commands of a model (include/unet_preproc.h) ----
 static const char* preproc_volume_error(const void* src, const void* dst, int w, int h, int d, int channels) {
     if (!src || !dst) return "unet_preproc: null device pointer";

@@ -20,6 +20,7 @@
 #include "../../include/unet_register.h"
 #include "../../include/unet_space.h"
 #include "../../include/unet_table.h"
+#include "../../include/unet_mirror.h"
 #include "../../include/unet_tiles.h"
 
 namespace unet {
@@ -380,6 +381,14 @@ void launch_tiles_blend(const float* tiles, int C, int tw, int th, int td, const
                         hipStream_t s);
 void launch_tiles_postproc(const float* tiles, int C, int tw, int th, int td, const UnetTilePlan& plan, int cw, int ch, int cd, float thr,
                            float* lp, float* fg, uint16_t* lab, hipStream_t s);
+
+// kernels_mirror.hip: the combine of mirrored members' logits, alone and inside the fused pass (include/unet_mirror.h); the arguments
+// are checked by the caller (n_members 1, 2, 4 or 8; masks and pairs in host memory)
+void launch_mirror_combine(const float* stack, int C, int W, int H, int D, int n_members, const int* masks, int swap_axis, const int* pairs,
+                           int n_pairs, float* mean, uint8_t* agreement, hipStream_t s);
+void launch_mirror_postproc(const float* stack, int C, int W, int H, int D, int n_members, const int* masks, int swap_axis,
+                            const int* pairs, int n_pairs, float thr, float* lp, float* fg, uint16_t* lab, uint8_t* agreement,
+                            hipStream_t s);
 
 // kernels_preproc.hip: the pre-processing commands of a model (include/unet_preproc.h); w, h, d are the source's dimensions
 int64_t preproc_filter_blocks(int w, int h, int d, int channels);

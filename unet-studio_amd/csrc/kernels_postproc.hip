@@ -48,68 +48,14 @@ int pp_blocks(int64_t n, int per_block) {
 }
 
 // ---- softmax / create_mask / argmax --------------------------------------------------------------------------------------------
-template <int VEC> __device__ __forceinline__ void ldv(const float* __restrict__ p, int64_t i, float (&x)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 q = *(const float4*)(p + i);
-        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-    } else {
-        x[0] = p[i];
-    }
-}
-template <int VEC> __device__ __forceinline__ void stv(float* __restrict__ p, int64_t i, const float (&x)[VEC]) {
-    if constexpr (VEC == 4) *(float4*)(p + i) = make_float4(x[0], x[1], x[2], x[3]);
-    else p[i] = x[0];
-}
-
-// pp_acc, the per-voxel online softmax state: device_util.h (shared with kernels_space.hip)
+// ldv, stv, pp_acc and pp_voxels, the per-voxel body: device_util.h (shared with kernels_space.hip and kernels_mirror.hip)
 template <int VEC>
 __global__ void __launch_bounds__(PP_T) k_pp_softmax(const float* __restrict__ lg, int C, int64_t S, float thr,
                                                      float* __restrict__ lp, float* __restrict__ fg, uint16_t* __restrict__ lab) {
     const int64_t step = (int64_t)gridDim.x * PP_T * VEC;
     for (int64_t v = ((int64_t)blockIdx.x * PP_T + threadIdx.x) * VEC; v < S; v += step) {   // VEC == 4 only when S % 4 == 0
-        float m[VEC], s[VEC], sf[VEC], best[VEC], x[VEC];
-        int arg[VEC];
-        ldv<VEC>(lg, v, x);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            m[j] = -INFINITY; s[j] = 0.f; sf[j] = 0.f; best[j] = 0.f; arg[j] = 1;
-            pp_acc(x[j], m[j], s[j], sf[j], 0.f);
-        }
-#pragma unroll 4
-        for (int c = 1; c < C; ++c) {
-            ldv<VEC>(lg, (int64_t)c * S + v, x);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                pp_acc(x[j], m[j], s[j], sf[j], 1.f);
-                if (c == 1 || x[j] > best[j]) { best[j] = x[j]; arg[j] = c; }   // torch.argmax: the first index wins a tie
-            }
-        }
-        bool bad[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) bad[j] = !(fabsf(m[j]) < INFINITY) || s[j] != s[j];
-        if (fg || lab) {
-            float f[VEC];
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) f[j] = bad[j] ? NAN : sf[j] / s[j];
-            if (fg) stv<VEC>(fg, v, f);
-            if (lab) {
-                uint16_t l[VEC];
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) l[j] = f[j] > thr ? (uint16_t)arg[j] : (uint16_t)0;   // NaN > thr is false
-                if constexpr (VEC == 4) *(ushort4*)(lab + v) = make_ushort4(l[0], l[1], l[2], l[3]);
-                else lab[v] = l[0];
-            }
-        }
-        if (lp) {
-#pragma unroll 4
-            for (int c = 1; c < C; ++c) {
-                ldv<VEC>(lg, (int64_t)c * S + v, x);
-                float p[VEC];
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) p[j] = bad[j] ? NAN : expf(x[j] - m[j]) / s[j];
-                stv<VEC>(lp, (int64_t)(c - 1) * S + v, p);
-            }
-        }
+        const auto load = [&](int c, float (&x)[VEC]) { ldv<VEC>(lg, (int64_t)c * S + v, x); };
+        pp_voxels<VEC>(C, S, v, thr, lp, fg, lab, load, load);
     }
 }
 

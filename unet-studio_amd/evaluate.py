@@ -53,13 +53,26 @@ dict: table int64 {n_regions + 1, 10} (table.py's columns), volume_mm3 float64, 
 2 * agree / (subject foreground + sampled template foreground) from one register.joint_hist at the map found, so that a failed
 registration is visible.  The label is produced for the stage whether or not it is among the wanted outputs and copied back only
 when it is.  parcellate synchronises with the host twice per buffer (the map, then its reports): the copy of the previous
-buffer's results still runs under the forward, but the host does not run ahead of this stage.  Without `atlas` nothing changes."""
+buffer's results still runs under the forward, but the host does not run ahead of this stage.  Without `atlas` nothing changes.
+
+With `mirror_axes` (a string of the letters x, y, z; None and "" are the paths above with no extra launch) every window is run
+under each combination of flips of those axes, K = 2^|axes| forwards on inputs flipped on the device, and the members' logits are
+flipped back and averaged before softmax / argmax (mirror.py, include/unet_mirror.h; the definitions are this project's).  The axes
+are the MODEL GRID's, i.e. after `orientation`.  `mirror_swap` = (axis letter, [(a, b), ...]), in the same frame, names the channel
+pairs a model with lateralised classes exchanges under a flip of that axis (left / right hippocampus): those members' channels are
+swapped back as well as their voxels.  A plain array with a chain does not store the mean logits: the chain's leading softmax /
+create_mask / argmax group combines the logits it reads, and `outputs` may then also name "agreement", uint8 (D, H, W): how many
+of the K members voted for the mean's top class (with it, from 4 members on, the mean is stored once: that measured faster).  A NativeVolume, a run without a chain and every tile take the mean logits
+(one gather pass) and then today's path unchanged; "agreement" is refused for a NativeVolume and under tiles.  The member stack
+costs K * out_count * voxels * 4 bytes on the device (8 members of 6 x 128^3: 403 MB), is reused across volumes, and the time is K
+forwards per window (the filter packs are reused from the second on)."""
 import numpy as np
 import torch
 
 from . import components as CMP
 from . import connectivity as CN
 from . import engine as E
+from . import mirror as MR
 from . import morph as MO
 from . import postproc as P
 from . import preproc as PRE
@@ -72,7 +85,7 @@ from . import tiles as TL
 class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
                  single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None, morphology=None,
-                 single_component_connectivity=6):
+                 single_component_connectivity=6, mirror_axes=None, mirror_swap=None):
         self.model = model
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
@@ -84,6 +97,8 @@ class EvaluateUNet:
         self.atlas = atlas                     # a register.Atlas: the outputs "atlas" and "regions" become available
         self.atlas_options = atlas_options     # register.parcellate's keywords (init, step, stages, max_iterations, ...)
         self.morphology = morphology           # a list of morph.run's ops on the label output, None / []: none
+        self.mirror_axes = mirror_axes         # letters of the model grid's axes to mirror over, None / "": no mirroring
+        self.mirror_swap = mirror_swap         # (axis letter, [(a, b), ...]): channel pairs exchanged under a flip of that axis
         self.params = params                   # the chain's parameters (postproc.parse_chain; postproc.txt in the reference GUI)
         self.outputs = tuple(outputs)
         self.device = torch.device(device) if device is not None else model.device()
@@ -121,7 +136,24 @@ class EvaluateUNet:
             chain = m.postproc if self.postproc == "model" else self.postproc
             steps = None
             staged = tuple(o for o in self.outputs if o in ("atlas", "regions"))          # the atlas stage's outputs
-            chain_outputs = tuple(o for o in self.outputs if o not in staged)
+            want_agr = "agreement" in self.outputs                                        # the mirror stage's output
+            chain_outputs = tuple(o for o in self.outputs if o not in staged and o != "agreement")
+            try:                                           # a bad mirror ends the run as a bad chain does
+                masks = MR.parse_axes(self.mirror_axes)
+                mirrored = len(masks) > 1
+                swap = None
+                if self.mirror_swap is not None:
+                    if not mirrored:
+                        raise E.UNetError("mirror_swap needs mirror_axes")
+                    swap = MR._swap(self.mirror_swap, m.out_count, masks)
+                    swap = ("xyz"[swap[0]], swap[1]) if swap[0] >= 0 else None
+                if want_agr and not mirrored:
+                    raise E.UNetError("output agreement needs mirror_axes")
+                if want_agr and not chain:
+                    raise E.UNetError("output agreement needs a postproc chain")
+            except E.UNetError as e:
+                self.error_msg, self.aborted, self.running = str(e), True, False
+                return out
             atl = self.atlas
             if atl is not None and "label" not in chain_outputs:
                 chain_outputs += ("label",)                # the stage reads it; it is copied back only when wanted
@@ -151,6 +183,10 @@ class EvaluateUNet:
                 if fov not in (None, "", "align_top", "tiles"):
                     raise E.UNetError("unknown fov_strategy %s" % (fov,))
                 tiled = fov == "tiles"
+                if tiled and want_agr:
+                    raise E.UNetError("output agreement is not available with fov_strategy tiles")
+                if want_agr and any(isinstance(io, SP.NativeVolume) for ios in out for io in ios):
+                    raise E.UNetError("output agreement is not available for a NativeVolume")
                 overlap = TL.check_overlap(self.tile_overlap) if tiled else 0.0
                 ops = MO.check_ops(self.morphology, m.out_count) if self.morphology else []
             except E.UNetError as e:
@@ -165,6 +201,14 @@ class EvaluateUNet:
             tab_scratch = None                             # the region table's scratch, reused across volumes
             packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
             mW, mH, mD = (int(v) for v in m.dim)
+            member_stack = [None]                          # the mirrored members' logits, reused across windows and volumes
+
+            def forward_mirrored(x1):
+                """x1 {1, in_count, d, h, w} on the device -> the stack {K, out_count, d, h, w} of the members' level-0 logits"""
+                need = MR.stack_bytes(masks, m.out_count, x1[0, 0].numel()) // 4
+                if member_stack[0] is None or member_stack[0].numel() < need:
+                    member_stack[0] = torch.empty(need, dtype=torch.float32, device=self.device)
+                return MR.forward_members(m, x1[0], masks, packed_sizes, out=member_stack[0])
 
             def forward_tiles(xc, plan):
                 """xc {in_count, cd, ch, cw} on the device -> the stack {tiles, out_count, D, H, W} of level-0 logits, one forward
@@ -174,6 +218,9 @@ class EvaluateUNet:
                 for t, (ox, oy, oz) in enumerate(origins):
                     crop = xc[:, oz:oz + mD, oy:oy + mH, ox:ox + mW].contiguous().unsqueeze(0)
                     size = tuple(crop.shape[2:])
+                    if mirrored:                           # the members' mean, straight into the tile's slot
+                        MR.combine(forward_mirrored(crop), masks, swap, out={"mean": stack[t]})
+                        continue
                     stack[t].copy_(m.forward(crop, packs_current=size in packed_sizes)[0].view(m.out_count, mD, mH, mW))
                     packed_sizes.add(size)
                 return stack
@@ -250,18 +297,25 @@ class EvaluateUNet:
                             back = SP.invert_map(fwd)                                    # native voxel -> model position
                             x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
                             x = SP.to_model_space(m, x, nv.voxel_size, map=fwd)[0].unsqueeze(0)
-                        stack = None
+                        stack = members = None
                         if plan is not None:                                             # one forward per tile (evaluate.cpp:223-230)
                             size = canvas[::-1]
                             stack = forward_tiles(x, plan)
                             if nv is not None or steps is None:                          # the canvas logits, as if the model's grid were the canvas
                                 result, stack = TL.blend(stack, plan, size), None
+                        elif mirrored:                                                   # one forward per member
+                            size = tuple(x.shape[2:])
+                            members = forward_mirrored(x)
+                            if nv is None and steps is not None:                         # the chain combines what it reads
+                                result = None
+                            else:                                                        # the mean logits, then today's path
+                                result, members = MR.combine(members, masks, swap)[0], None
                         else:
                             size = tuple(x.shape[2:])
                             result = m.forward(x, packs_current=size in packed_sizes)[0]     # evaluate.cpp:226-227
                             packed_sizes.add(size)
                         if steps is not None:                                            # evaluate.cpp:274, on the compute stream
-                            voxels = d * io.shape[1] * io.shape[2] if nv is not None or plan is not None else result.numel() // m.out_count
+                            voxels = d * io.shape[1] * io.shape[2] if nv is not None or plan is not None or result is None else result.numel() // m.out_count
                             if P.needs_scratch(steps):
                                 need = P.postproc_scratch_bytes(m.out_count, voxels)
                                 if scratch is None or scratch.numel() < need:
@@ -274,7 +328,9 @@ class EvaluateUNet:
                                 need = MO.morph_scratch_bytes((d, io.shape[1], io.shape[2]))
                                 if morph_scratch is None or morph_scratch.numel() < need:
                                     morph_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            results = P.run_postproc(result if stack is None else None, steps, outputs=chain_outputs, scratch=scratch,
+                            results = P.run_postproc(result if stack is None else None, steps,
+                                                     outputs=chain_outputs + (("agreement",) if want_agr else ()), scratch=scratch,
+                                                     mirror=None if members is None else (members, masks, swap),
                                                      native=None if nv is None else (back, native),
                                                      tiles=None if stack is None else (stack, plan, size),
                                                      single_component=listed or None, component_scratch=cmp_scratch,
@@ -297,7 +353,7 @@ class EvaluateUNet:
                                                                             [np.concatenate(report["map"])]).view(torch.int32)
                                     extra = dict(report=report, voxel_size=tuple(float(v) for v in vs))
                             results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2])
-                                           if k in P.OUTPUTS or k == "atlas" else tuple(v.shape))
+                                           if k in P.OUTPUTS or k in ("atlas", "agreement") else tuple(v.shape))
                                        for k, v in results.items() if k in self.outputs or k == "tissue_hist"}
                         else:
                             extra = {}

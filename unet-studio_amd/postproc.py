@@ -54,6 +54,7 @@ COMMANDS = {
 OUTPUTS = ("label_prob", "fg_prob", "label")
 MUTATORS = ("defragment", "defragment_each") + tuple(PLANE_OPS)   # commands that change label_prob / fg_prob / label in place
 PRODUCER = {"label_prob": "softmax", "fg_prob": "create_mask", "label": "argmax"}
+MIRROR_PAIR_FROM = 4   # run_postproc(mirror=) with agreement wanted: members from which combine + softmax replaces the fused pass
 
 
 def parse_chain(text, params=None):
@@ -173,7 +174,8 @@ def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
 
 
 def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
-                 component_scratch=None, tiles=None, morphology=None, morphology_scratch=None, single_component_connectivity=6):
+                 component_scratch=None, tiles=None, morphology=None, morphology_scratch=None, single_component_connectivity=6,
+                 mirror=None):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
     scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
@@ -190,13 +192,24 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     (tiles.postproc_tiles); a later group reads the blended canvas logits, made once when first needed.  Not with native.
     morphology: a list of morph.run's ops, run in place on the `label` output after single_component, on the grid the chain ran on;
     fg_prob and label_prob are not touched.  None or an empty list, or a chain whose wanted outputs hold no label, make no extra
-    call.  morphology_scratch: a uint8 device tensor of morph.morph_scratch_bytes((D, H, W)) bytes to reuse."""
+    call.  morphology_scratch: a uint8 device tensor of morph.morph_scratch_bytes((D, H, W)) bytes to reuse.
+    mirror: (stack, masks, swap) in place of logits (pass None): the volume's logits are the combine of a stack of mirrored members'
+    logits (mirror.py, include/unet_mirror.h).  A fused group that starts the chain combines the logits it reads and never stores
+    them (mirror.postproc_mirror), except when agreement is wanted from MIRROR_PAIR_FROM members on, where the stored mean measured
+    faster; a later group reads the mean logits, made once when first needed.  Not with tiles or native.
+    Only with mirror may `outputs` name "agreement", the uint8 {D, H, W} map of how many members voted for the mean's top class."""
     steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
     check_chain(steps)
     outputs = tuple(outputs)
+    want_agr = "agreement" in outputs                  # not a chain output (OUTPUTS): the mirror call produces it
+    if want_agr and mirror is None:
+        raise UNetError("output agreement needs mirror")
+    outputs = tuple(o for o in outputs if o != "agreement")
     check_outputs(steps, outputs)
     from . import connectivity as CN
     CN.check(single_component_connectivity, "single_component")   # refused before any device work
+    if tiles is not None and mirror is not None:
+        raise UNetError("run_postproc: mirror does not combine with tiles or native")
     if tiles is not None:
         from . import space as SP
         from . import tiles as TL
@@ -206,6 +219,15 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
         D, H, W = canvas_shape = SP._shape3(canvas_shape, "canvas shape")
         out_c = TL._stack(stack, TL._plan_struct(plan))[0]
         dev = stack.device
+    elif mirror is not None:
+        from . import mirror as MR
+        if logits is not None or native is not None:
+            raise UNetError("run_postproc: mirror comes in place of logits and does not combine with tiles or native")
+        mstack, masks, swap = mirror
+        masks = MR._masks(masks)
+        out_c, D, H, W = MR._stack(mstack, masks)
+        MR._swap(swap, out_c, masks)                   # a bad swap is refused before any device work
+        dev = mstack.device
     else:
         if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
             raise UNetError("run_postproc: logits must be a contiguous float32 device tensor")
@@ -266,8 +288,24 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
                     wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
                     wanted = {k: v for k, v in wanted.items() if v is not None}
                     TL.postproc_tiles(stack, plan, canvas_shape, thr, tuple(wanted), out=wanted)
+                elif mirror is not None and i == 0:
+                    wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
+                    wanted = {k: v for k, v in wanted.items() if v is not None}
+                    if want_agr and len(masks) >= MIRROR_PAIR_FROM:
+                        # the fused pass with the K + 1 running amax beside the softmax state runs at 2 waves per SIMD: from 4
+                        # members on, combine (where the agreement is free) + softmax measured faster, same bits
+                        logits, agr = MR.combine(mstack, masks, swap, True, want_agr)
+                        if want_agr:
+                            res["agreement"] = agr
+                        softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
+                    else:
+                        if want_agr:                          # the same pass counts the votes
+                            wanted["agreement"] = res["agreement"] = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
+                        MR.postproc_mirror(mstack, masks, swap, thr, tuple(wanted), out=wanted)
                 elif native is None:
-                    if logits is None:                        # a later group of a tiled volume: the canvas logits, made once
+                    if logits is None and mirror is not None:   # a later group of a mirrored volume: the mean logits, made once
+                        logits = MR.combine(mstack, masks, swap)[0]
+                    elif logits is None:                      # a later group of a tiled volume: the canvas logits, made once
                         logits = TL.blend(stack, plan, canvas_shape)
                     softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
                 else:
@@ -290,6 +328,10 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
             param = next(iter(p.values())) if p else 0.0
             plane_op_call(PLANE_OPS[name], param, (W, H, D), lp, out_c - 1, get_scratch())
         i += 1
+    if want_agr and "agreement" not in res:            # no fused group at the head of the chain wrote it
+        res["agreement"] = MR.combine(mstack, masks, swap, want_mean=False, want_agreement=True)[1]
+    if want_agr:
+        outputs += ("agreement",)
     if listed and "label" in outputs:
         from . import components as CMP
         CMP.keep_largest(res["label"], listed, out_c, scratch=component_scratch, connectivity=single_component_connectivity)
