@@ -454,3 +454,32 @@ def test_evaluate_with_a_longer_chain_and_params():
     exp, _ = restate_chain(torch.from_numpy(raw).view(4, 16, 24, 32).to(DEV), chain, params)
     assert np.array_equal(got["label"], exp["label"]) and np.array_equal(got["fg_prob"], exp["fg_prob"])
     assert np.array_equal(got["label_prob"], exp["label_prob"].reshape(3 * 16, 24, 32))
+
+
+def test_evaluate_state_carried_across_volumes():
+    """One start() over entries of different sizes (a plain array, a NativeVolume on a smaller and one on a larger grid, the
+    first array again) with a chain that needs scratch, single_component, morphology and mirroring: the scratch buffers, the
+    filter-pack bookkeeping, the member stack and the result in flight carry nothing from one entry into the next, so every
+    output equals, bit for bit, that of a fresh EvaluateUNet run on the entry alone."""
+    m = U.UNet3d(1, 4, SMOKE_ARCH % 4, device=DEV, dtype="fp32", seed=2)
+    m.dim, m.voxel_size = (16, 16, 16), (1.0, 1.0, 1.0)
+    rs = np.random.RandomState(11)
+    plain = rs.rand(16, 16, 16).astype(np.float32)
+    small = U.NativeVolume(rs.rand(10, 14, 12).astype(np.float32), (1.3, 1.1, 1.4))
+    large = U.NativeVolume(rs.rand(20, 18, 22).astype(np.float32), (0.8, 0.9, 0.75))
+    kw = dict(postproc="softmax+create_mask+defragment+argmax", params={"defragment": (0.55, 0.5), "argmax": 0.0},
+              outputs=("label", "fg_prob", "label_prob"), single_component=[1, 2], single_component_connectivity=18,
+              morphology=[("close", 2, 26, 1)], mirror_axes="x")
+    ev = U.EvaluateUNet(m, **kw)
+    got = ev.start([[plain, small], [large, plain.copy()]])
+    assert not ev.aborted and ev.error_msg == "" and ev.cur_prog == 2
+    got = got[0] + got[1]
+    for g, io in zip(got, (plain, small, large, plain)):
+        alone = U.EvaluateUNet(m, **kw)
+        exp = alone.start([[io]])[0][0]
+        assert not alone.aborted, alone.error_msg
+        shape = io.data.shape if isinstance(io, U.NativeVolume) else io.shape
+        assert sorted(g) == sorted(exp) == sorted(kw["outputs"]) and g["label"].shape == shape
+        for k in exp:
+            assert g[k].dtype == exp[k].dtype and np.array_equal(g[k], exp[k]), k
+    assert all(np.array_equal(got[3][k], got[0][k]) for k in got[0])

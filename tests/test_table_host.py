@@ -263,3 +263,30 @@ def test_evaluate_refuses_before_any_forward(monkeypatch):
     # without an atlas the names are unknown outputs of a chain's, as before
     ev = U.EvaluateUNet(m, device="cpu", postproc="model", outputs=("label",))
     assert ev.atlas is None and ev.atlas_options is None
+
+
+@pytest.mark.parametrize("kw,wins", [
+    (dict(mirror_axes="q", outputs=("atlas",)), "mirror_axes: unknown axis 'q'"),
+    (dict(mirror_swap=("x", [(1, 2)]), outputs=("atlas",)), "mirror_swap needs mirror_axes"),
+    (dict(outputs=("label", "agreement"), fov_strategy="spiral"), "output agreement needs mirror_axes"),
+    (dict(outputs=("atlas",), postproc="bogusA"), "output atlas needs an atlas"),
+    (dict(postproc="bogusA", fov_strategy="spiral"), "unknown command bogusA"),
+    (dict(postproc="model", preproc="bogusB", single_component_connectivity=7), "unknown command bogusB"),
+    (dict(postproc="model", orientation="bogusC", single_component=[9]), "unknown command bogusC"),
+    (dict(postproc="model", single_component=[9], single_component_connectivity=7), "single_component: class 9 is not in [1, 2]"),
+    (dict(postproc="model", single_component_connectivity=7, fov_strategy="spiral"),
+     "single_component: connectivity must be 6, 18 or 26, got 7"),
+    (dict(postproc="model", fov_strategy="spiral", morphology=[("bogus",)]), "unknown fov_strategy spiral"),
+    (dict(postproc="model", fov_strategy="tiles", tile_overlap=0.7, morphology=[("bogus",)]),
+     "tiles: tile_overlap must be in [0, 0.5), got 0.7"),
+    (dict(postproc="model", fov_strategy="tiles", mirror_axes="x", outputs=("label", "agreement"), tile_overlap=0.7),
+     "output agreement is not available with fov_strategy tiles"),
+])
+def test_evaluate_refusal_precedence(monkeypatch, kw, wins):
+    """two wrong arguments at once: the refusal that comes first in start()'s order of checks is the one reported"""
+    monkeypatch.setattr(torch.cuda, "Stream", lambda *a, **k: None)     # start() makes its copy stream first
+    marker = np.zeros((16, 16, 16), np.float32)
+    ev = U.EvaluateUNet(FakeModel(), device="cpu", **kw)
+    out = ev.start([[marker]])
+    assert ev.aborted and not ev.running and out[0][0] is marker
+    assert ev.error_msg.startswith(wins), ev.error_msg

@@ -50,16 +50,6 @@ def _maps(tissue, atlas, who):
     return tissue.element_size()
 
 
-def _scratch(scratch, need, device):
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=device)
-    return scratch, scratch.numel() * scratch.element_size()
-
-
-def _stream(stream, t):
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _reports(out, spec, dev, who):
     """the report tensors: the caller's (`out`, a dict that must hold every one, of the right size) or new ones"""
     if out is None:
@@ -84,10 +74,10 @@ def reclassify(tissue, atlas, n_regions, n_tissues, flags=0, count_only=False, i
     dev = atlas.device
     out = _reports(out, dict(votes=((R + 1, T), torch.uint32), tissue_total=((T,), torch.uint32), covered=((T,), torch.uint32),
                              majority=((R + 1,), torch.uint8), erased=((R + 1,), torch.uint32)), dev, "reclassify")
-    scratch, nbytes = _scratch(scratch, need, dev)
+    scratch = E.scratch(scratch, need, dev)
     E.check(E.lib.unet_atlas_reclassify(atlas.numel(), tissue.data_ptr(), tb, atlas.data_ptr(), R, T, flags, out["votes"].data_ptr(),
                                         out["tissue_total"].data_ptr(), out["covered"].data_ptr(), out["majority"].data_ptr(),
-                                        out["erased"].data_ptr(), int(impl), scratch.data_ptr(), nbytes, _stream(stream, atlas)))
+                                        out["erased"].data_ptr(), int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(atlas, stream)))
     return out
 
 
@@ -112,11 +102,11 @@ def grow(tissue, atlas, n_tissues, grow_tissues, flags=0, max_rounds=None, smoot
     need = atlas_scratch_bytes(W * H * D, 0, T, int(max_rounds))
     dev = atlas.device
     out = _reports(out, dict(filled=((T,), torch.uint32), relabelled=((T,), torch.uint32), info=((2,), torch.uint32)), dev, "grow")
-    scratch, nbytes = _scratch(scratch, need, dev)
+    scratch = E.scratch(scratch, need, dev)
     arr = (C.c_uint8 * MAX_TISSUES)(*flagged.tolist())
     E.check(E.lib.unet_atlas_grow(W, H, D, tissue.data_ptr(), tb, atlas.data_ptr(), T, int(flags), arr, int(max_rounds), int(smooth_rounds),
                                   out["filled"].data_ptr(), out["relabelled"].data_ptr(), out["info"].data_ptr(), scratch.data_ptr(),
-                                  nbytes, _stream(stream, atlas)))
+                                  scratch.nbytes, E.stream(atlas, stream)))
     return out
 
 

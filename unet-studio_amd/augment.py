@@ -253,11 +253,9 @@ def augment(recipe, image, label, scratch=None):
     if image.numel() != s.channels * D * H * W or label.numel() != D * H * W:
         raise engine.UNetError("augment: tensor sizes do not match the recipe (%d channels of %dx%dx%d)" % (s.channels, W, H, D))
     need = scratch_bytes(s)
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=image.device)
-    st = torch.cuda.current_stream(image.device).cuda_stream
+    scratch = engine.scratch(scratch, need, image.device)
     engine.check(engine.lib.unet_augment_run(C.byref(s), image.data_ptr(), label.data_ptr(), scratch.data_ptr(),
-                                              scratch.numel() * scratch.element_size(), st))
+                                              scratch.nbytes, engine.stream(image)))
     return scratch
 
 
@@ -394,11 +392,9 @@ def simulate(recipe, t1w, label=None, scratch=None):
         raise engine.UNetError("simulate: the recipe needs a float32 device label volume of the same size")
     need = C.c_size_t()
     engine.check(engine.lib.unet_simulate_modality_scratch_bytes(C.byref(s), C.byref(need)))
-    if scratch is None or scratch.numel() * scratch.element_size() < need.value:
-        scratch = torch.empty(need.value, dtype=torch.uint8, device=t1w.device)
-    st = torch.cuda.current_stream(t1w.device).cuda_stream
+    scratch = engine.scratch(scratch, need.value, t1w.device)
     engine.check(engine.lib.unet_simulate_modality_run(C.byref(s), t1w.data_ptr(), label.data_ptr() if s.with_label else None,
-                                                       scratch.data_ptr(), scratch.numel() * scratch.element_size(), st))
+                                                       scratch.data_ptr(), scratch.nbytes, engine.stream(t1w)))
     return scratch
 
 

@@ -8,7 +8,6 @@ faces, IMPL_GLOBAL hooks every voxel in global memory (the measured baseline and
 keep_largest(connectivity=18 | 26) goes through connectivity.py (include/unet_connectivity.h)."""
 import ctypes as C
 
-import torch
 
 from . import connectivity as CN
 from . import engine as E
@@ -58,23 +57,10 @@ def keep_largest(label, classes, n_classes, removed=None, scratch=None, impl=IMP
     size and impl values serve it)."""
     if CN.check(connectivity, "components.keep_largest") != 6:
         return CN.keep_largest(label, classes, n_classes, connectivity, removed=removed, scratch=scratch, impl=impl, stream=stream)
-    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.uint16 and label.is_contiguous() and label.dim() == 3):
-        raise UNetError("components: label must be a contiguous uint16 (D, H, W) device tensor")
-    D, H, W = (int(v) for v in label.shape)
-    if removed is not None and not (torch.is_tensor(removed) and removed.is_cuda and removed.device == label.device
-                                    and removed.dtype in (torch.uint32, torch.int32) and removed.is_contiguous()
-                                    and removed.numel() == int(n_classes)):
-        raise UNetError("components: removed must be a contiguous uint32 device tensor of n_classes entries on label's device")
-    classes = [int(v) for v in classes]
-    need = components_scratch_bytes(D * H * W, n_classes)        # the size checks, before any device work
-    for v in classes:
-        if not 0 <= v < 1 << 32:
-            raise UNetError("components: listed class %d is not in [1, %d]" % (v, int(n_classes) - 1))
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=label.device)
-    st = stream if stream is not None else torch.cuda.current_stream(label.device).cuda_stream
+    (D, H, W), classes, need = CN.keep_largest_args("components", label, classes, n_classes, removed, components_scratch_bytes)
+    scratch = E.scratch(scratch, need, label.device)
     arr = (C.c_uint32 * max(1, len(classes)))(*classes)
     E.check(E.lib.unet_components_keep_largest(W, H, D, label.data_ptr(), int(n_classes), arr, len(classes),
                                                removed.data_ptr() if removed is not None else None, int(impl), scratch.data_ptr(),
-                                               scratch.numel() * scratch.element_size(), st))
+                                               scratch.nbytes, E.stream(label, stream)))
     return label

@@ -73,14 +73,22 @@ def holes_scratch_bytes(shape):
     return n.value
 
 
-def _scratch(scratch, need, dev):
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    return scratch, scratch.numel() * scratch.element_size()
-
-
-def _stream(stream, t):
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+def keep_largest_args(who, label, classes, n_classes, removed, scratch_bytes):
+    """keep_largest's argument checks, here and in components.py, under the message prefix `who`: ((D, H, W), classes, the scratch
+    bytes needed)"""
+    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.uint16 and label.is_contiguous() and label.dim() == 3):
+        raise UNetError("%s: label must be a contiguous uint16 (D, H, W) device tensor" % who)
+    D, H, W = (int(v) for v in label.shape)
+    if removed is not None and not (torch.is_tensor(removed) and removed.is_cuda and removed.device == label.device
+                                    and removed.dtype in (torch.uint32, torch.int32) and removed.is_contiguous()
+                                    and removed.numel() == int(n_classes)):
+        raise UNetError("%s: removed must be a contiguous uint32 device tensor of n_classes entries on label's device" % who)
+    classes = [int(v) for v in classes]
+    need = scratch_bytes(D * H * W, n_classes)                   # the size checks, before any device work
+    for v in classes:
+        if not 0 <= v < 1 << 32:
+            raise UNetError("%s: listed class %d is not in [1, %d]" % (who, v, int(n_classes) - 1))
+    return (D, H, W), classes, need
 
 
 def keep_largest(label, classes, n_classes, connectivity=6, removed=None, scratch=None, impl=IMPL_DEFAULT, stream=None):
@@ -88,23 +96,12 @@ def keep_largest(label, classes, n_classes, connectivity=6, removed=None, scratc
     returns label.  Arguments as components.keep_largest: every listed class keeps its largest `connectivity`-connected component,
     the one holding the smallest linear index among equal counts."""
     c = check(connectivity, "connectivity.keep_largest")
-    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.uint16 and label.is_contiguous() and label.dim() == 3):
-        raise UNetError("connectivity.keep_largest: label must be a contiguous uint16 (D, H, W) device tensor")
-    D, H, W = (int(v) for v in label.shape)
-    if removed is not None and not (torch.is_tensor(removed) and removed.is_cuda and removed.device == label.device
-                                    and removed.dtype in (torch.uint32, torch.int32) and removed.is_contiguous()
-                                    and removed.numel() == int(n_classes)):
-        raise UNetError("connectivity.keep_largest: removed must be a contiguous uint32 device tensor of n_classes entries on label's device")
-    classes = [int(v) for v in classes]
-    need = keep_largest_scratch_bytes(D * H * W, n_classes)      # the size checks, before any device work
-    for v in classes:
-        if not 0 <= v < 1 << 32:
-            raise UNetError("connectivity.keep_largest: listed class %d is not in [1, %d]" % (v, int(n_classes) - 1))
-    scratch, sbytes = _scratch(scratch, need, label.device)
+    (D, H, W), classes, need = keep_largest_args("connectivity.keep_largest", label, classes, n_classes, removed, keep_largest_scratch_bytes)
+    scratch = E.scratch(scratch, need, label.device)
     arr = (C.c_uint32 * max(1, len(classes)))(*classes)
     E.check(E.lib.unet_conn_keep_largest(W, H, D, label.data_ptr(), int(n_classes), arr, len(classes),
-                                         removed.data_ptr() if removed is not None else None, c, int(impl), scratch.data_ptr(), sbytes,
-                                         _stream(stream, label)))
+                                         removed.data_ptr() if removed is not None else None, c, int(impl), scratch.data_ptr(), scratch.nbytes,
+                                         E.stream(label, stream)))
     return label
 
 
@@ -127,10 +124,10 @@ def label(labels, n_classes, classes=None, connectivity=6, max_instances=DEFAULT
     inst = INS._out(o[0], D * H * W, torch.int32, dev, "label", "inst")
     rows = INS._out(o[1], (M + 1) * COLUMNS, torch.int64, dev, "label", "rows")
     info = INS._out(o[2], 2, torch.int64, dev, "label", "info")
-    scratch, sbytes = _scratch(scratch, need, dev)
+    scratch = E.scratch(scratch, need, dev)
     arr = (C.c_uint32 * max(1, len(classes)))(*classes)
     E.check(E.lib.unet_conn_label(W, H, D, lab.data_ptr(), nc, arr, len(classes), inst.data_ptr(), rows.data_ptr(), M, info.data_ptr(), c,
-                                  int(impl), scratch.data_ptr(), sbytes, _stream(stream, lab)))
+                                  int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(lab, stream)))
     return inst.view(D, H, W), rows.view(M + 1, COLUMNS), info
 
 
@@ -141,8 +138,8 @@ def fill_holes(m, connectivity=6, impl=IMPL_DEFAULT, scratch=None, out=None):
     c = check(connectivity, "connectivity.fill_holes")
     D, H, W = MO._mask(m, "fill_holes").shape
     out = MO._out_mask(out, m, "fill_holes")
-    scratch, sbytes = _scratch(scratch, holes_scratch_bytes(m.shape), m.bits.device)
+    scratch = E.scratch(scratch, holes_scratch_bytes(m.shape), m.bits.device)
     info = torch.empty(2, dtype=torch.int64, device=m.bits.device)
-    E.check(E.lib.unet_conn_holes(W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), info.data_ptr(), c, int(impl), scratch.data_ptr(), sbytes,
-                                  _stream(None, m.bits)))
+    E.check(E.lib.unet_conn_holes(W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), info.data_ptr(), c, int(impl), scratch.data_ptr(), scratch.nbytes,
+                                  E.stream(m.bits)))
     return out, info

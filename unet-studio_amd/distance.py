@@ -101,16 +101,6 @@ def _weights(weights, who):
     return w
 
 
-def _scratch(scratch, need, dev):
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    return scratch, scratch.numel() * scratch.element_size()
-
-
-def _stream(stream, t):
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-
-
 def transform(labels, label, weights, of="surface", impl=IMPL_DEFAULT, out=None, scratch=None, stream=None):
     """unet_dist_transform on the current stream (or the raw `stream`).  labels: a (D, H, W) uint8 or uint16 device tensor.  Returns the
     int32 (D, H, W) device tensor (written into `out` when given) of the least squared distance, under weights = (wx, wy, wz), to the
@@ -129,9 +119,9 @@ def transform(labels, label, weights, of="surface", impl=IMPL_DEFAULT, out=None,
     elif not (torch.is_tensor(out) and out.is_cuda and out.device == labels.device and out.is_contiguous() and out.dtype == torch.int32
               and out.numel() == labels.numel()):
         raise UNetError("distance.transform: out must be a contiguous int32 device tensor of %d entries" % labels.numel())
-    scratch, sbytes = _scratch(scratch, need, labels.device)
+    scratch = E.scratch(scratch, need, labels.device)
     E.check(E.lib.unet_dist_transform(ptr, nbytes, w, h, d, int(label), _OF[of], wx, wy, wz, out.data_ptr(), int(impl), scratch.data_ptr(),
-                                      sbytes, _stream(stream, labels)))
+                                      scratch.nbytes, E.stream(labels, stream)))
     return out.view(d, h, w)
 
 
@@ -145,7 +135,7 @@ def surface_counts(a, b, n_labels, out=None, stream=None):
         raise UNetError("distance.surface_counts: n_labels must be in [1, 65535], got %d" % L)
     if out is None:
         out = torch.empty((L + 1) * 2, dtype=torch.int64, device=a.device)
-    E.check(E.lib.unet_dist_surface_counts(pa, ab, pb, bb, w, h, d, L, out.data_ptr(), _stream(stream, a)))
+    E.check(E.lib.unet_dist_surface_counts(pa, ab, pb, bb, w, h, d, L, out.data_ptr(), E.stream(a, stream)))
     return out.view(L + 1, 2)
 
 
@@ -170,8 +160,8 @@ def surface_distances(a, b, n_labels, weights, labels=None, impl=IMPL_DEFAULT, s
         raise UNetError("distance.surface_distances: labels must be distinct and in [1, n_labels]")
     d, h, w = (int(v) for v in a.shape)
     dev = a.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    scratch, _ = _scratch(scratch, distance_scratch_bytes((w, h, d)), dev)
+    stream = E.stream(dev)
+    scratch = E.scratch(scratch, distance_scratch_bytes((w, h, d)), dev)
     counts = surface_counts(a, b, L).cpu().numpy()                                   # the first synchronisation
     todo = sorted(l for l in labels if counts[l, 0] > 0 and counts[l, 1] > 0)
     result = {"counts": counts, "values": {}}

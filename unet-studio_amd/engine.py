@@ -126,6 +126,21 @@ def check(rc):
         raise UNetError(lib.unet_last_error().decode("utf-8", "replace"))
 
 
+def scratch(buf, need, device):
+    """buf when it holds at least `need` bytes, otherwise a new uint8 device tensor of `need` bytes"""
+    if buf is None or buf.nbytes < need:
+        buf = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+def stream(t_or_device, stream=None):
+    """the raw stream handle the C ABI takes: `stream` when given, otherwise the current stream of the tensor's device (or of the
+    device)"""
+    if stream is not None:
+        return stream
+    return torch.cuda.current_stream(t_or_device.device if torch.is_tensor(t_or_device) else t_or_device).cuda_stream
+
+
 def ptr_array(ptrs):
     """host array of device pointers (None -> NULL)"""
     arr = (C.c_void_p * max(1, len(ptrs)))()

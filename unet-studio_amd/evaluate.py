@@ -66,6 +66,8 @@ of the K members voted for the mean's top class (with it, from 4 members on, the
 (one gather pass) and then today's path unchanged; "agreement" is refused for a NativeVolume and under tiles.  The member stack
 costs K * out_count * voxels * 4 bytes on the device (8 members of 6 x 128^3: 403 MB), is reused across volumes, and the time is K
 forwards per window (the filter packs are reused from the second on)."""
+import collections
+
 import numpy as np
 import torch
 
@@ -80,6 +82,42 @@ from . import register as REG
 from . import space as SP
 from . import table as TAB
 from . import tiles as TL
+
+
+# what _check hands the loop: the parsed options of one start()
+_Checked = collections.namedtuple("_Checked", "steps chain_outputs staged masks swap pre ori ori_map listed cmp_conn tiled overlap ops atl")
+# one entry past the input stage: x on the device ({1, in_count, d, h, w}; {in_count, cd, ch, cw} with a plan), the map `back` from a
+# voxel of a NativeVolume's grid `native` (d, h, w) to the grid the forward runs on (None for a plain array), the tile plan and canvas
+# (w, h, d) when it runs in more than one tile, and `size`, the entry's own grid (d, h, w), where its results land
+_Entry = collections.namedtuple("_Entry", "x back native plan canvas size")
+
+
+class _Run:
+    """What one start() carries from volume to volume: the uint8 scratch buffers by stage (normalize's reduction, the chain's, the
+    component labelling's, the morphology's, the region table's), the volume sizes whose filter packs this run has already made
+    (the weights are frozen), and the mirrored members' logits, reused across windows and volumes."""
+
+    def __init__(self, device):
+        self.device, self.buffers, self.packed_sizes, self.member_stack = device, {}, set(), None
+
+    def scratch(self, stage, need):
+        buf = self.buffers[stage] = E.scratch(self.buffers.get(stage), need, self.device)
+        return buf
+
+
+def _land(out, pending):
+    """waits for the copies of one entry's results and puts them into out"""
+    fi, bi, hosts, ev, extra = pending
+    ev.synchronize()
+    # views of the pinned buffers the copies landed in (owned by the arrays)
+    res = {k: host.numpy().reshape(shape) for k, (host, shape) in hosts.items()}
+    if "regions" in res:                           # the host arithmetic on the table and on the histogram at the map found
+        hist = res.pop("tissue_hist").view(np.uint32)[0].astype(np.int64)
+        agree = int(np.trace(hist)) - int(hist[0, 0])
+        both = int(hist[1:].sum()) + int(hist[:, 1:].sum())
+        res["regions"] = dict(table=res["regions"], volume_mm3=TAB.volumes_mm3(res["regions"], extra["voxel_size"]),
+                              report=extra["report"], tissue_dice=np.float64(2.0 * agree / both) if both else np.float64("nan"))
+    out[fi][bi] = res[None] if None in res else res
 
 
 class EvaluateUNet:
@@ -115,276 +153,263 @@ class EvaluateUNet:
         self.model.prepare_for_inference(self.device)     # evaluate.cpp:391
         self.aborted, self.running, self.error_msg, self.cur_prog = False, True, "", 0
         out = [list(ios) for ios in model_io]
-        pending = None      # (file index, buffer index, {name: (pinned host tensor, shape)}, event): the previous result, in flight
+        pending = None      # (file index, buffer index, {name: (pinned host tensor, shape)}, event, extra): the previous result, in flight
         copy_stream = torch.cuda.Stream(self.device)
-
-        def land(p):
-            fi, bi, hosts, ev, extra = p
-            ev.synchronize()
-            # views of the pinned buffers the copies landed in (owned by the arrays)
-            res = {k: host.numpy().reshape(shape) for k, (host, shape) in hosts.items()}
-            if "regions" in res:                           # the host arithmetic on the table and on the histogram at the map found
-                hist = res.pop("tissue_hist").view(np.uint32)[0].astype(np.int64)
-                agree = int(np.trace(hist)) - int(hist[0, 0])
-                both = int(hist[1:].sum()) + int(hist[:, 1:].sum())
-                res["regions"] = dict(table=res["regions"], volume_mm3=TAB.volumes_mm3(res["regions"], extra["voxel_size"]),
-                                      report=extra["report"], tissue_dice=np.float64(2.0 * agree / both) if both else np.float64("nan"))
-            out[fi][bi] = res[None] if None in res else res
-
         try:
-            m = self.model
-            chain = m.postproc if self.postproc == "model" else self.postproc
-            steps = None
-            staged = tuple(o for o in self.outputs if o in ("atlas", "regions"))          # the atlas stage's outputs
-            want_agr = "agreement" in self.outputs                                        # the mirror stage's output
-            chain_outputs = tuple(o for o in self.outputs if o not in staged and o != "agreement")
-            try:                                           # a bad mirror ends the run as a bad chain does
-                masks = MR.parse_axes(self.mirror_axes)
-                mirrored = len(masks) > 1
-                swap = None
-                if self.mirror_swap is not None:
-                    if not mirrored:
-                        raise E.UNetError("mirror_swap needs mirror_axes")
-                    swap = MR._swap(self.mirror_swap, m.out_count, masks)
-                    swap = ("xyz"[swap[0]], swap[1]) if swap[0] >= 0 else None
-                if want_agr and not mirrored:
-                    raise E.UNetError("output agreement needs mirror_axes")
-                if want_agr and not chain:
-                    raise E.UNetError("output agreement needs a postproc chain")
+            try:                                           # a bad option ends the run as run_postproc's failure does (evaluate.cpp:274)
+                cfg = self._check(out)
             except E.UNetError as e:
                 self.error_msg, self.aborted, self.running = str(e), True, False
                 return out
-            atl = self.atlas
-            if atl is not None and "label" not in chain_outputs:
-                chain_outputs += ("label",)                # the stage reads it; it is copied back only when wanted
-            if staged and atl is None:
-                self.error_msg, self.aborted, self.running = "output %s needs an atlas" % staged[0], True, False
-                return out
-            if atl is not None and not chain:
-                self.error_msg, self.aborted, self.running = "an atlas needs a postproc chain that produces a label", True, False
-                return out
-            if chain:
-                try:                                       # a bad chain ends the run as run_postproc's failure does (evaluate.cpp:274)
-                    steps = P.parse_chain(chain, self.params)
-                    P.check_chain(steps)
-                    P.check_outputs(steps, chain_outputs)
-                    if atl is not None and not isinstance(atl, REG.Atlas):
-                        raise E.UNetError("atlas must be a register.Atlas")
-                except E.UNetError as e:
-                    self.error_msg, self.aborted, self.running = str(e), True, False
-                    return out
-            try:                                           # run_preproc / handle_orientation's failure (evaluate.cpp:201-204)
-                pre = PRE.active(PRE.parse_chain(m.preproc if self.preproc == "model" else self.preproc))
-                ori = PRE.parse_orientation(m.orientation if self.orientation == "model" else self.orientation)
-                D0, vs0, M = PRE.orientation_map(ori, m.dim, m.voxel_size) if ori else (None, None, None)
-                listed = CMP.resolve(self.single_component, m)
-                cmp_conn = CN.check(self.single_component_connectivity, "single_component")
-                fov = m.fov_strategy if self.fov_strategy == "model" else self.fov_strategy
-                if fov not in (None, "", "align_top", "tiles"):
-                    raise E.UNetError("unknown fov_strategy %s" % (fov,))
-                tiled = fov == "tiles"
-                if tiled and want_agr:
-                    raise E.UNetError("output agreement is not available with fov_strategy tiles")
-                if want_agr and any(isinstance(io, SP.NativeVolume) for ios in out for io in ios):
-                    raise E.UNetError("output agreement is not available for a NativeVolume")
-                overlap = TL.check_overlap(self.tile_overlap) if tiled else 0.0
-                ops = MO.check_ops(self.morphology, m.out_count) if self.morphology else []
-            except E.UNetError as e:
-                self.error_msg, self.aborted, self.running = str(e), True, False
-                return out
-            pre_scratch = None                             # normalize's reduction scratch, reused across volumes
-            scratch = None                                 # the chain's scratch (defragment, per-plane commands), reused across volumes
-            cmp_scratch = None                             # the component labelling's scratch, reused across volumes
-            listed = listed if steps is not None and "label" in chain_outputs else []
-            ops = ops if steps is not None and "label" in chain_outputs else []
-            morph_scratch = None                           # the morphology's scratch, reused across volumes
-            tab_scratch = None                             # the region table's scratch, reused across volumes
-            packed_sizes = set()                           # volume sizes whose filter packs this run has already made (weights are frozen)
-            mW, mH, mD = (int(v) for v in m.dim)
-            member_stack = [None]                          # the mirrored members' logits, reused across windows and volumes
-
-            def forward_mirrored(x1):
-                """x1 {1, in_count, d, h, w} on the device -> the stack {K, out_count, d, h, w} of the members' level-0 logits"""
-                need = MR.stack_bytes(masks, m.out_count, x1[0, 0].numel()) // 4
-                if member_stack[0] is None or member_stack[0].numel() < need:
-                    member_stack[0] = torch.empty(need, dtype=torch.float32, device=self.device)
-                return MR.forward_members(m, x1[0], masks, packed_sizes, out=member_stack[0])
-
-            def forward_tiles(xc, plan):
-                """xc {in_count, cd, ch, cw} on the device -> the stack {tiles, out_count, D, H, W} of level-0 logits, one forward
-                per integer crop in tile-index order"""
-                origins = TL.tile_origins(plan)
-                stack = torch.empty((len(origins), m.out_count, mD, mH, mW), dtype=torch.float32, device=self.device)
-                for t, (ox, oy, oz) in enumerate(origins):
-                    crop = xc[:, oz:oz + mD, oy:oy + mH, ox:ox + mW].contiguous().unsqueeze(0)
-                    size = tuple(crop.shape[2:])
-                    if mirrored:                           # the members' mean, straight into the tile's slot
-                        MR.combine(forward_mirrored(crop), masks, swap, out={"mean": stack[t]})
-                        continue
-                    stack[t].copy_(m.forward(crop, packs_current=size in packed_sizes)[0].view(m.out_count, mD, mH, mW))
-                    packed_sizes.add(size)
-                return stack
-
+            run = _Run(self.device)
             with torch.no_grad():                          # evaluate.cpp:221
                 while self.cur_prog < len(out) and not self.aborted:
                     self.status = "inferencing"
                     for i, io in enumerate(out[self.cur_prog]):
-                        nv = io if isinstance(io, SP.NativeVolume) else None
-                        if nv is not None:
-                            nv.check()
-                            io = nv.data
-                        elif pre or ori:
-                            raise E.UNetError("a plain model_io array is already at the model's grid: preproc / orientation need a "
-                                              "NativeVolume")
-                        io = np.ascontiguousarray(io, dtype=np.float32)
-                        if io.ndim != 3 or io.shape[0] % m.in_count:
-                            raise E.UNetError("model_io buffer must be (in_count*D, H, W), got %s" % (io.shape,))
-                        d = io.shape[0] // m.in_count
-                        plan = canvas = None                                             # set when this entry runs in more than one tile
-                        if tiled and nv is None:                                         # the array is its own canvas
-                            canvas = (io.shape[2], io.shape[1], d)
-                            if canvas[0] < mW or canvas[1] < mH or canvas[2] < mD:
-                                raise E.UNetError("fov_strategy tiles: a model_io array (w, h, d) = %s is smaller than the model's %s"
-                                                  % (canvas, (mW, mH, mD)))
-                        elif tiled:                                                      # the grid at the model's voxel size that covers the scan
-                            if nv.map is not None:
-                                raise E.UNetError("a caller's map and tiles do not combine")
-                            pdims, pvs, G = PRE.geometry(pre, (io.shape[2], io.shape[1], d), nv.voxel_size)
-                            canvas = TL.canvas_dims(m.dim, m.voxel_size, pdims, pvs, orientation=ori)
-                        if tiled and canvas != (mW, mH, mD):                             # a volume that fits takes the paths below
-                            plan = TL.plan_tiles(canvas, (mW, mH, mD), overlap)
-                        if plan is not None and nv is None:
-                            x = torch.from_numpy(io).view(m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
-                            back = None
-                        elif nv is None:
-                            x = torch.from_numpy(io).view(1, m.in_count, d, io.shape[1], io.shape[2]).to(self.device)
-                            back = None
-                        elif plan is not None:                                           # run_preproc, then ONE resample to the canvas
-                            native = (d, io.shape[1], io.shape[2])
-                            x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
-                            if pre:
-                                if PRE.needs_scratch(pre):
-                                    need = PRE.preproc_scratch_bytes(m.in_count * pdims[0] * pdims[1] * pdims[2])
-                                    if pre_scratch is None or pre_scratch.numel() < need:
-                                        pre_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                                x = PRE.run_preproc(x, pre, scratch=pre_scratch)
-                            cD0, cvs0, cM = PRE.orientation_map(ori, canvas, m.voxel_size) if ori else (canvas, m.voxel_size, None)
-                            fwd = SP.model_to_image_map(cD0, cvs0, pdims, pvs)           # canvas voxel -> preprocessed-grid position
-                            if ori:
-                                fwd = SP.compose_map(fwd, cM)
-                            back = SP.invert_map(SP.compose_map(G, fwd))                 # original native voxel -> canvas position
-                            x = SP.resample(x, canvas[::-1], fwd, "linear", normalize=True)   # one normalisation over the whole scan
-                        elif pre or ori:                                                 # evaluate.cpp:201-204, on the compute stream
-                            native = (d, io.shape[1], io.shape[2])
-                            x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
-                            pdims, pvs, G = PRE.geometry(pre, native[::-1], nv.voxel_size)
-                            if PRE.needs_scratch(pre):
-                                need = PRE.preproc_scratch_bytes(m.in_count * pdims[0] * pdims[1] * pdims[2])
-                                if pre_scratch is None or pre_scratch.numel() < need:
-                                    pre_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            x = PRE.run_preproc(x, pre, scratch=pre_scratch)
-                            if nv.map is not None:
-                                fwd = nv.map
-                            else:
-                                fwd = SP.model_to_image_map(D0 or m.dim, vs0 or m.voxel_size, pdims, pvs)
-                            if ori:
-                                fwd = SP.compose_map(fwd, M)                             # model voxel -> preprocessed-grid position
-                            back = SP.invert_map(SP.compose_map(G, fwd))                 # original native voxel -> model position
-                            x = SP.to_model_space(m, x, pvs, map=fwd)[0].unsqueeze(0)
-                        else:                                                            # read_image_and_label, on the compute stream
-                            native = (d, io.shape[1], io.shape[2])
-                            fwd = nv.map if nv.map is not None else SP.model_to_image_map(m.dim, m.voxel_size, native[::-1], nv.voxel_size)
-                            back = SP.invert_map(fwd)                                    # native voxel -> model position
-                            x = torch.from_numpy(io).view(m.in_count, *native).to(self.device)
-                            x = SP.to_model_space(m, x, nv.voxel_size, map=fwd)[0].unsqueeze(0)
-                        stack = members = None
-                        if plan is not None:                                             # one forward per tile (evaluate.cpp:223-230)
-                            size = canvas[::-1]
-                            stack = forward_tiles(x, plan)
-                            if nv is not None or steps is None:                          # the canvas logits, as if the model's grid were the canvas
-                                result, stack = TL.blend(stack, plan, size), None
-                        elif mirrored:                                                   # one forward per member
-                            size = tuple(x.shape[2:])
-                            members = forward_mirrored(x)
-                            if nv is None and steps is not None:                         # the chain combines what it reads
-                                result = None
-                            else:                                                        # the mean logits, then today's path
-                                result, members = MR.combine(members, masks, swap)[0], None
-                        else:
-                            size = tuple(x.shape[2:])
-                            result = m.forward(x, packs_current=size in packed_sizes)[0]     # evaluate.cpp:226-227
-                            packed_sizes.add(size)
-                        if steps is not None:                                            # evaluate.cpp:274, on the compute stream
-                            voxels = d * io.shape[1] * io.shape[2] if nv is not None or plan is not None or result is None else result.numel() // m.out_count
-                            if P.needs_scratch(steps):
-                                need = P.postproc_scratch_bytes(m.out_count, voxels)
-                                if scratch is None or scratch.numel() < need:
-                                    scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            if listed:
-                                need = CMP.components_scratch_bytes(voxels, m.out_count)
-                                if cmp_scratch is None or cmp_scratch.numel() < need:
-                                    cmp_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            if ops:
-                                need = MO.morph_scratch_bytes((d, io.shape[1], io.shape[2]))
-                                if morph_scratch is None or morph_scratch.numel() < need:
-                                    morph_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                            results = P.run_postproc(result if stack is None else None, steps,
-                                                     outputs=chain_outputs + (("agreement",) if want_agr else ()), scratch=scratch,
-                                                     mirror=None if members is None else (members, masks, swap),
-                                                     native=None if nv is None else (back, native),
-                                                     tiles=None if stack is None else (stack, plan, size),
-                                                     single_component=listed or None, component_scratch=cmp_scratch,
-                                                     single_component_connectivity=cmp_conn,
-                                                     morphology=ops or None, morphology_scratch=morph_scratch)
-                            extra = {}
-                            if atl is not None and staged:                               # the atlas stage, on the compute stream
-                                label = results["label"].view(d, io.shape[1], io.shape[2])
-                                vs = nv.voxel_size if nv is not None else m.voxel_size
-                                parc, report = REG.parcellate(label, vs, atl.template, atl.template_vs, atl.regions, atl.n_tissues,
-                                                              **dict(self.atlas_options or {}))
-                                if "atlas" in staged:
-                                    results["atlas"] = parc
-                                if "regions" in staged:
-                                    need = TAB.table_scratch_bytes(voxels, atl.n_regions)
-                                    if tab_scratch is None or tab_scratch.numel() < need:
-                                        tab_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                                    results["regions"] = TAB.regions(parc, atl.n_regions, scratch=tab_scratch)
-                                    results["tissue_hist"] = REG.joint_hist(label, atl.template, atl.n_tissues,
-                                                                            [np.concatenate(report["map"])]).view(torch.int32)
-                                    extra = dict(report=report, voxel_size=tuple(float(v) for v in vs))
-                            results = {k: (v, (v.numel() // (io.shape[1] * io.shape[2]), io.shape[1], io.shape[2])
-                                           if k in P.OUTPUTS or k in ("atlas", "agreement") else tuple(v.shape))
+                        entry = self._input(cfg, run, io)
+                        result, stack, members, size = self._forward(cfg, run, entry.x, entry.plan,
+                                                                     fused=entry.native is None and cfg.steps is not None)
+                        extra = {}
+                        if cfg.steps is not None:
+                            results = self._chain(cfg, run, entry, result, stack, members, size)
+                            if cfg.atl is not None and cfg.staged:
+                                extra = self._atlas_stage(cfg, run, io, entry, results)
+                            h, w = entry.size[1:]
+                            results = {k: (v, (v.numel() // (h * w), h, w) if k in P.OUTPUTS or k in ("atlas", "agreement") else tuple(v.shape))
                                        for k, v in results.items() if k in self.outputs or k == "tissue_hist"}
                         else:
-                            extra = {}
-                            if nv is not None:                                           # handle_fov_post alone: the logits on the native grid
-                                result = SP.resample(result.view(m.out_count, *size), native, back, "linear")
-                            results = {None: (result, (m.out_count * d, io.shape[1], io.shape[2]))}
-                        # evaluate.cpp:228-229 copies the logits to the host before the next forward starts; here the copy runs on its
-                        # own stream into pinned memory under the next buffer's upload + forward (same bytes, same order of results)
-                        done = torch.cuda.Event()
-                        done.record(torch.cuda.current_stream(self.device))
-                        # (pinning costs ~2.6 ms per 50 MB result whether it is done per volume or in one arena for the whole run:
-                        # measured 4.5 vs 7.1 ms per volume, profiles/bench_evaluate.py)
-                        hosts = {}
-                        with torch.cuda.stream(copy_stream):
-                            copy_stream.wait_event(done)
-                            for k, (r, shape) in results.items():
-                                host = torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
-                                host.copy_(r, non_blocking=True)
-                                r.record_stream(copy_stream)
-                                hosts[k] = (host, shape)
-                            ev = torch.cuda.Event()
-                            ev.record(copy_stream)
+                            if entry.native is not None:                                 # handle_fov_post alone: the logits on the native grid
+                                result = SP.resample(result.view(self.model.out_count, *size), entry.native, entry.back, "linear")
+                            results = {None: (result, (self.model.out_count * entry.size[0],) + entry.size[1:])}
+                        landing = self._copy_back(results, copy_stream)
                         if pending is not None:
-                            land(pending)
-                        pending = (self.cur_prog, i, hosts, ev, extra)
+                            _land(out, pending)
+                        pending = (self.cur_prog, i) + landing + (extra,)
                     self.cur_prog += 1
                 if pending is not None:
-                    land(pending)
-                    pending = None
+                    _land(out, pending)
         except Exception as e:                                                           # evaluate.cpp:234-242
             self.error_msg = "error during evaluation:" + str(e)
             self.aborted = True
         self.running = False
         return out
+
+    def _check(self, out):
+        """Everything that ends the run before the first upload, in this order; raises UNetError.  Returns what the loop needs."""
+        m = self.model
+        chain = m.postproc if self.postproc == "model" else self.postproc
+        staged = tuple(o for o in self.outputs if o in ("atlas", "regions"))              # the atlas stage's outputs
+        want_agr = "agreement" in self.outputs                                            # the mirror stage's output
+        chain_outputs = tuple(o for o in self.outputs if o not in staged and o != "agreement")
+        masks = MR.parse_axes(self.mirror_axes)
+        mirrored = len(masks) > 1
+        swap = None
+        if self.mirror_swap is not None:
+            if not mirrored:
+                raise E.UNetError("mirror_swap needs mirror_axes")
+            swap = MR._swap(self.mirror_swap, m.out_count, masks)
+            swap = ("xyz"[swap[0]], swap[1]) if swap[0] >= 0 else None
+        if want_agr and not mirrored:
+            raise E.UNetError("output agreement needs mirror_axes")
+        if want_agr and not chain:
+            raise E.UNetError("output agreement needs a postproc chain")
+        atl = self.atlas
+        if atl is not None and "label" not in chain_outputs:
+            chain_outputs += ("label",)                    # the stage reads it; it is copied back only when wanted
+        if staged and atl is None:
+            raise E.UNetError("output %s needs an atlas" % staged[0])
+        if atl is not None and not chain:
+            raise E.UNetError("an atlas needs a postproc chain that produces a label")
+        steps = None
+        if chain:
+            steps = P.parse_chain(chain, self.params)
+            P.check_chain(steps)
+            P.check_outputs(steps, chain_outputs)
+            if atl is not None and not isinstance(atl, REG.Atlas):
+                raise E.UNetError("atlas must be a register.Atlas")
+        # run_preproc / handle_orientation's failure (evaluate.cpp:201-204)
+        pre = PRE.active(PRE.parse_chain(m.preproc if self.preproc == "model" else self.preproc))
+        ori = PRE.parse_orientation(m.orientation if self.orientation == "model" else self.orientation)
+        ori_map = PRE.orientation_map(ori, m.dim, m.voxel_size) if ori else (None, None, None)
+        listed = CMP.resolve(self.single_component, m)
+        cmp_conn = CN.check(self.single_component_connectivity, "single_component")
+        fov = m.fov_strategy if self.fov_strategy == "model" else self.fov_strategy
+        if fov not in (None, "", "align_top", "tiles"):
+            raise E.UNetError("unknown fov_strategy %s" % (fov,))
+        tiled = fov == "tiles"
+        if tiled and want_agr:
+            raise E.UNetError("output agreement is not available with fov_strategy tiles")
+        if want_agr and any(isinstance(io, SP.NativeVolume) for ios in out for io in ios):
+            raise E.UNetError("output agreement is not available for a NativeVolume")
+        overlap = TL.check_overlap(self.tile_overlap) if tiled else 0.0
+        ops = MO.check_ops(self.morphology, m.out_count) if self.morphology else []
+        if steps is None or "label" not in chain_outputs:  # both act on the label output only
+            listed, ops = [], []
+        return _Checked(steps, chain_outputs, staged, masks, swap, pre, ori, ori_map, listed, cmp_conn, tiled, overlap, ops, atl)
+
+    def _input(self, cfg, run, io):
+        """one entry of model_io -> _Entry: the input on the device, the way back and the grids"""
+        m = self.model
+        model_dim = mW, mH, mD = tuple(int(v) for v in m.dim)
+        nv = io if isinstance(io, SP.NativeVolume) else None
+        if nv is not None:
+            nv.check()
+            io = nv.data
+        elif cfg.pre or cfg.ori:
+            raise E.UNetError("a plain model_io array is already at the model's grid: preproc / orientation need a "
+                              "NativeVolume")
+        io = np.ascontiguousarray(io, dtype=np.float32)
+        if io.ndim != 3 or io.shape[0] % m.in_count:
+            raise E.UNetError("model_io buffer must be (in_count*D, H, W), got %s" % (io.shape,))
+        size = (io.shape[0] // m.in_count, io.shape[1], io.shape[2])
+        plan = canvas = None                                                 # set when this entry runs in more than one tile
+        if cfg.tiled and nv is None:                                         # the array is its own canvas
+            canvas = size[::-1]
+            if canvas[0] < mW or canvas[1] < mH or canvas[2] < mD:
+                raise E.UNetError("fov_strategy tiles: a model_io array (w, h, d) = %s is smaller than the model's %s"
+                                  % (canvas, model_dim))
+        elif cfg.tiled:                                                      # the grid at the model's voxel size that covers the scan
+            if nv.map is not None:
+                raise E.UNetError("a caller's map and tiles do not combine")
+            pdims, pvs, G = PRE.geometry(cfg.pre, size[::-1], nv.voxel_size)
+            canvas = TL.canvas_dims(m.dim, m.voxel_size, pdims, pvs, orientation=cfg.ori)
+        if cfg.tiled and canvas != model_dim:                                # a volume that fits takes the paths below
+            plan = TL.plan_tiles(canvas, model_dim, cfg.overlap)
+        if plan is not None and nv is None:
+            x = torch.from_numpy(io).view(m.in_count, *size).to(self.device)
+            return _Entry(x, None, None, plan, canvas, size)
+        if nv is None:
+            x = torch.from_numpy(io).view(1, m.in_count, *size).to(self.device)
+            return _Entry(x, None, None, plan, canvas, size)
+        if plan is not None:                                                 # run_preproc, then ONE resample to the canvas
+            x = self._preprocessed(cfg, run, io, size, pdims)
+            cD0, cvs0, cM = PRE.orientation_map(cfg.ori, canvas, m.voxel_size) if cfg.ori else (canvas, m.voxel_size, None)
+            fwd = SP.model_to_image_map(cD0, cvs0, pdims, pvs)               # canvas voxel -> preprocessed-grid position
+            if cfg.ori:
+                fwd = SP.compose_map(fwd, cM)
+            back = SP.invert_map(SP.compose_map(G, fwd))                     # original native voxel -> canvas position
+            x = SP.resample(x, canvas[::-1], fwd, "linear", normalize=True)  # one normalisation over the whole scan
+            return _Entry(x, back, size, plan, canvas, size)
+        if cfg.pre or cfg.ori:
+            D0, vs0, M = cfg.ori_map
+            pdims, pvs, G = PRE.geometry(cfg.pre, size[::-1], nv.voxel_size)
+            x = self._preprocessed(cfg, run, io, size, pdims)
+            if nv.map is not None:
+                fwd = nv.map
+            else:
+                fwd = SP.model_to_image_map(D0 or m.dim, vs0 or m.voxel_size, pdims, pvs)
+            if cfg.ori:
+                fwd = SP.compose_map(fwd, M)                                 # model voxel -> preprocessed-grid position
+            back = SP.invert_map(SP.compose_map(G, fwd))                     # original native voxel -> model position
+            x = SP.to_model_space(m, x, pvs, map=fwd)[0].unsqueeze(0)
+        else:                                                                # read_image_and_label, on the compute stream
+            fwd = nv.map if nv.map is not None else SP.model_to_image_map(m.dim, m.voxel_size, size[::-1], nv.voxel_size)
+            back = SP.invert_map(fwd)                                        # native voxel -> model position
+            x = torch.from_numpy(io).view(m.in_count, *size).to(self.device)
+            x = SP.to_model_space(m, x, nv.voxel_size, map=fwd)[0].unsqueeze(0)
+        return _Entry(x, back, size, plan, canvas, size)
+
+    def _preprocessed(self, cfg, run, io, size, pdims):
+        """the upload of a NativeVolume's data, then run_preproc on its own grid, on the compute stream (evaluate.cpp:201-204)"""
+        x = torch.from_numpy(io).view(self.model.in_count, *size).to(self.device)
+        scratch = None
+        if PRE.needs_scratch(cfg.pre):                     # normalize's reduction scratch
+            scratch = run.scratch("preproc", PRE.preproc_scratch_bytes(self.model.in_count * pdims[0] * pdims[1] * pdims[2]))
+        return PRE.run_preproc(x, cfg.pre, scratch=scratch)
+
+    def _forward_mirrored(self, cfg, run, x1):
+        """x1 {1, in_count, d, h, w} on the device -> the stack {K, out_count, d, h, w} of the members' level-0 logits"""
+        m = self.model
+        need = MR.stack_bytes(cfg.masks, m.out_count, x1[0, 0].numel()) // 4
+        if run.member_stack is None or run.member_stack.numel() < need:
+            run.member_stack = torch.empty(need, dtype=torch.float32, device=self.device)
+        return MR.forward_members(m, x1[0], cfg.masks, run.packed_sizes, out=run.member_stack)
+
+    def _forward_tiles(self, cfg, run, xc, plan):
+        """xc {in_count, cd, ch, cw} on the device -> the stack {tiles, out_count, D, H, W} of level-0 logits, one forward
+        per integer crop in tile-index order"""
+        m = self.model
+        mW, mH, mD = (int(v) for v in m.dim)
+        origins = TL.tile_origins(plan)
+        stack = torch.empty((len(origins), m.out_count, mD, mH, mW), dtype=torch.float32, device=self.device)
+        for t, (ox, oy, oz) in enumerate(origins):
+            crop = xc[:, oz:oz + mD, oy:oy + mH, ox:ox + mW].contiguous().unsqueeze(0)
+            size = tuple(crop.shape[2:])
+            if len(cfg.masks) > 1:                         # the members' mean, straight into the tile's slot
+                MR.combine(self._forward_mirrored(cfg, run, crop), cfg.masks, cfg.swap, out={"mean": stack[t]})
+                continue
+            stack[t].copy_(m.forward(crop, packs_current=size in run.packed_sizes)[0].view(m.out_count, mD, mH, mW))
+            run.packed_sizes.add(size)
+        return stack
+
+    def _forward(self, cfg, run, x, plan, fused):
+        """The input on the device -> (result, stack, members, size): the logits on the grid `size` the forward ran on, or, when the
+        chain's leading group reads them itself (fused), the tile stack or the mirrored members' stack in their place."""
+        size = tuple(x.shape[-3:])
+        result = stack = members = None
+        if plan is not None:                               # one forward per tile (evaluate.cpp:223-230)
+            stack = self._forward_tiles(cfg, run, x, plan)
+            if not fused:                                  # the canvas logits, as if the model's grid were the canvas
+                result, stack = TL.blend(stack, plan, size), None
+        elif len(cfg.masks) > 1:                           # one forward per member
+            members = self._forward_mirrored(cfg, run, x)
+            if not fused:                                  # the mean logits, then today's path
+                result, members = MR.combine(members, cfg.masks, cfg.swap)[0], None
+        else:
+            result = self.model.forward(x, packs_current=size in run.packed_sizes)[0]     # evaluate.cpp:226-227
+            run.packed_sizes.add(size)
+        return result, stack, members, size
+
+    def _chain(self, cfg, run, entry, result, stack, members, size):
+        """run_postproc on the grid the results come back on (evaluate.cpp:274), on the compute stream: {output: device tensor}"""
+        m = self.model
+        d, h, w = entry.size
+        voxels = d * h * w if entry.native is not None or entry.plan is not None or result is None else result.numel() // m.out_count
+        want_agr = "agreement" in self.outputs
+        return P.run_postproc(
+            result if stack is None else None, cfg.steps, outputs=cfg.chain_outputs + (("agreement",) if want_agr else ()),
+            scratch=run.scratch("chain", P.postproc_scratch_bytes(m.out_count, voxels)) if P.needs_scratch(cfg.steps) else None,
+            mirror=None if members is None else (members, cfg.masks, cfg.swap),
+            native=None if entry.native is None else (entry.back, entry.native),
+            tiles=None if stack is None else (stack, entry.plan, size),
+            single_component=cfg.listed or None, single_component_connectivity=cfg.cmp_conn,
+            component_scratch=run.scratch("components", CMP.components_scratch_bytes(voxels, m.out_count)) if cfg.listed else None,
+            morphology=cfg.ops or None,
+            morphology_scratch=run.scratch("morphology", MO.morph_scratch_bytes(entry.size)) if cfg.ops else None)
+
+    def _atlas_stage(self, cfg, run, io, entry, results):
+        """register.parcellate on the final label and table.regions on its result, on the compute stream: adds "atlas", "regions" and
+        "tissue_hist" to results and returns what the host arithmetic on them needs"""
+        atl = cfg.atl
+        label = results["label"].view(entry.size)
+        vs = io.voxel_size if isinstance(io, SP.NativeVolume) else self.model.voxel_size
+        parc, report = REG.parcellate(label, vs, atl.template, atl.template_vs, atl.regions, atl.n_tissues,
+                                      **dict(self.atlas_options or {}))
+        if "atlas" in cfg.staged:
+            results["atlas"] = parc
+        if "regions" not in cfg.staged:
+            return {}
+        scratch = run.scratch("table", TAB.table_scratch_bytes(label.numel(), atl.n_regions))
+        results["regions"] = TAB.regions(parc, atl.n_regions, scratch=scratch)
+        results["tissue_hist"] = REG.joint_hist(label, atl.template, atl.n_tissues, [np.concatenate(report["map"])]).view(torch.int32)
+        return dict(report=report, voxel_size=tuple(float(v) for v in vs))
+
+    def _copy_back(self, results, copy_stream):
+        """evaluate.cpp:228-229 copies the logits to the host before the next forward starts; here the copy runs on its own stream
+        into pinned memory under the next buffer's upload + forward (same bytes, same order of results).  Returns
+        ({name: (pinned host tensor, shape)}, the event after the copies)."""
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self.device))
+        # (pinning costs ~2.6 ms per 50 MB result whether it is done per volume or in one arena for the whole run:
+        # measured 4.5 vs 7.1 ms per volume, profiles/bench_evaluate.py)
+        hosts = {}
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(done)
+            for k, (r, shape) in results.items():
+                host = torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
+                host.copy_(r, non_blocking=True)
+                r.record_stream(copy_stream)
+                hosts[k] = (host, shape)
+            ev = torch.cuda.Event()
+            ev.record(copy_stream)
+        return hosts, ev

@@ -51,13 +51,7 @@ def _f32(a, name):
 
 def _scratch(voxels, device, scratch):
     need = feed_scratch_bytes(voxels)
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=device)
-    return scratch
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return E.scratch(scratch, need, device)
 
 
 def label_max(label, out=None, scratch=None):
@@ -65,7 +59,7 @@ def label_max(label, out=None, scratch=None):
     _f32(label, "label")
     out = out if out is not None else torch.empty(1, dtype=torch.int32, device=label.device)
     sc = _scratch(label.numel(), label.device, scratch)
-    E.check(E.lib.unet_feed_label_max(label.data_ptr(), label.numel(), out.data_ptr(), sc.data_ptr(), sc.numel(), _stream(label)))
+    E.check(E.lib.unet_feed_label_max(label.data_ptr(), label.numel(), out.data_ptr(), sc.data_ptr(), sc.numel(), E.stream(label)))
     return out
 
 
@@ -79,7 +73,7 @@ def prepare(label, image0=None, normalize=False, shift_by=0, label_max_out=None,
     sc = _scratch(S, label.device, scratch)
     E.check(E.lib.unet_feed_prepare(image0.data_ptr() if shift_by > 0 else None, label.data_ptr(), S, int(bool(normalize)),
                                     int(shift_by), label_max_out.data_ptr() if label_max_out is not None else None, sc.data_ptr(),
-                                    sc.numel(), _stream(label)))
+                                    sc.numel(), E.stream(label)))
     return label
 
 
@@ -92,7 +86,7 @@ def target(label, normalize=False, out=None, scratch=None):
         raise UNetError("feed: target must be a contiguous int64 tensor of the label's size and device")
     sc = _scratch(label.numel(), label.device, scratch)
     E.check(E.lib.unet_feed_target(label.data_ptr(), label.numel(), int(bool(normalize)), out.data_ptr(), sc.data_ptr(), sc.numel(),
-                                   _stream(label)))
+                                   E.stream(label)))
     return out
 
 
@@ -180,11 +174,8 @@ class TrainingFeed:
 
     def _scratch(self, what, nbytes):
         """scratch per (kind, stream): samples made on two streams never share it"""
-        key = (what, torch.cuda.current_stream(self.device).cuda_stream)
-        sc = self._sc.get(key)
-        if sc is None or sc.numel() < nbytes:
-            sc = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._sc[key] = sc
+        key = (what, E.stream(self.device))
+        sc = self._sc[key] = E.scratch(self._sc.get(key), nbytes, self.device)
         return sc
 
     def _case_of(self, index):

@@ -53,16 +53,6 @@ def match_scratch_bytes(max_pairs):
     return n.value
 
 
-def _scratch(scratch, need, dev):
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    return scratch, scratch.numel() * scratch.element_size()
-
-
-def _stream(stream, t):
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _out(t, n, dtype, dev, who, name):
     if t is None:
         return torch.empty(n, dtype=dtype, device=dev)
@@ -101,10 +91,10 @@ def label(labels, n_classes, classes=None, max_instances=DEFAULT_MAX_INSTANCES, 
     inst = _out(o[0], D * H * W, torch.int32, dev, "label", "inst")
     rows = _out(o[1], (M + 1) * COLUMNS, torch.int64, dev, "label", "rows")
     info = _out(o[2], 2, torch.int64, dev, "label", "info")
-    scratch, sbytes = _scratch(scratch, need, dev)
+    scratch = E.scratch(scratch, need, dev)
     arr = (C.c_uint32 * max(1, len(classes)))(*classes)
     E.check(E.lib.unet_inst_label(W, H, D, lab.data_ptr(), nc, arr, len(classes), inst.data_ptr(), rows.data_ptr(), M, info.data_ptr(),
-                                  int(impl), scratch.data_ptr(), sbytes, _stream(stream, lab)))
+                                  int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(lab, stream)))
     return inst.view(D, H, W), rows.view(M + 1, COLUMNS), info
 
 
@@ -129,9 +119,9 @@ def match_raw(ia, ib, max_pairs, impl=IMPL_DEFAULT, scratch=None, out=None, stre
     keys = _out(o[0], P, torch.int64, dev, "match", "keys")
     counts = _out(o[1], P, torch.int64, dev, "match", "counts")
     info = _out(o[2], 2, torch.int64, dev, "match", "info")
-    scratch, sbytes = _scratch(scratch, need, dev)
+    scratch = E.scratch(scratch, need, dev)
     E.check(E.lib.unet_inst_match(ia.data_ptr(), ib.data_ptr(), ia.numel(), keys.data_ptr() if P else None, counts.data_ptr() if P else None, P,
-                                  info.data_ptr(), int(impl), scratch.data_ptr(), sbytes, _stream(stream, ia)))
+                                  info.data_ptr(), int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(ia, stream)))
     return keys, counts, info
 
 
@@ -173,7 +163,7 @@ def remove_small(labels, inst, rows, min_voxels, removed=None, n_classes=0, stre
         raise UNetError("instances.remove_small: removed must be a contiguous uint32 device tensor of n_classes entries on labels' device")
     E.check(E.lib.unet_inst_remove_small(labels.data_ptr(), inst.data_ptr(), labels.numel(), rows.data_ptr(), rows.numel() // COLUMNS - 1,
                                          int(min_voxels), removed.data_ptr() if removed is not None else None, int(n_classes),
-                                         _stream(stream, labels)))
+                                         E.stream(labels, stream)))
     return labels
 
 

@@ -238,7 +238,7 @@ def combine(stack, masks, swap=None, want_mean=True, want_agreement=False, out=N
     cm, ax, cp, npairs = _host_args(ms, axis, pairs)
     E.check(E.lib.unet_mirror_combine(stack.data_ptr(), out_c, W, H, D, len(ms), cm, ax, cp, npairs,
                                       mean.data_ptr() if mean is not None else None, agr.data_ptr() if agr is not None else None,
-                                      SP._stream(stack)))
+                                      E.stream(stack)))
     return mean, agr
 
 
@@ -262,5 +262,5 @@ def postproc_mirror(stack, masks, swap=None, threshold=0.5, outputs=SP.OUTPUTS, 
     ptr = lambda o: res[o].data_ptr() if o in res else None
     cm, ax, cp, npairs = _host_args(ms, axis, pairs)
     E.check(E.lib.unet_mirror_postproc(stack.data_ptr(), out_c, W, H, D, len(ms), cm, ax, cp, npairs, float(threshold),
-                                       ptr("label_prob"), ptr("fg_prob"), ptr("label"), ptr("agreement"), SP._stream(stack)))
+                                       ptr("label_prob"), ptr("fg_prob"), ptr("label"), ptr("agreement"), E.stream(stack)))
     return res

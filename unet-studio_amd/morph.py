@@ -70,13 +70,7 @@ def morph_scratch_bytes(shape):
 
 def _scratch(scratch, shape, dev):
     need = morph_scratch_bytes(shape)                    # the size checks, before any device work
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    return scratch, scratch.numel() * scratch.element_size()
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return E.scratch(scratch, need, dev)
 
 
 def _mask(m, who, name="m"):
@@ -125,13 +119,13 @@ def pack(labels, n_classes, classes=None, scratch=None, out=None):
         if not 0 <= v < 1 << 32:
             raise UNetError("morph.pack: listed class %d is not in [1, %d]" % (v, nc - 1))
     dev = lab.device
-    scratch, sbytes = _scratch(scratch, (D, H, W), dev)
+    scratch = _scratch(scratch, (D, H, W), dev)
     m = out if out is not None else Mask(torch.empty((D, H, (W + 63) // 64), dtype=torch.int64, device=dev), (D, H, W))
     if _mask(m, "pack", "out").shape != (D, H, W) or m.bits.device != dev:
         raise UNetError("morph.pack: out must be a Mask of shape %s on labels' device" % ((D, H, W),))
     arr = (C.c_uint32 * max(1, len(classes)))(*classes)
     E.check(E.lib.unet_morph_pack(W, H, D, lab.data_ptr(), lab.element_size(), nc, arr, len(classes), m.bits.data_ptr(),
-                                  scratch.data_ptr(), sbytes, _stream(lab)))
+                                  scratch.data_ptr(), scratch.nbytes, E.stream(lab)))
     return m
 
 
@@ -139,7 +133,7 @@ def unpack(m):
     """unet_morph_unpack: a uint8 (D, H, W) device tensor, 1 where the bit is set"""
     D, H, W = _mask(m, "unpack").shape
     out = torch.empty((D, H, W), dtype=torch.uint8, device=m.bits.device)
-    E.check(E.lib.unet_morph_unpack(W, H, D, m.bits.data_ptr(), out.data_ptr(), _stream(out)))
+    E.check(E.lib.unet_morph_unpack(W, H, D, m.bits.data_ptr(), out.data_ptr(), E.stream(out)))
     return out
 
 
@@ -147,7 +141,7 @@ def count(m):
     """unet_morph_count: a device int64[1] tensor, the set bits"""
     D, H, W = _mask(m, "count").shape
     out = torch.empty(1, dtype=torch.int64, device=m.bits.device)
-    E.check(E.lib.unet_morph_count(W, H, D, m.bits.data_ptr(), out.data_ptr(), _stream(out)))
+    E.check(E.lib.unet_morph_count(W, H, D, m.bits.data_ptr(), out.data_ptr(), E.stream(out)))
     return out
 
 
@@ -155,9 +149,9 @@ def _step(m, op, connectivity, iterations, border, impl, scratch, out, who):
     D, H, W = _mask(m, who).shape
     c, n = _connectivity(connectivity, who), _iterations(iterations, who)
     out = _out_mask(out, m, who)
-    scratch, sbytes = _scratch(scratch, m.shape, m.bits.device)
+    scratch = _scratch(scratch, m.shape, m.bits.device)
     E.check(E.lib.unet_morph_step(W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), op, c, n, int(border), int(impl), scratch.data_ptr(),
-                                  sbytes, _stream(m.bits)))
+                                  scratch.nbytes, E.stream(m.bits)))
     return out
 
 
@@ -190,10 +184,10 @@ def fill_holes(m, impl=IMPL_DEFAULT, scratch=None, out=None, connectivity=6):
         return CN.fill_holes(m, connectivity, impl=impl, scratch=scratch, out=out)
     D, H, W = _mask(m, "fill_holes").shape
     out = _out_mask(out, m, "fill_holes")
-    scratch, sbytes = _scratch(scratch, m.shape, m.bits.device)
+    scratch = _scratch(scratch, m.shape, m.bits.device)
     info = torch.empty(2, dtype=torch.int64, device=m.bits.device)
-    E.check(E.lib.unet_morph_holes(W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), info.data_ptr(), int(impl), scratch.data_ptr(), sbytes,
-                                   _stream(m.bits)))
+    E.check(E.lib.unet_morph_holes(W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), info.data_ptr(), int(impl), scratch.data_ptr(), scratch.nbytes,
+                                   E.stream(m.bits)))
     return out, info
 
 
@@ -210,7 +204,7 @@ def apply(labels, m, value, mode, changed=None):
               and changed.numel() == 1):
         raise UNetError("morph.apply: changed must be a device int64 tensor of one entry on labels' device")
     D, H, W = m.shape
-    E.check(E.lib.unet_morph_apply(W, H, D, lab.data_ptr(), m.bits.data_ptr(), int(value), int(mode), changed.data_ptr(), _stream(lab)))
+    E.check(E.lib.unet_morph_apply(W, H, D, lab.data_ptr(), m.bits.data_ptr(), int(value), int(mode), changed.data_ptr(), E.stream(lab)))
     return changed
 
 
@@ -226,7 +220,7 @@ def _label_op(name, labels, value, connectivity, iterations, border, impl, scrat
     v = _value(value, name + "_label")
     _connectivity(connectivity, name + "_label")
     _iterations(iterations, name + "_label")
-    scratch, _ = _scratch(scratch, lab.shape, lab.device)
+    scratch = _scratch(scratch, lab.shape, lab.device)
     m = pack(lab, v + 1, [v], scratch=scratch)             # the voxels equal to value: everything above it is no member
     if name == "dilate":
         m = dilate(m, connectivity, iterations, impl, scratch)
@@ -265,7 +259,7 @@ def fill_holes_label(labels, classes, value, n_classes, impl=IMPL_DEFAULT, scrat
     CN.check(connectivity, "morph.fill_holes_label")
     lab = _label_map(labels, "fill_holes_label", (torch.uint16,))
     v = _value(value, "fill_holes_label")
-    scratch, _ = _scratch(scratch, lab.shape, lab.device)
+    scratch = _scratch(scratch, lab.shape, lab.device)
     m = pack(lab, n_classes, classes, scratch=scratch)
     fill_holes(m, impl, scratch, out=m, connectivity=connectivity)
     return apply(lab, m, v, SET, changed)
@@ -329,7 +323,7 @@ def run(labels, ops, n_classes, scratch=None):
     lab = _label_map(labels, "run", (torch.uint16,))
     changed = torch.zeros(len(ops), dtype=torch.int64, device=lab.device)
     if ops:
-        scratch, _ = _scratch(scratch, lab.shape, lab.device)
+        scratch = _scratch(scratch, lab.shape, lab.device)
     for i, op in enumerate(ops):
         if op[0] == "fill_holes":
             fill_holes_label(lab, op[1], op[2], n_classes, scratch=scratch, changed=changed[i:i + 1],

@@ -14,6 +14,7 @@ The per-plane commands and defragment_each act on label_prob.  A wanted output t
 Adjacent softmax / create_mask / argmax run as one fused kernel, and an output nobody asked for and no later command reads is
 never written (the default chain with outputs=("label",) reads the logits once and writes 2 bytes per voxel).
 run_postproc(morphology=...) repairs the `label` output afterwards (morph.py: dilate / erode / open / close / fill_holes)."""
+import collections
 import ctypes as C
 
 import torch
@@ -143,14 +144,14 @@ def _ptr(t):
 
 def softmax_call(logits, out_c, voxels, threshold=0.5, label_prob=None, fg_prob=None, label=None, stream=None):
     """unet_postproc_softmax on device pointers / tensors (None: not wanted); stream: the current one when None"""
-    st = stream if stream is not None else torch.cuda.current_stream(logits.device).cuda_stream
+    st = E.stream(logits, stream)
     E.check(E.lib.unet_postproc_softmax(_ptr(logits), int(out_c), int(voxels), float(threshold), _ptr(label_prob), _ptr(fg_prob),
                                         _ptr(label), st))
 
 
 def argmax_planes_call(label_prob, n_planes, voxels, fg_prob, threshold, label, stream=None):
     """unet_postproc_argmax_planes"""
-    st = stream if stream is not None else torch.cuda.current_stream(label_prob.device).cuda_stream
+    st = E.stream(label_prob, stream)
     E.check(E.lib.unet_postproc_argmax_planes(_ptr(label_prob), int(n_planes), int(voxels), _ptr(fg_prob), float(threshold), _ptr(label),
                                               st))
 
@@ -159,18 +160,90 @@ def defragment_call(dims, each, threshold, size_ratio, fg_prob, label_prob, n_pl
     """unet_postproc_defragment; dims = (W, H, D)"""
     any_t = label_prob if each else fg_prob
     dev = any_t.device if any_t is not None else torch.device("cuda", torch.cuda.current_device())
-    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = E.stream(dev, stream)
     E.check(E.lib.unet_postproc_defragment(int(dims[0]), int(dims[1]), int(dims[2]), int(bool(each)), float(threshold), float(size_ratio),
                                            _ptr(fg_prob), _ptr(label_prob), int(n_planes), _ptr(label), _ptr(scratch),
-                                           scratch.numel() * scratch.element_size() if scratch is not None else 0, st))
+                                           scratch.nbytes if scratch is not None else 0, st))
 
 
 def plane_op_call(op, param, dims, label_prob, n_planes, scratch, stream=None):
     """unet_postproc_plane_op; dims = (W, H, D)"""
     dev = label_prob.device if label_prob is not None else torch.device("cuda", torch.cuda.current_device())
-    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = E.stream(dev, stream)
     E.check(E.lib.unet_postproc_plane_op(int(op), float(param), int(dims[0]), int(dims[1]), int(dims[2]), _ptr(label_prob), int(n_planes),
-                                         _ptr(scratch), scratch.numel() * scratch.element_size() if scratch is not None else 0, st))
+                                         _ptr(scratch), scratch.nbytes if scratch is not None else 0, st))
+
+
+# where one volume's logits come from: head(thr, wanted) is the fused pass that reads a stack without storing logits (it returns the
+# outputs it made beyond `wanted`), logits() the materialised logits, made once; agreement() the mirror's vote map on its own
+Source = collections.namedtuple("Source", "out_c shape device head logits agreement")
+
+
+def _tensor_source(logits):
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
+        raise UNetError("run_postproc: logits must be a contiguous float32 device tensor")
+    if logits.dim() == 5:
+        if logits.shape[0] != 1:
+            raise UNetError("run_postproc: one volume at a time, got a batch of %d" % logits.shape[0])
+        logits = logits[0]
+    if logits.dim() != 4:
+        raise UNetError("run_postproc: logits must be {C, D, H, W}, got %s" % (tuple(logits.shape),))
+    out_c, D, H, W = (int(v) for v in logits.shape)
+    return Source(out_c, (D, H, W), logits.device, None, lambda: logits, None)
+
+
+def _tile_source(tiles, logits, native):
+    from . import space as SP
+    from . import tiles as TL
+    if logits is not None or native is not None:
+        raise UNetError("run_postproc: tiles come in place of logits and do not combine with native")
+    stack, plan, canvas_shape = tiles
+    canvas_shape = SP._shape3(canvas_shape, "canvas shape")
+    out_c = TL._stack(stack, TL._plan_struct(plan))[0]
+    blended = None
+
+    def canvas_logits():
+        nonlocal blended
+        if blended is None:
+            blended = TL.blend(stack, plan, canvas_shape)
+        return blended
+
+    def head(thr, wanted):
+        TL.postproc_tiles(stack, plan, canvas_shape, thr, tuple(wanted), out=wanted)
+        return {}
+    return Source(out_c, canvas_shape, stack.device, head, canvas_logits, None)
+
+
+def _mirror_source(mirror, logits, native, want_agr):
+    from . import mirror as MR
+    if logits is not None or native is not None:
+        raise UNetError("run_postproc: mirror comes in place of logits and does not combine with tiles or native")
+    stack, masks, swap = mirror
+    masks = MR._masks(masks)
+    out_c, D, H, W = MR._stack(stack, masks)
+    MR._swap(swap, out_c, masks)                       # a bad swap is refused before any device work
+    mean = None
+
+    def mean_logits():
+        nonlocal mean
+        if mean is None:
+            mean = MR.combine(stack, masks, swap)[0]
+        return mean
+
+    def head(thr, wanted):
+        nonlocal mean
+        if want_agr and len(masks) >= MIRROR_PAIR_FROM:
+            # the fused pass with the K + 1 running amax beside the softmax state runs at 2 waves per SIMD: from 4
+            # members on, combine (where the agreement is free) + softmax measured faster (DESIGN.md §26), same bits
+            mean, agr = MR.combine(stack, masks, swap, True, True)
+            softmax_call(mean, out_c, D * H * W, thr, wanted.get("label_prob"), wanted.get("fg_prob"), wanted.get("label"))
+            return {"agreement": agr}
+        # otherwise the same pass counts the votes
+        extra = {"agreement": torch.empty((D, H, W), dtype=torch.uint8, device=stack.device)} if want_agr else {}
+        MR.postproc_mirror(stack, masks, swap, thr, tuple(wanted) + tuple(extra), out={**wanted, **extra})
+        return extra
+    return Source(out_c, (D, H, W), stack.device, head, mean_logits,
+                  lambda: MR.combine(stack, masks, swap, want_mean=False, want_agreement=True)[1])
 
 
 def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
@@ -211,34 +284,12 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     if tiles is not None and mirror is not None:
         raise UNetError("run_postproc: mirror does not combine with tiles or native")
     if tiles is not None:
-        from . import space as SP
-        from . import tiles as TL
-        if logits is not None or native is not None:
-            raise UNetError("run_postproc: tiles come in place of logits and do not combine with native")
-        stack, plan, canvas_shape = tiles
-        D, H, W = canvas_shape = SP._shape3(canvas_shape, "canvas shape")
-        out_c = TL._stack(stack, TL._plan_struct(plan))[0]
-        dev = stack.device
+        src = _tile_source(tiles, logits, native)
     elif mirror is not None:
-        from . import mirror as MR
-        if logits is not None or native is not None:
-            raise UNetError("run_postproc: mirror comes in place of logits and does not combine with tiles or native")
-        mstack, masks, swap = mirror
-        masks = MR._masks(masks)
-        out_c, D, H, W = MR._stack(mstack, masks)
-        MR._swap(swap, out_c, masks)                   # a bad swap is refused before any device work
-        dev = mstack.device
+        src = _mirror_source(mirror, logits, native, want_agr)
     else:
-        if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
-            raise UNetError("run_postproc: logits must be a contiguous float32 device tensor")
-        if logits.dim() == 5:
-            if logits.shape[0] != 1:
-                raise UNetError("run_postproc: one volume at a time, got a batch of %d" % logits.shape[0])
-            logits = logits[0]
-        if logits.dim() != 4:
-            raise UNetError("run_postproc: logits must be {C, D, H, W}, got %s" % (tuple(logits.shape),))
-        out_c, D, H, W = (int(v) for v in logits.shape)
-        dev = logits.device
+        src = _tensor_source(logits)
+    out_c, (D, H, W), dev = src.out_c, src.shape, src.device
     if native is not None:
         from . import space as SP
         native_map, (D, H, W) = native[0], SP._shape3(native[1], "native shape")
@@ -258,13 +309,11 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     want_lab = "argmax" in names and "label" in outputs
     changed = False
     res = {}
-    scr = [scratch]
 
     def get_scratch():
-        need = postproc_scratch_bytes(out_c, S)
-        if scr[0] is None or scr[0].numel() * scr[0].element_size() < need:
-            scr[0] = torch.empty(need, dtype=torch.uint8, device=dev)
-        return scr[0]
+        nonlocal scratch
+        scratch = E.scratch(scratch, postproc_scratch_bytes(out_c, S), dev)
+        return scratch
 
     i = 0
     while i < len(steps):
@@ -284,34 +333,13 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
             thr = run.get("argmax", {}).get("threshold", 0.5)
             fused_lab = lab if not changed else None      # after a change argmax reads the current planes, below
             if lp is not None or fg is not None or fused_lab is not None:
-                if tiles is not None and i == 0:
-                    wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
-                    wanted = {k: v for k, v in wanted.items() if v is not None}
-                    TL.postproc_tiles(stack, plan, canvas_shape, thr, tuple(wanted), out=wanted)
-                elif mirror is not None and i == 0:
-                    wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
-                    wanted = {k: v for k, v in wanted.items() if v is not None}
-                    if want_agr and len(masks) >= MIRROR_PAIR_FROM:
-                        # the fused pass with the K + 1 running amax beside the softmax state runs at 2 waves per SIMD: from 4
-                        # members on, combine (where the agreement is free) + softmax measured faster, same bits
-                        logits, agr = MR.combine(mstack, masks, swap, True, want_agr)
-                        if want_agr:
-                            res["agreement"] = agr
-                        softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
-                    else:
-                        if want_agr:                          # the same pass counts the votes
-                            wanted["agreement"] = res["agreement"] = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
-                        MR.postproc_mirror(mstack, masks, swap, thr, tuple(wanted), out=wanted)
-                elif native is None:
-                    if logits is None and mirror is not None:   # a later group of a mirrored volume: the mean logits, made once
-                        logits = MR.combine(mstack, masks, swap)[0]
-                    elif logits is None:                      # a later group of a tiled volume: the canvas logits, made once
-                        logits = TL.blend(stack, plan, canvas_shape)
-                    softmax_call(logits, out_c, S, thr, lp, fg, fused_lab)
+                wanted = {k: v for k, v in (("label_prob", lp), ("fg_prob", fg), ("label", fused_lab)) if v is not None}
+                if native is not None:
+                    SP.postproc_native(src.logits(), native_map, (D, H, W), thr, tuple(wanted), out=wanted)
+                elif i == 0 and src.head is not None:
+                    res.update(src.head(thr, wanted))
                 else:
-                    wanted = {"label_prob": lp, "fg_prob": fg, "label": fused_lab}
-                    wanted = {k: v for k, v in wanted.items() if v is not None}
-                    SP.postproc_native(logits, native_map, (D, H, W), thr, tuple(wanted), out=wanted)
+                    softmax_call(src.logits(), out_c, S, thr, lp, fg, fused_lab)
             if lab is not None and changed:
                 argmax_planes_call(res["label_prob"], out_c - 1, S, res["fg_prob"], thr, lab)
             i = j
@@ -329,7 +357,7 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
             plane_op_call(PLANE_OPS[name], param, (W, H, D), lp, out_c - 1, get_scratch())
         i += 1
     if want_agr and "agreement" not in res:            # no fused group at the head of the chain wrote it
-        res["agreement"] = MR.combine(mstack, masks, swap, want_mean=False, want_agreement=True)[1]
+        res["agreement"] = src.agreement()
     if want_agr:
         outputs += ("agreement",)
     if listed and "label" in outputs:

@@ -164,7 +164,7 @@ def apply(name, src, out=None, impl=IMPL_DEFAULT):
     if name not in COMMANDS or name in ("none", "normalize"):
         raise UNetError("preproc: %s is not an out-of-place command" % (name,))
     out = _out(src, out, result_shape(name, src.shape))
-    st = SP._stream(src)
+    st = E.stream(src)
     if name in FILTERS:
         E.check(E.lib.unet_preproc_filter(src.data_ptr(), out.data_ptr(), w, h, d, c, FILTERS[name], int(impl), st))
     elif name == "downsampling":
@@ -181,10 +181,9 @@ def normalize_(buf, scratch=None):
     if not (torch.is_tensor(buf) and buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
         raise UNetError("preproc: normalize needs a contiguous float32 device tensor")
     need = preproc_scratch_bytes(buf.numel())
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=buf.device)
-    E.check(E.lib.unet_preproc_normalize(buf.data_ptr(), buf.numel(), scratch.data_ptr(), scratch.numel() * scratch.element_size(),
-                                         SP._stream(buf)))
+    scratch = E.scratch(scratch, need, buf.device)
+    E.check(E.lib.unet_preproc_normalize(buf.data_ptr(), buf.numel(), scratch.data_ptr(), scratch.nbytes,
+                                         E.stream(buf)))
     return buf
 
 

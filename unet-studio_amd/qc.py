@@ -80,13 +80,12 @@ def qc_counts(logits, label, collapse_before=0, image0=None, shift_by=0, scratch
         if image0.numel() < S:
             raise UNetError("qc_counts: image0 holds fewer than %d voxels" % S)
     need = qc_scratch_bytes(out_c, S, collapse_before)
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    scratch = E.scratch(scratch, need, dev)
     cp = out_c - collapse_before + 1 if collapse_before else out_c
     counts = torch.empty(2 * cp, dtype=torch.uint64, device=dev)
     E.check(E.lib.unet_qc_counts(logits.data_ptr(), label.data_ptr(), image0.data_ptr() if image0 is not None else None, out_c, S,
                                  int(collapse_before), int(shift_by), counts.data_ptr(), scratch.data_ptr(),
-                                 scratch.numel() * scratch.element_size(), torch.cuda.current_stream(dev).cuda_stream))
+                                 scratch.nbytes, E.stream(dev)))
     return counts
 
 

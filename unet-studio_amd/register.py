@@ -88,10 +88,6 @@ def _tissue(t, name, who, dev=None):
     return (t.data_ptr(), t.element_size(), w, h, d)
 
 
-def _stream(stream, t):
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _out(out, n, dtype, dev, name, who):
     if out is None:
         return torch.empty(n, dtype=dtype, device=dev)
@@ -114,7 +110,7 @@ def joint_hist(subject, template, n_tissues, maps, stride=1, impl=IMPL_DEFAULT, 
     if not (1 <= K <= MAX_MAPS and 2 <= T <= MAX_TISSUES):
         raise UNetError("register.joint_hist: K must be in [1, %d] and n_tissues in [2, %d], got %d and %d" % (MAX_MAPS, MAX_TISSUES, K, T))
     hist = _out(out, K * T * T, torch.uint32, subject.device, "out", "joint_hist")
-    E.check(E.lib.unet_reg_hist(*sg, *tg, T, _floats(flat), K, int(stride), hist.data_ptr(), int(impl), None, 0, _stream(stream, subject)))
+    E.check(E.lib.unet_reg_hist(*sg, *tg, T, _floats(flat), K, int(stride), hist.data_ptr(), int(impl), None, 0, E.stream(subject, stream)))
     return hist.view(K, T, T)
 
 
@@ -134,14 +130,13 @@ def search(subject, template, n_tissues, init, step=DEFAULT_STEP, stages=DEFAULT
         raise UNetError("register.search: step must be 12 numbers and stages (stride, first_level, last_level) triples")
     T, n_it, dev = int(n_tissues), int(max_iterations), subject.device
     need = reg_scratch_bytes(subject.numel(), T, n_it)               # the range checks, before any device work
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    scratch = E.scratch(scratch, need, dev)
     map_out = torch.empty(12, dtype=torch.float32, device=dev)
     tr = torch.empty((n_it, 4), dtype=torch.int64, device=dev) if trace else None
     info = torch.empty(4, dtype=torch.int64, device=dev)
     E.check(E.lib.unet_reg_search(*sg, *tg, T, _floats(m0), _floats(st), sl.ctypes.data_as(C.POINTER(C.c_int)), int(sl.shape[0]), n_it,
                                   map_out.data_ptr(), tr.data_ptr() if trace else None, info.data_ptr(), int(impl), scratch.data_ptr(),
-                                  scratch.numel() * scratch.element_size(), _stream(stream, subject)))
+                                  scratch.nbytes, E.stream(subject, stream)))
     return map_out, tr, info
 
 
@@ -161,7 +156,7 @@ def carry(subject, template, atlas, n_tissues, map, counts=True, out=None, strea
     regions = _out(out, subject.numel(), torch.uint16, subject.device, "out", "carry")
     cnt = torch.empty(3 * T, dtype=torch.uint32, device=subject.device) if counts else None
     E.check(E.lib.unet_reg_carry(*sg, *tg, atlas.data_ptr(), T, _floats(m), regions.data_ptr(), cnt.data_ptr() if counts else None,
-                                 _stream(stream, subject)))
+                                 E.stream(subject, stream)))
     return regions.view(subject.shape), (cnt.view(3, T) if counts else None)
 
 

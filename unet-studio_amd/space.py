@@ -139,10 +139,6 @@ def _shape3(v, name):
     return d, h, w
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def resample(src, dst_shape, map, mode="linear", normalize=False, out=None, scratch=None):
     """unet_space_resample on the current stream.  src: {C, d, h, w} (or {d, h, w}) contiguous fp32 device tensor; dst_shape:
     (D, H, W); map: destination voxel -> source position.  Returns {C, D, H, W} (or {D, H, W}).  normalize (linear only) divides
@@ -166,11 +162,10 @@ def resample(src, dst_shape, map, mode="linear", normalize=False, out=None, scra
     sc_ptr, sc_bytes = None, 0
     if normalize:
         need = space_scratch_bytes(D * H * W, ch)
-        if scratch is None or scratch.numel() * scratch.element_size() < need:
-            scratch = torch.empty(need, dtype=torch.uint8, device=src.device)
-        sc_ptr, sc_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+        scratch = E.scratch(scratch, need, src.device)
+        sc_ptr, sc_bytes = scratch.data_ptr(), scratch.nbytes
     E.check(E.lib.unet_space_resample(src.data_ptr(), sw, sh, sd, out.data_ptr(), W, H, D, ch, C.byref(ms), mode, int(bool(normalize)),
-                                      sc_ptr, sc_bytes, _stream(src)))
+                                      sc_ptr, sc_bytes, E.stream(src)))
     return out.view(shape)
 
 
@@ -204,7 +199,7 @@ def postproc_native(logits, map, native_shape, threshold=0.5, outputs=OUTPUTS, o
         res[o] = t
     ptr = lambda o: res[o].data_ptr() if o in res else None
     E.check(E.lib.unet_space_postproc(logits.data_ptr(), out_c, W, H, D, C.byref(ms), w, h, d, float(threshold), ptr("label_prob"),
-                                      ptr("fg_prob"), ptr("label"), _stream(logits)))
+                                      ptr("fg_prob"), ptr("label"), E.stream(logits)))
     return res
 
 

@@ -55,16 +55,6 @@ def _rows(out, n, dev, who):
     return out
 
 
-def _scratch(scratch, need, dev):
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    return scratch, scratch.numel() * scratch.element_size()
-
-
-def _stream(stream, t):
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-
-
 def regions(labels, n_labels, impl=IMPL_DEFAULT, out=None, scratch=None, stream=None):
     """unet_table_regions on the current stream (or the raw `stream`).  labels: a (D, H, W) uint8 or uint16 device tensor; a value
     above n_labels reads as 0.  Returns int64 {n_labels + 1, 10} on the device (written into `out` when given): per label the
@@ -77,8 +67,8 @@ def regions(labels, n_labels, impl=IMPL_DEFAULT, out=None, scratch=None, stream=
     L = int(n_labels)
     need = table_scratch_bytes(labels.numel(), L)                  # the range checks, before any device work
     rows = _rows(out, (L + 1) * REGION_COLUMNS, labels.device, "regions")
-    scratch, sbytes = _scratch(scratch, need, labels.device)
-    E.check(E.lib.unet_table_regions(ptr, nbytes, w, h, d, L, rows.data_ptr(), int(impl), scratch.data_ptr(), sbytes, _stream(stream, labels)))
+    scratch = E.scratch(scratch, need, labels.device)
+    E.check(E.lib.unet_table_regions(ptr, nbytes, w, h, d, L, rows.data_ptr(), int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(labels, stream)))
     return rows.view(L + 1, REGION_COLUMNS)
 
 
@@ -93,8 +83,8 @@ def overlap(a, b, n_labels, impl=IMPL_DEFAULT, out=None, scratch=None, stream=No
     L = int(n_labels)
     need = table_scratch_bytes(a.numel(), L)
     rows = _rows(out, (L + 1) * OVERLAP_COLUMNS, a.device, "overlap")
-    scratch, sbytes = _scratch(scratch, need, a.device)
-    E.check(E.lib.unet_table_overlap(pa, ab, pb, bb, a.numel(), L, rows.data_ptr(), int(impl), scratch.data_ptr(), sbytes, _stream(stream, a)))
+    scratch = E.scratch(scratch, need, a.device)
+    E.check(E.lib.unet_table_overlap(pa, ab, pb, bb, a.numel(), L, rows.data_ptr(), int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(a, stream)))
     return rows.view(L + 1, OVERLAP_COLUMNS)
 
 

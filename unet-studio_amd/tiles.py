@@ -145,7 +145,7 @@ def blend(tiles, plan, canvas_shape, out=None):
         out = torch.empty((out_c, D, H, W), dtype=torch.float32, device=tiles.device)
     elif SP._f32(out, "out").numel() != out_c * D * H * W or out.device != tiles.device:
         raise UNetError("tiles: out must hold %d values on the stack's device" % (out_c * D * H * W))
-    E.check(E.lib.unet_tiles_blend(tiles.data_ptr(), out_c, tw, th, td, C.byref(ps), W, H, D, out.data_ptr(), SP._stream(tiles)))
+    E.check(E.lib.unet_tiles_blend(tiles.data_ptr(), out_c, tw, th, td, C.byref(ps), W, H, D, out.data_ptr(), E.stream(tiles)))
     return out.view(out_c, D, H, W)
 
 
@@ -176,5 +176,5 @@ def postproc_tiles(tiles, plan, canvas_shape, threshold=0.5, outputs=OUTPUTS, ou
         res[o] = t
     ptr = lambda o: res[o].data_ptr() if o in res else None
     E.check(E.lib.unet_tiles_postproc(tiles.data_ptr(), out_c, tw, th, td, C.byref(ps), W, H, D, float(threshold), ptr("label_prob"),
-                                      ptr("fg_prob"), ptr("label"), SP._stream(tiles)))
+                                      ptr("fg_prob"), ptr("label"), E.stream(tiles)))
     return res

@@ -13,6 +13,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import engine as E
+
 
 class TrainingParam:
     """training_param, train.hpp:8-30 (the fields the step loop reads)."""
@@ -111,7 +113,7 @@ class Trainer:
         # bucketed backward, so the per-bucket all-reduces are only used when EVERY rank has at least one micro-step.
         multi = self.world_size > 1 or self.comm is not None
         overlap = (multi and self.overlap and hasattr(m, "forward_backward_bucketed") and p.batch_size >= self.world_size)
-        stream = torch.cuda.current_stream(m.device()).cuda_stream if self.comm is not None else None
+        stream = E.stream(m.device()) if self.comm is not None else None
 
         def reduce_bucket(lo, hi):   # the bucket's gradients are final: sum them over the replicas under the rest of the backward
             if hi > lo and self.comm is not None:
@@ -199,7 +201,6 @@ class Trainer:
         """this rank's micro-steps of one optimizer step, `in_flight` at a time: micro-step k on lane k % in_flight (stream order inside a
         lane), gradients of micro-step k into buffer k (buffer 0 = flat_grads), then ONE ordered sum into flat_grads"""
         import torch.cuda as tc
-        from . import engine as E
         p, m = self.param, self.model
         x0, _ = self.source(cur_data_index + mine[0])
         if self._lanes is None:

@@ -18,10 +18,6 @@ _DT = {"fp32": E.DTYPE_F32, "f32": E.DTYPE_F32, "float32": E.DTYPE_F32, "bf16": 
 _NO_FUSED_LOSS = False   # (forward and loss as two engine calls: test_fused_forward_loss_equals_the_two_calls compares them through the ABI)
 
 
-def _stream_ptr(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 class SGD:
     """What callers use of torch::optim::SGD (train.cpp:567-571,765-766): param_groups()[i].lr, step(), zero_grad().
     Configuration is create_optimizer's (unet.cpp:246-277): momentum 0.99, nesterov, weight decay 3e-5 on
@@ -48,13 +44,13 @@ class SGD:
                                                self.momentum_buffer.data_ptr(), lr, self.momentum, int(self.nesterov),
                                                self.weight_decay, clip_norm, grad_scale, self.last_grad_norm.data_ptr(),
                                                m._workspace(plan).data_ptr(), 1, ctypes.byref(made), self._scratch.data_ptr(),
-                                               _stream_ptr(m.device())))
+                                               E.stream(m.device())))
         else:
             plan = m._any_plan()
             E.check(E.lib.unet_sgd_step(plan.handle, m.flat_params.data_ptr(), m.flat_grads.data_ptr(),
                                         self.momentum_buffer.data_ptr(), lr, self.momentum, int(self.nesterov),
                                         self.weight_decay, clip_norm, grad_scale, self.last_grad_norm.data_ptr(),
-                                        self._scratch.data_ptr(), _stream_ptr(m.device())))
+                                        self._scratch.data_ptr(), E.stream(m.device())))
         m._params_version += 1
         return bool(made.value)
 
@@ -301,7 +297,7 @@ class UNet3d:
         outs = [torch.empty(s, dtype=torch.float32, device=self._device) if s[1] > 0 else None for s in plan.output_shapes]
         pp, bp = self._pp, self._bp
         op = E.ptr_array([o.data_ptr() if o is not None else None for o in outs])
-        E.check(E.lib.unet_forward(plan.handle, pp, bp, x.data_ptr(), op, ws.data_ptr(), mode, _stream_ptr(self._device)))
+        E.check(E.lib.unet_forward(plan.handle, pp, bp, x.data_ptr(), op, ws.data_ptr(), mode, E.stream(self._device)))
         if (mode & 1) and self._buffers:
             self.num_batches_tracked += 1
         return outs
@@ -314,7 +310,7 @@ class UNet3d:
         ws = self._workspace(plan)
         made = ctypes.c_int(0)
         E.check(E.lib.unet_pack_filters(plan.handle, self._pp, ws.data_ptr(), 1 if with_dgrad else 0, ctypes.byref(made),
-                                        _stream_ptr(self._device)))
+                                        E.stream(self._device)))
         return bool(made.value)
 
     def _run_backward(self, plan, ws, grad_outs, grad_x=None, gp=None):
@@ -322,12 +318,12 @@ class UNet3d:
         pp, gp = self._pp, (gp if gp is not None else self._gp)
         go = E.ptr_array([g.data_ptr() if g is not None else None for g in grad_outs])
         E.check(E.lib.unet_backward(plan.handle, pp, go, gp, grad_x.data_ptr() if grad_x is not None else None,
-                                    ws.data_ptr(), _stream_ptr(self._device)))
+                                    ws.data_ptr(), E.stream(self._device)))
 
     def _run_backward_part(self, plan, ws, grad_outs, op_hi, op_lo):
         pp, gp = self._pp, self._gp
         go = E.ptr_array([g.data_ptr() if g is not None else None for g in grad_outs])
-        E.check(E.lib.unet_backward_part(plan.handle, pp, go, gp, None, ws.data_ptr(), op_hi, op_lo, _stream_ptr(self._device)))
+        E.check(E.lib.unet_backward_part(plan.handle, pp, go, gp, None, ws.data_ptr(), op_hi, op_lo, E.stream(self._device)))
 
     def forward_backward_bucketed(self, x, target, on_bucket, cost_ce=True, cost_dice=True, cost_mse=True, collapse_before=0,
                                   max_buckets=3, packs_current=False, losses_out=None):
@@ -414,7 +410,7 @@ class UNet3d:
         out = torch.empty(shape, dtype=torch.float32, device=self._device)
         op = E.ptr_array([out.data_ptr()] + [None] * (len(plan.output_shapes) - 1))
         mode = 1 if self._training else 0
-        E.check(E.lib.unet_forward(plan.handle, self._pp, self._bp, x.data_ptr(), op, ws.data_ptr(), mode, _stream_ptr(self._device)))
+        E.check(E.lib.unet_forward(plan.handle, self._pp, self._bp, x.data_ptr(), op, ws.data_ptr(), mode, E.stream(self._device)))
         if mode and self._buffers:
             self.num_batches_tracked += 1
         return out
@@ -465,7 +461,7 @@ class UNet3d:
                                              target.data_ptr(), mask, collapse_before, E.ptr_array([g.data_ptr() for g in gouts]),
                                              losses.data_ptr(), (loss_scratch if loss_scratch is not None else self._loss_scratch(plan)).data_ptr(),
                                              ws.data_ptr(), mode,
-                                             _stream_ptr(self._device)))
+                                             E.stream(self._device)))
         if self._buffers:
             self.num_batches_tracked += 1
         return outs, losses, gouts
@@ -484,5 +480,5 @@ class UNet3d:
         E.check(E.lib.unet_loss(plan.handle, E.ptr_array([o.data_ptr() if o is not None else None for o in outs]),
                                 target.data_ptr(), mask, collapse_before,
                                 E.ptr_array([g.data_ptr() if g is not None else None for g in gouts]),
-                                losses.data_ptr(), sc.data_ptr(), _stream_ptr(self._device)))
+                                losses.data_ptr(), sc.data_ptr(), E.stream(self._device)))
         return losses, gouts
