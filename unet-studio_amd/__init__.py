@@ -33,6 +33,7 @@ from . import distance  # noqa: F401  (the module: distance.EXPORTS the symbols 
 from . import instances  # noqa: F401  (the module: instances.EXPORTS the symbols of include/unet_instances.h)
 from . import morph  # noqa: F401  (the module: morph.EXPORTS the symbols of include/unet_morph.h)
 from . import connectivity  # noqa: F401  (the module: connectivity.EXPORTS the symbols of include/unet_connectivity.h)
+from . import stats  # noqa: F401  (the module: stats.EXPORTS the symbols of include/unet_stats.h)
 
 
 def save_to_file(model, file_name):

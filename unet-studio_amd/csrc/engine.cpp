@@ -2498,6 +2498,84 @@ int unet_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, i
     });
 }
 
+// ---- the per-region intensity statistics (include/unet_stats.h) ----
+// everything the three calls share, in the order the header lists it; scale: 65536.0f / (hi - lo) in fp32, one subtraction, one division
+static std::string stats_common_error(const std::string& w, const void* labels, int label_bytes, const float* image, int64_t voxels,
+                                      int n_labels, int max_labels, float lo, float hi, const void* rows, const char* rows_name, int rows_align,
+                                      int impl, float* scale) {
+    if (!image) return w + "null image";
+    if ((uintptr_t)image & 3) return w + "image must be 4-byte aligned";
+    if (!labels && n_labels != 0) return w + "n_labels must be 0 when labels is null, got " + std::to_string(n_labels);
+    if (labels && (n_labels < 1 || n_labels > max_labels))
+        return w + "n_labels must be in [1, " + std::to_string(max_labels) + "] when labels is given, got " + std::to_string(n_labels);
+    if (labels && label_bytes != 1 && label_bytes != 2) return w + "label_bytes must be 1 or 2, got " + std::to_string(label_bytes);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31)";
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return w + "lo and hi must be finite";
+    if (!(lo < hi)) return w + "lo must be below hi";
+    const float diff = hi - lo;
+    *scale = 65536.0f / diff;
+    if (!std::isfinite(diff) || !std::isfinite(*scale) || !(*scale > 0.f)) return w + "the scale 65536 / (hi - lo) must be finite";
+    if (!rows) return w + "null " + rows_name;
+    if ((uintptr_t)rows & (uintptr_t)(rows_align - 1)) return w + rows_name + " must be " + std::to_string(rows_align) + "-byte aligned";
+    if (impl < UNET_STATS_IMPL_DEFAULT || impl > UNET_STATS_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
+    return std::string();
+}
+static std::string stats_scratch_error(const std::string& w, const void* scratch, size_t scratch_bytes, int n_labels, int n_quantiles) {
+    if (!scratch) return w + "null scratch";
+    if (scratch_bytes < stats_scratch_bytes(n_labels, n_quantiles)) return w + "scratch too small (see unet_stats_scratch_bytes)";
+    return std::string();
+}
+int unet_stats_scratch_bytes(int64_t voxels, int n_labels, int n_quantiles, size_t* bytes) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail("unet_stats: voxels must be in [1, 2^31)");
+    if (n_quantiles < 0 || n_quantiles > UNET_STATS_MAX_QUANTILES) return fail("unet_stats: n_quantiles must be in [0, 8], got " + std::to_string(n_quantiles));
+    const int max_labels = n_quantiles ? UNET_STATS_MAX_QUANTILE_LABELS : UNET_STATS_MAX_LABELS;
+    if (n_labels < 0 || n_labels > max_labels)
+        return fail("unet_stats: n_labels must be in [0, " + std::to_string(max_labels) + "], got " + std::to_string(n_labels));
+    if (!bytes) return fail("unet_stats_scratch_bytes: null output");
+    *bytes = stats_scratch_bytes(n_labels, n_quantiles);   // the running tables: nothing per voxel
+    return 0;
+}
+int unet_stats_moments(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi,
+                       int64_t* rows, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_stats_moments: ";
+    float scale = 0.f;
+    std::string e = stats_common_error(who, labels, label_bytes, image, voxels, n_labels, UNET_STATS_MAX_LABELS, lo, hi, rows, "rows", 8, impl, &scale);
+    if (e.empty()) e = stats_scratch_error(who, scratch, scratch_bytes, n_labels, 0);
+    if (!e.empty()) return fail(e);
+    return pp_run(image, stream, [&](hipStream_t s) {
+        launch_stats_moments(labels, label_bytes, image, voxels, n_labels, lo, hi, scale, rows, impl, scratch, s);
+    });
+}
+int unet_stats_hist(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi,
+                    int64_t* rows, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_stats_hist: ";
+    float scale = 0.f;
+    std::string e = stats_common_error(who, labels, label_bytes, image, voxels, n_labels, UNET_STATS_MAX_QUANTILE_LABELS, lo, hi, rows, "rows", 8,
+                                       impl, &scale);
+    if (e.empty()) e = stats_scratch_error(who, scratch, scratch_bytes, n_labels, 0);
+    if (!e.empty()) return fail(e);
+    return pp_run(image, stream, [&](hipStream_t s) {
+        launch_stats_hist(labels, label_bytes, image, voxels, n_labels, lo, hi, scale, rows, impl, scratch, s);
+    });
+}
+int unet_stats_quantiles(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi,
+                         const int* permille, int n_quantiles, int32_t* out, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_stats_quantiles: ";
+    float scale = 0.f;
+    if (!permille) return fail(who + "null permille");
+    if (n_quantiles < 1 || n_quantiles > UNET_STATS_MAX_QUANTILES) return fail(who + "n_quantiles must be in [1, 8], got " + std::to_string(n_quantiles));
+    for (int k = 0; k < n_quantiles; ++k)
+        if (permille[k] < 0 || permille[k] > 1000)
+            return fail(who + "permille[" + std::to_string(k) + "] must be in [0, 1000], got " + std::to_string(permille[k]));
+    std::string e = stats_common_error(who, labels, label_bytes, image, voxels, n_labels, UNET_STATS_MAX_QUANTILE_LABELS, lo, hi, out, "out", 4,
+                                       impl, &scale);
+    if (e.empty()) e = stats_scratch_error(who, scratch, scratch_bytes, n_labels, n_quantiles);
+    if (!e.empty()) return fail(e);
+    return pp_run(image, stream, [&](hipStream_t s) {   // permille is consumed inside the launcher
+        launch_stats_quantiles(labels, label_bytes, image, voxels, n_labels, lo, hi, scale, permille, n_quantiles, out, impl, scratch, s);
+    });
+}
+
 // ---- the boundary distances of label maps (include/unet_distance.h) ----
 static std::string dist_grid_error(const std::string& w_, const void* map, const char* name, int bytes, int w, int h, int d) {
     if (!map) return w_ + "null " + name;

@@ -19,6 +19,7 @@
 #include "../../include/unet_qc.h"
 #include "../../include/unet_register.h"
 #include "../../include/unet_space.h"
+#include "../../include/unet_stats.h"
 #include "../../include/unet_table.h"
 #include "../../include/unet_mirror.h"
 #include "../../include/unet_tiles.h"
@@ -466,6 +467,17 @@ void launch_table_regions(const void* labels, int label_bytes, int w, int h, int
                           hipStream_t s);
 void launch_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, int64_t voxels, int n_labels, int64_t* rows, int impl,
                           void* scratch, hipStream_t s);
+
+// kernels_stats.hip: the per-region intensity statistics (include/unet_stats.h); labels may be null (one region, n_labels 0); scale =
+// 65536.0f / (hi - lo), formed by the caller; permille: n_quantiles host ints, read before the return; the running tables live in the
+// scratch
+size_t stats_scratch_bytes(int n_labels, int n_quantiles);
+void launch_stats_moments(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi, float scale,
+                          int64_t* rows, int impl, void* scratch, hipStream_t s);
+void launch_stats_hist(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi, float scale,
+                       int64_t* rows, int impl, void* scratch, hipStream_t s);
+void launch_stats_quantiles(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi,
+                            float scale, const int* permille, int n_quantiles, int32_t* out, int impl, void* scratch, hipStream_t s);
 
 // kernels_distance.hip: the exact squared distance transform and the surface lists (include/unet_distance.h); the volume between
 // the passes lives in the scratch
