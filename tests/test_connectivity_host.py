@@ -1,9 +1,11 @@
 """CPU: the host half of connected components with a chosen connectivity (include/unet_connectivity.h,
 unet-studio_amd/connectivity.py) -- this file's restatements (`label_ref`, `keep_largest_ref`, `holes_ref`: scipy.ndimage.label with
 generate_binary_structure(3, 1 | 2 | 3), importing nothing of the package's kernels), the half neighbourhoods the kernels hook to, the
-maps the GPU tests share, the ABI the library exports, every argument error before any device call, the ops `check_ops` accepts, and
-the facts the definitions rest on.  No device calls.  Shapes are (D, H, W)."""
+maps the GPU tests share, the ABI the library exports, every argument error before any device call (and the whole text of each,
+as tests/golden/conn_abi_errors.json records it), the ops `check_ops` accepts, and the facts the definitions rest on.  No device
+calls.  Shapes are (D, H, W)."""
 import ctypes
+import json
 import os
 import re
 import sys
@@ -432,6 +434,50 @@ def test_wrapper_errors_need_no_device():
         U.run_postproc(torch.zeros((3, 2, 2, 2)), "softmax+create_mask+argmax", single_component=[1], single_component_connectivity=7)
     assert U.qc.lesion_qc(None, "m.nz", [], connectivity=7) == (1, "lesion_qc: connectivity must be 6, 18 or 26, got 7")
     assert "6, 18 or 26" in U.qc.lesion_qc.__doc__ and "6-connected" not in U.qc.lesion_qc.__doc__
+
+
+# ---- the whole texts of those errors (tests/golden/conn_abi_errors.json) -------------------------------------------------------------
+class ClaimsDevice(torch.Tensor):
+    """a host tensor that answers is_cuda with True: it passes a wrapper's check of the tensor, so the checks behind it (the scratch
+    size, the listed classes) are reached on a machine without a device"""
+    is_cuda = True
+
+
+def abi_error(case):
+    """unet_last_error() after one recorded C call.  args: an int or null as it is, a list as a uint32 array, "out" as a size_t
+    to write to"""
+    args = [(ctypes.c_uint32 * max(1, len(a)))(*a) if isinstance(a, list) else ctypes.byref(ctypes.c_size_t()) if a == "out" else a
+            for a in case["args"]]
+    return failing(getattr(U.engine.lib, case["fn"]), *args)
+
+
+def python_error(case):
+    """the UNetError text of one recorded call of a wrapper: its first argument is a (2, 2, 2) uint16 host tensor ("host") or the
+    same as a ClaimsDevice ("claims_device")"""
+    t = torch.zeros((2, 2, 2), dtype=torch.uint16)
+    if case["tensor"] == "claims_device":
+        t = t.as_subclass(ClaimsDevice)
+    module, name = case["fn"].split(".")
+    with pytest.raises(U.UNetError) as e:
+        getattr(getattr(U, module), name)(t, *case["args"], **case["kwargs"])
+    return str(e.value)
+
+
+def test_every_argument_error_of_the_twelve_calls_and_six_wrappers_reads_as_recorded():
+    """The file was recorded from the commit before keep-largest, instance labelling and hole filling got one body per operation: the
+    cases the argument-error tests of test_components_host, test_instances_host, test_morph_host and this file drive through
+    unet_components_* / unet_inst_scratch_bytes / unet_inst_label / unet_morph_scratch_bytes / unet_morph_holes / unet_conn_*, and
+    through the six wrappers a bad connectivity, a host tensor and a listed class of -1 and of 2^32.  Every case fails before any
+    device call."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "conn_abi_errors.json")))
+    assert {c["fn"] for c in golden["abi"]} == set(CN.EXPORTS) | set(U.components.EXPORTS) | {
+        "unet_inst_scratch_bytes", "unet_inst_label", "unet_morph_scratch_bytes", "unet_morph_holes"}
+    assert {c["fn"] for c in golden["python"]} == {"components.keep_largest", "instances.label", "morph.fill_holes",
+                                                    "connectivity.keep_largest", "connectivity.label", "connectivity.fill_holes"}
+    for case in golden["abi"]:
+        assert abi_error(case) == case["error"], case
+    for case in golden["python"]:
+        assert python_error(case) == case["error"], case
 
 
 # ---- check_ops -----------------------------------------------------------------------------------------------------------------------

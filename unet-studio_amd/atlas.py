@@ -34,9 +34,7 @@ MAX_TISSUES, MAX_REGIONS, MAX_ROUNDS, MAX_SMOOTH = 256, 65535, 65534, 16
 def atlas_scratch_bytes(voxels, n_regions, n_tissues, max_rounds=0):
     """One size for both calls; reclassify alone needs only atlas_scratch_bytes(1, n_regions, n_tissues, 0): it has no per-voxel
     scratch."""
-    n = C.c_size_t()
-    E.check(E.lib.unet_atlas_scratch_bytes(int(voxels), int(n_regions), int(n_tissues), int(max_rounds), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_atlas_scratch_bytes, int(voxels), int(n_regions), int(n_tissues), int(max_rounds))
 
 
 def _maps(tissue, atlas, who):

@@ -236,9 +236,7 @@ def to_struct(r):
 
 def scratch_bytes(recipe):
     s = recipe if isinstance(recipe, Recipe) else to_struct(recipe)
-    n = C.c_size_t()
-    engine.check(engine.lib.unet_augment_scratch_bytes(C.byref(s), C.byref(n)))
-    return n.value
+    return engine.size_query(engine.lib.unet_augment_scratch_bytes, C.byref(s))
 
 
 def augment(recipe, image, label, scratch=None):
@@ -390,9 +388,7 @@ def simulate(recipe, t1w, label=None, scratch=None):
         raise engine.UNetError("simulate: t1w must be a contiguous float32 device tensor of the recipe's size (there is no CPU path)")
     if s.with_label and (label is None or not label.is_cuda or label.dtype != torch.float32 or not label.is_contiguous() or label.numel() != n):
         raise engine.UNetError("simulate: the recipe needs a float32 device label volume of the same size")
-    need = C.c_size_t()
-    engine.check(engine.lib.unet_simulate_modality_scratch_bytes(C.byref(s), C.byref(need)))
-    scratch = engine.scratch(scratch, need.value, t1w.device)
+    scratch = engine.scratch(scratch, engine.size_query(engine.lib.unet_simulate_modality_scratch_bytes, C.byref(s)), t1w.device)
     engine.check(engine.lib.unet_simulate_modality_run(C.byref(s), t1w.data_ptr(), label.data_ptr() if s.with_label else None,
                                                        scratch.data_ptr(), scratch.nbytes, engine.stream(t1w)))
     return scratch

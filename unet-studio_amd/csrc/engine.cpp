@@ -43,6 +43,20 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+// f(stream) with the device that owns `any` current: how every call on caller-owned device pointers that has no plan reaches its
+// launcher.  What f throws and a failed launch become the call's error (0 or 1, as the C ABI returns)
+int run_on_device_of(const void* any, void* stream, const std::function<void(hipStream_t)>& f) {
+    try {
+        {
+            hipPointerAttribute_t at;
+            HIP_OK(hipPointerGetAttributes(&at, any));
+            DeviceGuard guard(at.device);
+            f((hipStream_t)stream);
+        }
+        HIP_OK(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
 
 size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
@@ -2030,14 +2044,6 @@ static const char* pp_volume_error(int w, int h, int d, int n_planes, void* scra
         return "unet_postproc: scratch too small (see unet_postproc_scratch_bytes)";
     return nullptr;
 }
-static int pp_run(const void* any, void* stream, const std::function<void(hipStream_t)>& f) {
-    OP_TRY({
-        hipPointerAttribute_t at;
-        HIP_OK(hipPointerGetAttributes(&at, any));
-        DeviceGuard guard(at.device);
-        f((hipStream_t)stream);
-    })
-}
 int unet_postproc_scratch_bytes(int out_c, int64_t voxels, size_t* bytes) {
     if (const char* e = pp_class_error(out_c, voxels)) return fail(e);
     if (!bytes) return fail("unet_postproc_scratch_bytes: null output");
@@ -2049,7 +2055,7 @@ int unet_postproc_softmax(const float* logits, int out_c, int64_t voxels, float 
     if (const char* e = pp_class_error(out_c, voxels)) return fail(e);
     if (!logits) return fail("unet_postproc_softmax: null logits");
     if (!label_prob && !fg_prob && !label) return fail("unet_postproc_softmax: no output wanted");
-    return pp_run(logits, stream, [&](hipStream_t s) {
+    return run_on_device_of(logits, stream, [&](hipStream_t s) {
         launch_postproc_softmax(logits, out_c, voxels, threshold, label_prob, fg_prob, label, s);
     });
 }
@@ -2057,7 +2063,7 @@ int unet_postproc_argmax_planes(const float* label_prob, int n_planes, int64_t v
                                 uint16_t* label, void* stream) {
     if (const char* e = pp_class_error(n_planes + 1, voxels)) return fail(e);
     if (!label_prob || !fg_prob || !label) return fail("unet_postproc_argmax_planes: null device pointer");
-    return pp_run(label_prob, stream, [&](hipStream_t s) {
+    return run_on_device_of(label_prob, stream, [&](hipStream_t s) {
         launch_postproc_argmax_planes(label_prob, n_planes, voxels, fg_prob, threshold, label, s);
     });
 }
@@ -2069,7 +2075,7 @@ int unet_postproc_defragment(int w, int h, int d, int each, float threshold, dou
     if (!each && !fg_prob) return fail("unet_postproc_defragment: defragment needs fg_prob (create_mask)");
     if (label_prob && n_planes < 1 && !each) return fail("unet_postproc_defragment: label_prob given with no planes");
     if (!(size_ratio == size_ratio)) return fail("unet_postproc_defragment: size_ratio is NaN");
-    return pp_run(each ? label_prob : fg_prob, stream, [&](hipStream_t s) {
+    return run_on_device_of(each ? label_prob : fg_prob, stream, [&](hipStream_t s) {
         launch_postproc_defragment(w, h, d, each, threshold, size_ratio, fg_prob, each ? label_prob : (n_planes ? label_prob : nullptr),
                                    n_planes, each ? nullptr : label, scratch, s);
     });
@@ -2079,7 +2085,7 @@ int unet_postproc_plane_op(int op, float param, int w, int h, int d, float* labe
     if (op < UNET_PP_UPPER_THRESHOLD || op > UNET_PP_SMOOTH) return fail("unet_postproc_plane_op: unknown op " + std::to_string(op));
     if (const char* e = pp_volume_error(w, h, d, n_planes, scratch, scratch_bytes)) return fail(e);
     if (!label_prob || n_planes < 1) return fail("unet_postproc_plane_op: no label_prob planes");
-    return pp_run(label_prob, stream, [&](hipStream_t s) { launch_postproc_plane_op(op, param, w, h, d, label_prob, n_planes, scratch, s); });
+    return run_on_device_of(label_prob, stream, [&](hipStream_t s) { launch_postproc_plane_op(op, param, w, h, d, label_prob, n_planes, scratch, s); });
 }
 
 // ---- between a scan's grid and the model's (include/unet_space.h) ----
@@ -2109,7 +2115,7 @@ int unet_space_resample(const float* src, int sw, int sh, int sd, float* dst, in
     if (normalize && scratch_bytes < space_scratch_bytes((int64_t)dw * dh * dd, channels))
         return fail("unet_space_resample: scratch too small (see unet_space_scratch_bytes)");
     const UnetSpaceMap m = *map;
-    return pp_run(dst, stream, [&](hipStream_t s) {
+    return run_on_device_of(dst, stream, [&](hipStream_t s) {
         launch_space_resample(src, sw, sh, sd, dst, dw, dh, dd, channels, m, mode, normalize, scratch, s);
     });
 }
@@ -2122,7 +2128,7 @@ int unet_space_postproc(const float* logits, int out_c, int mw, int mh, int md, 
     if (!map) return fail("unet_space_postproc: null map");
     if (!label_prob && !fg_prob && !label) return fail("unet_space_postproc: no output wanted");
     const UnetSpaceMap m = *map;
-    return pp_run(logits, stream, [&](hipStream_t s) {
+    return run_on_device_of(logits, stream, [&](hipStream_t s) {
         launch_space_postproc(logits, out_c, mw, mh, md, m, nw, nh, nd, threshold, label_prob, fg_prob, label, s);
     });
 }
@@ -2162,7 +2168,7 @@ int unet_tiles_blend(const float* tiles, int out_c, int tw, int th, int td, cons
     if (!e.empty()) return fail(e);
     if (!canvas) return fail("unet_tiles_blend: null canvas");
     const UnetTilePlan p = *plan;
-    return pp_run(tiles, stream, [&](hipStream_t s) { launch_tiles_blend(tiles, out_c, tw, th, td, p, cw, ch, cd, canvas, s); });
+    return run_on_device_of(tiles, stream, [&](hipStream_t s) { launch_tiles_blend(tiles, out_c, tw, th, td, p, cw, ch, cd, canvas, s); });
 }
 int unet_tiles_postproc(const float* tiles, int out_c, int tw, int th, int td, const UnetTilePlan* plan, int cw, int ch, int cd,
                         float threshold, float* label_prob, float* fg_prob, uint16_t* label, void* stream) {
@@ -2170,7 +2176,7 @@ int unet_tiles_postproc(const float* tiles, int out_c, int tw, int th, int td, c
     if (!e.empty()) return fail(e);
     if (!label_prob && !fg_prob && !label) return fail("unet_tiles_postproc: no output wanted");
     const UnetTilePlan p = *plan;
-    return pp_run(tiles, stream, [&](hipStream_t s) {
+    return run_on_device_of(tiles, stream, [&](hipStream_t s) {
         launch_tiles_postproc(tiles, out_c, tw, th, td, p, cw, ch, cd, threshold, label_prob, fg_prob, label, s);
     });
 }
@@ -2212,7 +2218,7 @@ int unet_mirror_combine(const float* stack, int out_c, int w, int h, int d, int 
     const std::string e = mirror_args_error("unet_mirror_combine", stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs);
     if (!e.empty()) return fail(e);
     if (!mean && !agreement) return fail("unet_mirror_combine: no output wanted");
-    return pp_run(stack, stream, [&](hipStream_t s) {
+    return run_on_device_of(stack, stream, [&](hipStream_t s) {
         launch_mirror_combine(stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs, mean, agreement, s);
     });
 }
@@ -2222,7 +2228,7 @@ int unet_mirror_postproc(const float* stack, int out_c, int w, int h, int d, int
     const std::string e = mirror_args_error("unet_mirror_postproc", stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs);
     if (!e.empty()) return fail(e);
     if (!label_prob && !fg_prob && !label && !agreement) return fail("unet_mirror_postproc: no output wanted");
-    return pp_run(stack, stream, [&](hipStream_t s) {
+    return run_on_device_of(stack, stream, [&](hipStream_t s) {
         launch_mirror_postproc(stack, out_c, w, h, d, n_members, masks, swap_axis, pairs, n_pairs, threshold, label_prob, fg_prob, label,
                                agreement, s);
     });
@@ -2242,21 +2248,21 @@ int unet_preproc_filter(const float* src, float* dst, int w, int h, int d, int c
     if (kind != UNET_PREPROC_GAUSSIAN && kind != UNET_PREPROC_MEAN) return fail("unet_preproc_filter: unknown kind " + std::to_string(kind));
     if (impl < UNET_PREPROC_IMPL_DEFAULT || impl > UNET_PREPROC_IMPL_VOXEL) return fail("unet_preproc_filter: unknown impl " + std::to_string(impl));
     if (preproc_filter_blocks(w, h, d, channels) >= ((int64_t)1 << 31)) return fail("unet_preproc_filter: too many tiles for one launch");
-    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_filter(src, dst, w, h, d, channels, kind, impl, s); });
+    return run_on_device_of(dst, stream, [&](hipStream_t s) { launch_preproc_filter(src, dst, w, h, d, channels, kind, impl, s); });
 }
 int unet_preproc_downsample(const float* src, float* dst, int w, int h, int d, int channels, void* stream) {
     if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
-    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_downsample(src, dst, w, h, d, channels, s); });
+    return run_on_device_of(dst, stream, [&](hipStream_t s) { launch_preproc_downsample(src, dst, w, h, d, channels, s); });
 }
 int unet_preproc_upsample(const float* src, float* dst, int w, int h, int d, int channels, void* stream) {
     if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
     if (8 * (int64_t)w * h * d >= ((int64_t)1 << 31)) return fail("unet_preproc_upsample: the result must stay below 2^31 voxels");
-    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_upsample(src, dst, w, h, d, channels, s); });
+    return run_on_device_of(dst, stream, [&](hipStream_t s) { launch_preproc_upsample(src, dst, w, h, d, channels, s); });
 }
 int unet_preproc_permute(const float* src, float* dst, int w, int h, int d, int channels, int op, void* stream) {
     if (const char* e = preproc_volume_error(src, dst, w, h, d, channels)) return fail(e);
     if (op < UNET_PREPROC_FLIP_X || op > UNET_PREPROC_SWAP_XZ) return fail("unet_preproc_permute: unknown op " + std::to_string(op));
-    return pp_run(dst, stream, [&](hipStream_t s) { launch_preproc_permute(src, dst, w, h, d, channels, op, s); });
+    return run_on_device_of(dst, stream, [&](hipStream_t s) { launch_preproc_permute(src, dst, w, h, d, channels, op, s); });
 }
 int unet_preproc_scratch_bytes(int64_t values, size_t* bytes) {
     if (values <= 0) return fail("unet_preproc: values must be positive");
@@ -2269,7 +2275,42 @@ int unet_preproc_normalize(float* buf, int64_t values, void* scratch, size_t scr
     if (values <= 0) return fail("unet_preproc: values must be positive");
     if (!scratch) return fail("unet_preproc_normalize: null scratch");
     if (scratch_bytes < preproc_scratch_bytes(values)) return fail("unet_preproc_normalize: scratch too small (see unet_preproc_scratch_bytes)");
-    return pp_run(buf, stream, [&](hipStream_t s) { launch_preproc_normalize(buf, values, scratch, s); });
+    return run_on_device_of(buf, stream, [&](hipStream_t s) { launch_preproc_normalize(buf, values, scratch, s); });
+}
+
+// ---- checks the headers below word alike (w: the message prefix, "unet_xxx: ") ----
+static std::string ptr_error(const std::string& w, const void* p, const char* name, int align) {
+    if (!p) return w + "null " + name;
+    if ((uintptr_t)p & (uintptr_t)(align - 1)) return w + name + " must be " + std::to_string(align) + "-byte aligned";
+    return std::string();
+}
+static std::string labelling_size_error(const std::string& w, int64_t voxels, int n_classes) {
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
+    if (n_classes < 1 || n_classes > 65536) return w + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
+    return std::string();
+}
+// the labelling's connectivity and impl.  UNET_CONN_IMPL_*, UNET_INST_LABEL_* and UNET_MORPH_IMPL_* are the same three values, so the
+// one range serves the calls of all three headers; a caller whose header has no connectivity passes 6
+static_assert(UNET_INST_LABEL_DEFAULT == UNET_CONN_IMPL_DEFAULT && UNET_INST_LABEL_GLOBAL == UNET_CONN_IMPL_GLOBAL &&
+              UNET_MORPH_IMPL_DEFAULT == UNET_CONN_IMPL_DEFAULT && UNET_MORPH_IMPL_GLOBAL == UNET_CONN_IMPL_GLOBAL, "one impl range");
+static std::string conn_error(const std::string& w, int connectivity, int impl) {
+    if (connectivity != UNET_CONN_6 && connectivity != UNET_CONN_18 && connectivity != UNET_CONN_26)
+        return w + "connectivity must be 6, 18 or 26, got " + std::to_string(connectivity);
+    if (impl < UNET_CONN_IMPL_DEFAULT || impl > UNET_CONN_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
+    return std::string();
+}
+static std::string listed_range_error(const std::string& w, const uint32_t* listed, int n_listed, int n_classes) {
+    for (int i = 0; i < n_listed; ++i)
+        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
+            return w + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]";
+    return std::string();
+}
+// the caller's list as the labelling takes it: a copy (the caller's is consumed here), ascending, each class once
+static std::vector<uint32_t> listed_classes(const uint32_t* listed, int n_listed) {
+    std::vector<uint32_t> classes(listed, listed + n_listed);
+    std::sort(classes.begin(), classes.end());
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    return classes;
 }
 
 // ---- a model's single_component_label (include/unet_components.h) ----
@@ -2284,6 +2325,16 @@ int unet_components_scratch_bytes(int64_t voxels, int n_classes, size_t* bytes) 
     *bytes = components_scratch_bytes(voxels, n_classes);
     return 0;
 }
+// what follows the argument checks of unet_components_keep_largest and unet_conn_keep_largest, which word theirs differently
+static int keep_largest_call(const std::string& who, int w, int h, int d, uint16_t* label, int n_classes, const uint32_t* listed, int n_listed,
+                             uint32_t* removed, int connectivity, int impl, void* scratch, void* stream) {
+    const std::string e = listed_range_error(who, listed, n_listed, n_classes);
+    if (!e.empty()) return fail(e);
+    const std::vector<uint32_t> classes = listed_classes(listed, n_listed);
+    return run_on_device_of(label, stream, [&](hipStream_t s) {
+        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, connectivity, scratch, s);
+    });
+}
 int unet_components_keep_largest(int w, int h, int d, uint16_t* label, int n_classes, const uint32_t* listed, int n_listed,
                                  uint32_t* removed, int impl, void* scratch, size_t scratch_bytes, void* stream) {
     if (w <= 0 || h <= 0 || d <= 0) return fail("unet_components: volume dimensions must be positive");
@@ -2296,16 +2347,7 @@ int unet_components_keep_largest(int w, int h, int d, uint16_t* label, int n_cla
     if (!scratch) return fail("unet_components_keep_largest: null scratch");
     if (scratch_bytes < components_scratch_bytes((int64_t)w * h * d, n_classes))
         return fail("unet_components_keep_largest: scratch too small (see unet_components_scratch_bytes)");
-    for (int i = 0; i < n_listed; ++i)
-        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
-            return fail("unet_components_keep_largest: listed class " + std::to_string(listed[i]) + " is not in [1, " +
-                        std::to_string(n_classes - 1) + "]");
-    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
-    std::sort(classes.begin(), classes.end());
-    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
-    return pp_run(label, stream, [&](hipStream_t s) {
-        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, 6, scratch, s);
-    });
+    return keep_largest_call("unet_components_keep_largest: ", w, h, d, label, n_classes, listed, n_listed, removed, 6, impl, scratch, stream);
 }
 
 // ---- the atlas preparation of load_atlas (include/unet_atlas.h) ----
@@ -2336,7 +2378,7 @@ int unet_atlas_reclassify(int64_t voxels, const void* tissue, int tissue_bytes, 
     if (!scratch) return fail("unet_atlas_reclassify: null scratch");
     if (scratch_bytes < atlas_scratch_bytes(1, n_regions, n_tissues, 0))   // the tables only: no per-voxel scratch
         return fail("unet_atlas_reclassify: scratch too small (see unet_atlas_scratch_bytes)");
-    return pp_run(atlas, stream, [&](hipStream_t s) {
+    return run_on_device_of(atlas, stream, [&](hipStream_t s) {
         launch_atlas_reclassify(voxels, tissue, tissue_bytes, atlas, n_regions, n_tissues, flags, votes, tissue_total, covered, majority,
                                 erased, impl, scratch, s);
     });
@@ -2356,7 +2398,7 @@ int unet_atlas_grow(int w, int h, int d, const void* tissue, int tissue_bytes, u
     if (!scratch) return fail("unet_atlas_grow: null scratch");
     if (scratch_bytes < atlas_scratch_bytes((int64_t)w * h * d, 0, n_tissues, max_rounds))
         return fail("unet_atlas_grow: scratch too small (see unet_atlas_scratch_bytes)");
-    return pp_run(atlas, stream, [&](hipStream_t s) {   // grow is consumed inside the launcher, before this returns
+    return run_on_device_of(atlas, stream, [&](hipStream_t s) {   // grow is consumed inside the launcher, before this returns
         launch_atlas_grow(w, h, d, tissue, tissue_bytes, atlas, n_tissues, flags, grow, max_rounds, smooth_rounds, filled, relabelled,
                           info, scratch, s);
     });
@@ -2398,7 +2440,7 @@ int unet_reg_hist(const void* subject, int sbytes, int sw, int sh, int sd, const
     if (!hist) return fail("unet_reg_hist: null hist");
     if ((uintptr_t)hist & 3) return fail("unet_reg_hist: hist must be 4-byte aligned");
     if (impl < UNET_REG_IMPL_DEFAULT || impl > UNET_REG_IMPL_GLOBAL) return fail("unet_reg_hist: unknown impl " + std::to_string(impl));
-    return pp_run(hist, stream, [&](hipStream_t s) {   // maps is consumed inside the launcher, before this returns
+    return run_on_device_of(hist, stream, [&](hipStream_t s) {   // maps is consumed inside the launcher, before this returns
         launch_reg_hist(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, maps, K, stride, hist, impl, s);
     });
 }
@@ -2432,7 +2474,7 @@ int unet_reg_search(const void* subject, int sbytes, int sw, int sh, int sd, con
     if (impl < UNET_REG_IMPL_DEFAULT || impl > UNET_REG_IMPL_GLOBAL) return fail("unet_reg_search: unknown impl " + std::to_string(impl));
     if (!scratch) return fail("unet_reg_search: null scratch");
     if (scratch_bytes < reg_scratch_bytes(n_tissues)) return fail("unet_reg_search: scratch too small (see unet_reg_scratch_bytes)");
-    return pp_run(map_out, stream, [&](hipStream_t s) {   // init, step and stages are consumed inside the launcher
+    return run_on_device_of(map_out, stream, [&](hipStream_t s) {   // init, step and stages are consumed inside the launcher
         launch_reg_search(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, init, step, stages, n_stages, max_iterations,
                           map_out, trace, info, impl, scratch, s);
     });
@@ -2447,7 +2489,7 @@ int unet_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, cons
     if (!out) return fail("unet_reg_carry: null out");
     if ((uintptr_t)out & 1) return fail("unet_reg_carry: out must be 2-byte aligned");
     if ((uintptr_t)counts & 3) return fail("unet_reg_carry: counts must be 4-byte aligned");
-    return pp_run(out, stream, [&](hipStream_t s) {   // map is consumed inside the launcher
+    return run_on_device_of(out, stream, [&](hipStream_t s) {   // map is consumed inside the launcher
         launch_reg_carry(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, atlas, n_tissues, map, out, counts, s);
     });
 }
@@ -2457,8 +2499,7 @@ static std::string table_common_error(const std::string& w, int64_t voxels, int 
                                       size_t scratch_bytes) {
     if (voxels >= ((int64_t)1 << 31)) return w + "the grid must stay below 2^31 voxels";
     if (n_labels < 1 || n_labels > UNET_TABLE_MAX_LABELS) return w + "n_labels must be in [1, 65535], got " + std::to_string(n_labels);
-    if (!rows) return w + "null rows";
-    if ((uintptr_t)rows & 7) return w + "rows must be 8-byte aligned";
+    if (std::string e = ptr_error(w, rows, "rows", 8); !e.empty()) return e;
     if (impl < UNET_TABLE_IMPL_DEFAULT || impl > UNET_TABLE_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
     if (!scratch) return w + "null scratch";
     if (scratch_bytes < table_scratch_bytes(n_labels)) return w + "scratch too small (see unet_table_scratch_bytes)";
@@ -2479,7 +2520,7 @@ int unet_table_regions(const void* labels, int label_bytes, int w, int h, int d,
     if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions must be positive");
     const std::string e = table_common_error(who, (int64_t)w * h * d, n_labels, rows, impl, scratch, scratch_bytes);
     if (!e.empty()) return fail(e);
-    return pp_run(labels, stream, [&](hipStream_t s) {
+    return run_on_device_of(labels, stream, [&](hipStream_t s) {
         launch_table_regions(labels, label_bytes, w, h, d, n_labels, rows, impl, scratch, s);
     });
 }
@@ -2493,7 +2534,7 @@ int unet_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, i
     if (voxels <= 0) return fail(who + "voxels must be positive");
     const std::string e = table_common_error(who, voxels, n_labels, rows, impl, scratch, scratch_bytes);
     if (!e.empty()) return fail(e);
-    return pp_run(a, stream, [&](hipStream_t s) {
+    return run_on_device_of(a, stream, [&](hipStream_t s) {
         launch_table_overlap(a, a_bytes, b, b_bytes, voxels, n_labels, rows, impl, scratch, s);
     });
 }
@@ -2503,8 +2544,7 @@ int unet_table_overlap(const void* a, int a_bytes, const void* b, int b_bytes, i
 static std::string stats_common_error(const std::string& w, const void* labels, int label_bytes, const float* image, int64_t voxels,
                                       int n_labels, int max_labels, float lo, float hi, const void* rows, const char* rows_name, int rows_align,
                                       int impl, float* scale) {
-    if (!image) return w + "null image";
-    if ((uintptr_t)image & 3) return w + "image must be 4-byte aligned";
+    if (std::string e = ptr_error(w, image, "image", 4); !e.empty()) return e;
     if (!labels && n_labels != 0) return w + "n_labels must be 0 when labels is null, got " + std::to_string(n_labels);
     if (labels && (n_labels < 1 || n_labels > max_labels))
         return w + "n_labels must be in [1, " + std::to_string(max_labels) + "] when labels is given, got " + std::to_string(n_labels);
@@ -2515,8 +2555,7 @@ static std::string stats_common_error(const std::string& w, const void* labels, 
     const float diff = hi - lo;
     *scale = 65536.0f / diff;
     if (!std::isfinite(diff) || !std::isfinite(*scale) || !(*scale > 0.f)) return w + "the scale 65536 / (hi - lo) must be finite";
-    if (!rows) return w + "null " + rows_name;
-    if ((uintptr_t)rows & (uintptr_t)(rows_align - 1)) return w + rows_name + " must be " + std::to_string(rows_align) + "-byte aligned";
+    if (std::string e = ptr_error(w, rows, rows_name, rows_align); !e.empty()) return e;
     if (impl < UNET_STATS_IMPL_DEFAULT || impl > UNET_STATS_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
     return std::string();
 }
@@ -2542,7 +2581,7 @@ int unet_stats_moments(const void* labels, int label_bytes, const float* image, 
     std::string e = stats_common_error(who, labels, label_bytes, image, voxels, n_labels, UNET_STATS_MAX_LABELS, lo, hi, rows, "rows", 8, impl, &scale);
     if (e.empty()) e = stats_scratch_error(who, scratch, scratch_bytes, n_labels, 0);
     if (!e.empty()) return fail(e);
-    return pp_run(image, stream, [&](hipStream_t s) {
+    return run_on_device_of(image, stream, [&](hipStream_t s) {
         launch_stats_moments(labels, label_bytes, image, voxels, n_labels, lo, hi, scale, rows, impl, scratch, s);
     });
 }
@@ -2554,7 +2593,7 @@ int unet_stats_hist(const void* labels, int label_bytes, const float* image, int
                                        impl, &scale);
     if (e.empty()) e = stats_scratch_error(who, scratch, scratch_bytes, n_labels, 0);
     if (!e.empty()) return fail(e);
-    return pp_run(image, stream, [&](hipStream_t s) {
+    return run_on_device_of(image, stream, [&](hipStream_t s) {
         launch_stats_hist(labels, label_bytes, image, voxels, n_labels, lo, hi, scale, rows, impl, scratch, s);
     });
 }
@@ -2571,7 +2610,7 @@ int unet_stats_quantiles(const void* labels, int label_bytes, const float* image
                                        impl, &scale);
     if (e.empty()) e = stats_scratch_error(who, scratch, scratch_bytes, n_labels, n_quantiles);
     if (!e.empty()) return fail(e);
-    return pp_run(image, stream, [&](hipStream_t s) {   // permille is consumed inside the launcher
+    return run_on_device_of(image, stream, [&](hipStream_t s) {   // permille is consumed inside the launcher
         launch_stats_quantiles(labels, label_bytes, image, voxels, n_labels, lo, hi, scale, permille, n_quantiles, out, impl, scratch, s);
     });
 }
@@ -2609,12 +2648,12 @@ int unet_dist_transform(const void* labels, int label_bytes, int w, int h, int d
     const auto sq = [](int n) { return (unsigned __int128)((uint64_t)(n - 1) * (uint64_t)(n - 1)); };
     if (sq(w) * (unsigned)wx + sq(h) * (unsigned)wy + sq(d) * (unsigned)wz >= (unsigned __int128)UNET_DIST_INF)
         return fail(who + "weights (wx, wy, wz): wx (w-1)^2 + wy (h-1)^2 + wz (d-1)^2 must stay below 2^31 - 1");
-    if (!out) return fail(who + "null out");
-    if ((uintptr_t)out & 3) return fail(who + "out must be 4-byte aligned");
+    e = ptr_error(who, out, "out", 4);
+    if (!e.empty()) return fail(e);
     if (impl < UNET_DIST_IMPL_DEFAULT || impl > UNET_DIST_IMPL_GLOBAL) return fail(who + "unknown impl " + std::to_string(impl));
     if (!scratch) return fail(who + "null scratch");
     if (scratch_bytes < dist_scratch_bytes((int64_t)w * h * d)) return fail(who + "scratch too small (see unet_dist_scratch_bytes)");
-    return pp_run(labels, stream, [&](hipStream_t s) {
+    return run_on_device_of(labels, stream, [&](hipStream_t s) {
         launch_dist_transform(labels, label_bytes, w, h, d, label, of, wx, wy, wz, out, impl, scratch, s);
     });
 }
@@ -2624,72 +2663,70 @@ int unet_dist_surface_counts(const void* a, int a_bytes, const void* b, int b_by
     std::string e = dist_grid_error(who, a, "a", a_bytes, w, h, d);
     if (e.empty()) e = dist_grid_error(who, b, "b", b_bytes, w, h, d);
     if (e.empty()) e = dist_label_error(who, "n_labels", n_labels);
+    if (e.empty()) e = ptr_error(who, rows, "rows", 8);
     if (!e.empty()) return fail(e);
-    if (!rows) return fail(who + "null rows");
-    if ((uintptr_t)rows & 7) return fail(who + "rows must be 8-byte aligned");
-    return pp_run(a, stream, [&](hipStream_t s) { launch_dist_surface_counts(a, a_bytes, b, b_bytes, w, h, d, n_labels, rows, s); });
+    return run_on_device_of(a, stream, [&](hipStream_t s) { launch_dist_surface_counts(a, a_bytes, b, b_bytes, w, h, d, n_labels, rows, s); });
 }
 int unet_dist_gather(const void* at, int at_bytes, int w, int h, int d, int label, const int32_t* dist, int32_t* values, int64_t capacity,
                      unsigned long long* cursor, void* stream) {
     const std::string who = "unet_dist_gather: ";
     std::string e = dist_grid_error(who, at, "at", at_bytes, w, h, d);
     if (e.empty()) e = dist_label_error(who, "label", label);
+    if (e.empty()) e = ptr_error(who, dist, "dist", 4);
+    if (e.empty()) e = ptr_error(who, values, "values", 4);
+    if (e.empty() && capacity < 0) e = who + "capacity must not be negative, got " + std::to_string(capacity);
+    if (e.empty()) e = ptr_error(who, cursor, "cursor", 8);
     if (!e.empty()) return fail(e);
-    if (!dist) return fail(who + "null dist");
-    if ((uintptr_t)dist & 3) return fail(who + "dist must be 4-byte aligned");
-    if (!values) return fail(who + "null values");
-    if ((uintptr_t)values & 3) return fail(who + "values must be 4-byte aligned");
-    if (capacity < 0) return fail(who + "capacity must not be negative, got " + std::to_string(capacity));
-    if (!cursor) return fail(who + "null cursor");
-    if ((uintptr_t)cursor & 7) return fail(who + "cursor must be 8-byte aligned");
-    return pp_run(at, stream, [&](hipStream_t s) { launch_dist_gather(at, at_bytes, w, h, d, label, dist, values, capacity, cursor, s); });
+    return run_on_device_of(at, stream, [&](hipStream_t s) { launch_dist_gather(at, at_bytes, w, h, d, label, dist, values, capacity, cursor, s); });
 }
 
 // ---- the instances of a label map (include/unet_instances.h) ----
-static std::string inst_out_error(const std::string& w, const void* p, const char* name, int align) {
-    if (!p) return w + "null " + name;
-    if ((uintptr_t)p & (uintptr_t)(align - 1)) return w + name + " must be " + std::to_string(align) + "-byte aligned";
-    return std::string();
-}
 static std::string inst_size_error(const std::string& w, int64_t voxels, int n_classes, int64_t max_instances) {
-    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
-    if (n_classes < 1 || n_classes > 65536) return w + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
+    const std::string e = labelling_size_error(w, voxels, n_classes);
+    if (!e.empty()) return e;
     if (max_instances < 0 || max_instances > UNET_INST_MAX_INSTANCES)
         return w + "max_instances must be in [0, 2147483646], got " + std::to_string(max_instances);
     return std::string();
 }
-int unet_inst_scratch_bytes(int64_t voxels, int n_classes, int64_t max_instances, size_t* bytes) {
-    const std::string e = inst_size_error("unet_inst_scratch_bytes: ", voxels, n_classes, max_instances);
+// unet_inst_scratch_bytes and unet_conn_label_scratch_bytes
+static int inst_scratch_query(const std::string& who, int64_t voxels, int n_classes, int64_t max_instances, size_t* bytes) {
+    const std::string e = inst_size_error(who, voxels, n_classes, max_instances);
     if (!e.empty()) return fail(e);
-    if (!bytes) return fail("unet_inst_scratch_bytes: null bytes");
+    if (!bytes) return fail(who + "null bytes");
     *bytes = inst_scratch_bytes(voxels, n_classes, max_instances);
     return 0;
 }
-int unet_inst_label(int w, int h, int d, const uint16_t* label, int n_classes, const uint32_t* listed, int n_listed, int32_t* inst,
-                    int64_t* rows, int64_t max_instances, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
-    const std::string who = "unet_inst_label: ";
+// unet_inst_label (connectivity 6: that check cannot fire) and unet_conn_label; sizes: the scratch-size call the text names
+static int inst_label_call(const std::string& who, const char* sizes, int w, int h, int d, const uint16_t* label, int n_classes,
+                           const uint32_t* listed, int n_listed, int32_t* inst, int64_t* rows, int64_t max_instances, int64_t* info,
+                           int connectivity, int impl, void* scratch, size_t scratch_bytes, void* stream) {
     if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions (w, h, d) must be positive");
     std::string e = inst_size_error(who, (int64_t)w * h * d, n_classes, max_instances);
     if (e.empty() && !label) e = who + "null label";
     if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
     if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
-    if (e.empty()) e = inst_out_error(who, inst, "inst", 4);
-    if (e.empty()) e = inst_out_error(who, rows, "rows", 8);
-    if (e.empty()) e = inst_out_error(who, info, "info", 8);
+    if (e.empty()) e = ptr_error(who, inst, "inst", 4);
+    if (e.empty()) e = ptr_error(who, rows, "rows", 8);
+    if (e.empty()) e = ptr_error(who, info, "info", 8);
+    if (e.empty()) e = conn_error(who, connectivity, impl);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < inst_scratch_bytes((int64_t)w * h * d, n_classes, max_instances))
+        e = who + "scratch too small (see " + sizes + ")";
+    if (e.empty()) e = listed_range_error(who, listed, n_listed, n_classes);
     if (!e.empty()) return fail(e);
-    if (impl < UNET_INST_LABEL_DEFAULT || impl > UNET_INST_LABEL_GLOBAL) return fail(who + "unknown impl " + std::to_string(impl));
-    if (!scratch) return fail(who + "null scratch");
-    if (scratch_bytes < inst_scratch_bytes((int64_t)w * h * d, n_classes, max_instances))
-        return fail(who + "scratch too small (see unet_inst_scratch_bytes)");
-    for (int i = 0; i < n_listed; ++i)
-        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
-            return fail(who + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]");
-    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
-    std::sort(classes.begin(), classes.end());
-    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
-    return pp_run(label, stream, [&](hipStream_t s) {
-        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, 6, scratch, s);
+    const std::vector<uint32_t> classes = listed_classes(listed, n_listed);
+    return run_on_device_of(label, stream, [&](hipStream_t s) {
+        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, connectivity,
+                          scratch, s);
     });
+}
+int unet_inst_scratch_bytes(int64_t voxels, int n_classes, int64_t max_instances, size_t* bytes) {
+    return inst_scratch_query("unet_inst_scratch_bytes: ", voxels, n_classes, max_instances, bytes);
+}
+int unet_inst_label(int w, int h, int d, const uint16_t* label, int n_classes, const uint32_t* listed, int n_listed, int32_t* inst,
+                    int64_t* rows, int64_t max_instances, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    return inst_label_call("unet_inst_label: ", "unet_inst_scratch_bytes", w, h, d, label, n_classes, listed, n_listed, inst, rows,
+                           max_instances, info, 6, impl, scratch, scratch_bytes, stream);
 }
 int unet_inst_match_scratch_bytes(int64_t max_pairs, size_t* bytes) {
     if (max_pairs < 0 || max_pairs > UNET_INST_MAX_PAIRS)
@@ -2701,30 +2738,29 @@ int unet_inst_match_scratch_bytes(int64_t max_pairs, size_t* bytes) {
 int unet_inst_match(const int32_t* ia, const int32_t* ib, int64_t voxels, uint64_t* keys, int64_t* counts, int64_t max_pairs, int64_t* info,
                     int impl, void* scratch, size_t scratch_bytes, void* stream) {
     const std::string who = "unet_inst_match: ";
-    std::string e = inst_out_error(who, ia, "ia", 4);
-    if (e.empty()) e = inst_out_error(who, ib, "ib", 4);
+    std::string e = ptr_error(who, ia, "ia", 4);
+    if (e.empty()) e = ptr_error(who, ib, "ib", 4);
     if (!e.empty()) return fail(e);
     if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail(who + "voxels must be in [1, 2^31), got " + std::to_string(voxels));
     if (max_pairs < 0 || max_pairs > UNET_INST_MAX_PAIRS) return fail(who + "max_pairs must be in [0, 2^30], got " + std::to_string(max_pairs));
     // keys and counts may be null only when they hold nothing
-    if (max_pairs > 0 || keys) e = inst_out_error(who, keys, "keys", 8);
-    if (e.empty() && (max_pairs > 0 || counts)) e = inst_out_error(who, counts, "counts", 8);
-    if (e.empty()) e = inst_out_error(who, info, "info", 8);
+    if (max_pairs > 0 || keys) e = ptr_error(who, keys, "keys", 8);
+    if (e.empty() && (max_pairs > 0 || counts)) e = ptr_error(who, counts, "counts", 8);
+    if (e.empty()) e = ptr_error(who, info, "info", 8);
     if (!e.empty()) return fail(e);
     if (impl < UNET_INST_IMPL_DEFAULT || impl > UNET_INST_IMPL_GLOBAL) return fail(who + "unknown impl " + std::to_string(impl));
     if (!scratch) return fail(who + "null scratch");
     if (scratch_bytes < inst_match_scratch_bytes(max_pairs)) return fail(who + "scratch too small (see unet_inst_match_scratch_bytes)");
-    return pp_run(ia, stream, [&](hipStream_t s) {
+    return run_on_device_of(ia, stream, [&](hipStream_t s) {
         launch_inst_match(ia, ib, voxels, (unsigned long long*)keys, counts, max_pairs, info, impl, scratch, s);
     });
 }
 int unet_inst_remove_small(uint16_t* label, const int32_t* inst, int64_t voxels, const int64_t* rows, int64_t max_instances,
                            int64_t min_voxels, uint32_t* removed, int n_classes, void* stream) {
     const std::string who = "unet_inst_remove_small: ";
-    if (!label) return fail(who + "null label");
-    if ((uintptr_t)label & 1) return fail(who + "label must be 2-byte aligned");
-    std::string e = inst_out_error(who, inst, "inst", 4);
-    if (e.empty()) e = inst_out_error(who, rows, "rows", 8);
+    std::string e = ptr_error(who, label, "label", 2);
+    if (e.empty()) e = ptr_error(who, inst, "inst", 4);
+    if (e.empty()) e = ptr_error(who, rows, "rows", 8);
     if (!e.empty()) return fail(e);
     if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail(who + "voxels must be in [1, 2^31), got " + std::to_string(voxels));
     if (max_instances < 0 || max_instances > UNET_INST_MAX_INSTANCES)
@@ -2733,7 +2769,7 @@ int unet_inst_remove_small(uint16_t* label, const int32_t* inst, int64_t voxels,
         if ((uintptr_t)removed & 3) return fail(who + "removed must be 4-byte aligned");
         if (n_classes < 1 || n_classes > 65536) return fail(who + "n_classes must be in [1, 65536], got " + std::to_string(n_classes));
     }
-    return pp_run(label, stream, [&](hipStream_t s) {
+    return run_on_device_of(label, stream, [&](hipStream_t s) {
         launch_inst_remove_small(label, inst, voxels, rows, max_instances, min_voxels, removed, n_classes, s);
     });
 }
@@ -2744,23 +2780,20 @@ static std::string morph_grid_error(const std::string& w_, int w, int h, int d) 
     if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return w_ + "voxels must be in [1, 2^31), got " + std::to_string((int64_t)w * h * d);
     return std::string();
 }
-static std::string morph_ptr_error(const std::string& w, const void* p, const char* name, int align) {
-    if (!p) return w + "null " + name;
-    if ((uintptr_t)p & (uintptr_t)(align - 1)) return w + name + " must be " + std::to_string(align) + "-byte aligned";
-    return std::string();
-}
 static std::string morph_scratch_error(const std::string& w_, int w, int h, int d, const void* scratch, size_t scratch_bytes) {
     if (!scratch) return w_ + "null scratch";
     if (scratch_bytes < morph_scratch_bytes(w, h, d)) return w_ + "scratch too small (see unet_morph_scratch_bytes)";
     return std::string();
 }
-int unet_morph_scratch_bytes(int w, int h, int d, size_t* bytes) {
-    const std::string e = morph_grid_error("unet_morph_scratch_bytes: ", w, h, d);
+// unet_morph_scratch_bytes and unet_conn_holes_scratch_bytes
+static int morph_scratch_query(const std::string& who, int w, int h, int d, size_t* bytes) {
+    const std::string e = morph_grid_error(who, w, h, d);
     if (!e.empty()) return fail(e);
-    if (!bytes) return fail("unet_morph_scratch_bytes: null bytes");
+    if (!bytes) return fail(who + "null bytes");
     *bytes = morph_scratch_bytes(w, h, d);
     return 0;
 }
+int unet_morph_scratch_bytes(int w, int h, int d, size_t* bytes) { return morph_scratch_query("unet_morph_scratch_bytes: ", w, h, d, bytes); }
 int unet_morph_pack(int w, int h, int d, const void* labels, int label_bytes, int n_classes, const uint32_t* listed, int n_listed,
                     uint64_t* bits, void* scratch, size_t scratch_bytes, void* stream) {
     const std::string who = "unet_morph_pack: ";
@@ -2770,39 +2803,37 @@ int unet_morph_pack(int w, int h, int d, const void* labels, int label_bytes, in
     if (e.empty() && (n_classes < 1 || n_classes > 65536)) e = who + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
     if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
     if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
-    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty()) e = ptr_error(who, bits, "bits", 8);
     if (e.empty()) e = morph_scratch_error(who, w, h, d, scratch, scratch_bytes);
+    if (e.empty()) e = listed_range_error(who, listed, n_listed, n_classes);
     if (!e.empty()) return fail(e);
-    for (int i = 0; i < n_listed; ++i)
-        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
-            return fail(who + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]");
-    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
-    return pp_run(labels, stream, [&](hipStream_t s) {
+    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here, in its order
+    return run_on_device_of(labels, stream, [&](hipStream_t s) {
         launch_morph_pack(w, h, d, labels, label_bytes, n_classes, classes.data(), (int)classes.size(), bits, scratch, s);
     });
 }
 int unet_morph_unpack(int w, int h, int d, const uint64_t* bits, uint8_t* mask, void* stream) {
     const std::string who = "unet_morph_unpack: ";
     std::string e = morph_grid_error(who, w, h, d);
-    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty()) e = ptr_error(who, bits, "bits", 8);
     if (e.empty() && !mask) e = who + "null mask";
     if (!e.empty()) return fail(e);
-    return pp_run(bits, stream, [&](hipStream_t s) { launch_morph_unpack(w, h, d, bits, mask, s); });
+    return run_on_device_of(bits, stream, [&](hipStream_t s) { launch_morph_unpack(w, h, d, bits, mask, s); });
 }
 int unet_morph_count(int w, int h, int d, const uint64_t* bits, int64_t* count, void* stream) {
     const std::string who = "unet_morph_count: ";
     std::string e = morph_grid_error(who, w, h, d);
-    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
-    if (e.empty()) e = morph_ptr_error(who, count, "count", 8);
+    if (e.empty()) e = ptr_error(who, bits, "bits", 8);
+    if (e.empty()) e = ptr_error(who, count, "count", 8);
     if (!e.empty()) return fail(e);
-    return pp_run(bits, stream, [&](hipStream_t s) { launch_morph_count(w, h, d, bits, count, s); });
+    return run_on_device_of(bits, stream, [&](hipStream_t s) { launch_morph_count(w, h, d, bits, count, s); });
 }
 int unet_morph_step(int w, int h, int d, const uint64_t* in, uint64_t* out, int op, int connectivity, int iterations, int border, int impl,
                     void* scratch, size_t scratch_bytes, void* stream) {
     const std::string who = "unet_morph_step: ";
     std::string e = morph_grid_error(who, w, h, d);
-    if (e.empty()) e = morph_ptr_error(who, in, "in", 8);
-    if (e.empty()) e = morph_ptr_error(who, out, "out", 8);
+    if (e.empty()) e = ptr_error(who, in, "in", 8);
+    if (e.empty()) e = ptr_error(who, out, "out", 8);
     if (e.empty() && in == out) e = who + "in and out must not be the same mask";
     if (e.empty() && op != UNET_MORPH_DILATE && op != UNET_MORPH_ERODE) e = who + "unknown op " + std::to_string(op);
     if (e.empty() && connectivity != 6 && connectivity != 18 && connectivity != 26)
@@ -2814,58 +2845,48 @@ int unet_morph_step(int w, int h, int d, const uint64_t* in, uint64_t* out, int 
     if (e.empty()) e = morph_scratch_error(who, w, h, d, scratch, scratch_bytes);
     if (!e.empty()) return fail(e);
     if (impl == UNET_MORPH_IMPL_DEFAULT) impl = UNET_MORPH_IMPL_GLOBAL;   // the faster as measured
-    return pp_run(in, stream, [&](hipStream_t s) {
+    return run_on_device_of(in, stream, [&](hipStream_t s) {
         launch_morph_step(w, h, d, in, out, op, connectivity, iterations, border, impl, scratch, s);
     });
 }
+// unet_morph_holes (connectivity 6: that check cannot fire) and unet_conn_holes; impl is checked as the caller's header gives it,
+// labelling is what the caller mapped it to; sizes: the scratch-size call the text names
+static int holes_call(const std::string& who, const char* sizes, int w, int h, int d, const uint64_t* in, uint64_t* out, int64_t* info,
+                      int connectivity, int impl, int labelling, void* scratch, size_t scratch_bytes, void* stream) {
+    std::string e = morph_grid_error(who, w, h, d);
+    if (e.empty()) e = ptr_error(who, in, "in", 8);
+    if (e.empty()) e = ptr_error(who, out, "out", 8);
+    if (e.empty() && info) e = ptr_error(who, info, "info", 8);
+    if (e.empty()) e = conn_error(who, connectivity, impl);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < morph_scratch_bytes(w, h, d)) e = who + "scratch too small (see " + sizes + ")";
+    if (!e.empty()) return fail(e);
+    return run_on_device_of(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, connectivity, scratch, s); });
+}
 int unet_morph_holes(int w, int h, int d, const uint64_t* in, uint64_t* out, int64_t* info, int impl, void* scratch, size_t scratch_bytes,
                      void* stream) {
-    const std::string who = "unet_morph_holes: ";
-    std::string e = morph_grid_error(who, w, h, d);
-    if (e.empty()) e = morph_ptr_error(who, in, "in", 8);
-    if (e.empty()) e = morph_ptr_error(who, out, "out", 8);
-    if (e.empty() && info) e = morph_ptr_error(who, info, "info", 8);
-    if (e.empty() && (impl < UNET_MORPH_IMPL_DEFAULT || impl > UNET_MORPH_IMPL_GLOBAL)) e = who + "unknown impl " + std::to_string(impl);
-    if (e.empty()) e = morph_scratch_error(who, w, h, d, scratch, scratch_bytes);
-    if (!e.empty()) return fail(e);
     // this header's impls onto the labelling's: the tiled union-find in LDS, or every voxel hooked in global memory
-    const int labelling = impl == UNET_MORPH_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED;
-    return pp_run(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, 6, scratch, s); });
+    return holes_call("unet_morph_holes: ", "unet_morph_scratch_bytes", w, h, d, in, out, info, 6, impl,
+                      impl == UNET_MORPH_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED, scratch, scratch_bytes, stream);
 }
 int unet_morph_apply(int w, int h, int d, uint16_t* labels, const uint64_t* bits, int value, int mode, int64_t* changed, void* stream) {
     const std::string who = "unet_morph_apply: ";
     std::string e = morph_grid_error(who, w, h, d);
-    if (e.empty()) e = morph_ptr_error(who, labels, "labels", 2);
-    if (e.empty()) e = morph_ptr_error(who, bits, "bits", 8);
+    if (e.empty()) e = ptr_error(who, labels, "labels", 2);
+    if (e.empty()) e = ptr_error(who, bits, "bits", 8);
     if (e.empty() && (value < 1 || value > 65535)) e = who + "value must be in [1, 65535], got " + std::to_string(value);
     if (e.empty() && mode != UNET_MORPH_SET && mode != UNET_MORPH_KEEP) e = who + "unknown mode " + std::to_string(mode);
-    if (e.empty() && changed) e = morph_ptr_error(who, changed, "changed", 8);
+    if (e.empty() && changed) e = ptr_error(who, changed, "changed", 8);
     if (!e.empty()) return fail(e);
-    return pp_run(labels, stream, [&](hipStream_t s) { launch_morph_apply(w, h, d, labels, bits, value, mode, changed, s); });
+    return run_on_device_of(labels, stream, [&](hipStream_t s) { launch_morph_apply(w, h, d, labels, bits, value, mode, changed, s); });
 }
 
 // ---- connected components with a chosen connectivity (include/unet_connectivity.h) ----
-// the siblings of the keep-largest, instance labelling and hole filling calls above with a connectivity of 6, 18 or 26; the impl
+// keep-largest, instance labelling and hole filling with a connectivity of 6, 18 or 26: each call runs the one body of its operation
+// above (keep_largest_call, inst_label_call, holes_call) under its own name, as its sibling does with a connectivity of 6; the impl
 // values are those of the labelling stage (DEFAULT and TILED: the tile's union-find in LDS, GLOBAL: every voxel in global memory)
-static std::string conn_error(const std::string& w, int connectivity, int impl) {
-    if (connectivity != UNET_CONN_6 && connectivity != UNET_CONN_18 && connectivity != UNET_CONN_26)
-        return w + "connectivity must be 6, 18 or 26, got " + std::to_string(connectivity);
-    if (impl < UNET_CONN_IMPL_DEFAULT || impl > UNET_CONN_IMPL_GLOBAL) return w + "unknown impl " + std::to_string(impl);
-    return std::string();
-}
-static std::string conn_size_error(const std::string& w, int64_t voxels, int n_classes) {
-    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
-    if (n_classes < 1 || n_classes > 65536) return w + "n_classes must be in [1, 65536], got " + std::to_string(n_classes);
-    return std::string();
-}
-static std::string conn_list_error(const std::string& w, const uint32_t* listed, int n_listed, int n_classes) {
-    for (int i = 0; i < n_listed; ++i)
-        if (listed[i] == 0 || listed[i] >= (uint32_t)n_classes)
-            return w + "listed class " + std::to_string(listed[i]) + " is not in [1, " + std::to_string(n_classes - 1) + "]";
-    return std::string();
-}
 int unet_conn_scratch_bytes(int64_t voxels, int n_classes, size_t* bytes) {
-    const std::string e = conn_size_error("unet_conn_scratch_bytes: ", voxels, n_classes);
+    const std::string e = labelling_size_error("unet_conn_scratch_bytes: ", voxels, n_classes);
     if (!e.empty()) return fail(e);
     if (!bytes) return fail("unet_conn_scratch_bytes: null bytes");
     *bytes = components_scratch_bytes(voxels, n_classes);
@@ -2875,7 +2896,7 @@ int unet_conn_keep_largest(int w, int h, int d, uint16_t* label, int n_classes, 
                            int connectivity, int impl, void* scratch, size_t scratch_bytes, void* stream) {
     const std::string who = "unet_conn_keep_largest: ";
     if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions (w, h, d) must be positive");
-    std::string e = conn_size_error(who, (int64_t)w * h * d, n_classes);
+    std::string e = labelling_size_error(who, (int64_t)w * h * d, n_classes);
     if (e.empty() && !label) e = who + "null label";
     if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
     if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
@@ -2883,68 +2904,25 @@ int unet_conn_keep_largest(int w, int h, int d, uint16_t* label, int n_classes, 
     if (e.empty() && !scratch) e = who + "null scratch";
     if (e.empty() && scratch_bytes < components_scratch_bytes((int64_t)w * h * d, n_classes))
         e = who + "scratch too small (see unet_conn_scratch_bytes)";
-    if (e.empty()) e = conn_list_error(who, listed, n_listed, n_classes);
     if (!e.empty()) return fail(e);
-    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
-    std::sort(classes.begin(), classes.end());
-    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
-    return pp_run(label, stream, [&](hipStream_t s) {
-        launch_components_keep_largest(w, h, d, label, n_classes, classes.data(), (int)classes.size(), removed, impl, connectivity, scratch, s);
-    });
+    return keep_largest_call(who, w, h, d, label, n_classes, listed, n_listed, removed, connectivity, impl, scratch, stream);
 }
 int unet_conn_label_scratch_bytes(int64_t voxels, int n_classes, int64_t max_instances, size_t* bytes) {
-    const std::string e = inst_size_error("unet_conn_label_scratch_bytes: ", voxels, n_classes, max_instances);
-    if (!e.empty()) return fail(e);
-    if (!bytes) return fail("unet_conn_label_scratch_bytes: null bytes");
-    *bytes = inst_scratch_bytes(voxels, n_classes, max_instances);
-    return 0;
+    return inst_scratch_query("unet_conn_label_scratch_bytes: ", voxels, n_classes, max_instances, bytes);
 }
 int unet_conn_label(int w, int h, int d, const uint16_t* label, int n_classes, const uint32_t* listed, int n_listed, int32_t* inst,
                     int64_t* rows, int64_t max_instances, int64_t* info, int connectivity, int impl, void* scratch, size_t scratch_bytes,
                     void* stream) {
-    const std::string who = "unet_conn_label: ";
-    if (w <= 0 || h <= 0 || d <= 0) return fail(who + "dimensions (w, h, d) must be positive");
-    std::string e = inst_size_error(who, (int64_t)w * h * d, n_classes, max_instances);
-    if (e.empty() && !label) e = who + "null label";
-    if (e.empty() && n_listed < 0) e = who + "n_listed must not be negative, got " + std::to_string(n_listed);
-    if (e.empty() && n_listed > 0 && !listed) e = who + "null listed";
-    if (e.empty()) e = inst_out_error(who, inst, "inst", 4);
-    if (e.empty()) e = inst_out_error(who, rows, "rows", 8);
-    if (e.empty()) e = inst_out_error(who, info, "info", 8);
-    if (e.empty()) e = conn_error(who, connectivity, impl);
-    if (e.empty() && !scratch) e = who + "null scratch";
-    if (e.empty() && scratch_bytes < inst_scratch_bytes((int64_t)w * h * d, n_classes, max_instances))
-        e = who + "scratch too small (see unet_conn_label_scratch_bytes)";
-    if (e.empty()) e = conn_list_error(who, listed, n_listed, n_classes);
-    if (!e.empty()) return fail(e);
-    std::vector<uint32_t> classes(listed, listed + n_listed);   // the caller's list is consumed here
-    std::sort(classes.begin(), classes.end());
-    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
-    return pp_run(label, stream, [&](hipStream_t s) {
-        launch_inst_label(w, h, d, label, n_classes, classes.data(), (int)classes.size(), inst, rows, max_instances, info, impl, connectivity,
-                          scratch, s);
-    });
+    return inst_label_call("unet_conn_label: ", "unet_conn_label_scratch_bytes", w, h, d, label, n_classes, listed, n_listed, inst, rows,
+                           max_instances, info, connectivity, impl, scratch, scratch_bytes, stream);
 }
 int unet_conn_holes_scratch_bytes(int w, int h, int d, size_t* bytes) {
-    const std::string e = morph_grid_error("unet_conn_holes_scratch_bytes: ", w, h, d);
-    if (!e.empty()) return fail(e);
-    if (!bytes) return fail("unet_conn_holes_scratch_bytes: null bytes");
-    *bytes = morph_scratch_bytes(w, h, d);
-    return 0;
+    return morph_scratch_query("unet_conn_holes_scratch_bytes: ", w, h, d, bytes);
 }
 int unet_conn_holes(int w, int h, int d, const uint64_t* in, uint64_t* out, int64_t* info, int connectivity, int impl, void* scratch,
                     size_t scratch_bytes, void* stream) {
-    const std::string who = "unet_conn_holes: ";
-    std::string e = morph_grid_error(who, w, h, d);
-    if (e.empty()) e = morph_ptr_error(who, in, "in", 8);
-    if (e.empty()) e = morph_ptr_error(who, out, "out", 8);
-    if (e.empty() && info) e = morph_ptr_error(who, info, "info", 8);
-    if (e.empty()) e = conn_error(who, connectivity, impl);
-    if (e.empty() && !scratch) e = who + "null scratch";
-    if (e.empty() && scratch_bytes < morph_scratch_bytes(w, h, d)) e = who + "scratch too small (see unet_conn_holes_scratch_bytes)";
-    if (!e.empty()) return fail(e);
-    const int labelling = impl == UNET_CONN_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED;
-    return pp_run(in, stream, [&](hipStream_t s) { launch_morph_holes(w, h, d, in, out, info, labelling, connectivity, scratch, s); });
+    return holes_call("unet_conn_holes: ", "unet_conn_holes_scratch_bytes", w, h, d, in, out, info, connectivity, impl,
+                      impl == UNET_CONN_IMPL_GLOBAL ? UNET_COMPONENTS_IMPL_GLOBAL : UNET_COMPONENTS_IMPL_TILED, scratch, scratch_bytes, stream);
 }
 
 }  // extern "C"

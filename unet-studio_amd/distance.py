@@ -76,9 +76,7 @@ def metric(voxel_size, dims):
 def distance_scratch_bytes(dims):
     """dims = (W, H, D): one int32 per voxel between the passes"""
     w, h, d = (int(v) for v in dims)
-    n = C.c_size_t()
-    E.check(E.lib.unet_dist_scratch_bytes(w, h, d, C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_dist_scratch_bytes, w, h, d)
 
 
 def _map(t, name, who, like=None):

@@ -149,6 +149,28 @@ def ptr_array(ptrs):
     return arr
 
 
+def size_query(fn, *args):
+    """what a `*_bytes(..., size_t* bytes)` call of the C ABI writes; its refusal of the arguments raises"""
+    n = C.c_size_t()
+    check(fn(*args, C.byref(n)))
+    return n.value
+
+
+def u32_array(values):
+    """host uint32 array of the values (one unused entry when there are none)"""
+    return (C.c_uint32 * max(1, len(values)))(*values)
+
+
+def listed_classes(who, classes, n_classes):
+    """the listed classes of a call as a list of ints, None for 1..n_classes-1; one that no uint32 holds raises under `who` (the
+    library refuses 0 and the values from n_classes on)"""
+    classes = list(range(1, int(n_classes))) if classes is None else [int(v) for v in classes]
+    for v in classes:
+        if not 0 <= v < 1 << 32:
+            raise UNetError("%s: listed class %d is not in [1, %d]" % (who, v, int(n_classes) - 1))
+    return classes
+
+
 class Plan:
     """unet_plan: architecture DSL bound to one input size, element type and device."""
 
@@ -184,11 +206,8 @@ class Plan:
         for l in range(n.value):
             check(lib.unet_plan_output_shape(self.handle, l, dims))
             self.output_shapes.append(tuple(dims[k] for k in range(5)))
-        b = C.c_size_t()
-        check(lib.unet_plan_workspace_bytes(self.handle, C.byref(b)))
-        self.workspace_bytes = b.value
-        check(lib.unet_loss_scratch_bytes(self.handle, C.byref(b)))
-        self.loss_scratch_bytes = b.value
+        self.workspace_bytes = size_query(lib.unet_plan_workspace_bytes, self.handle)
+        self.loss_scratch_bytes = size_query(lib.unet_loss_scratch_bytes, self.handle)
         f, g = C.c_double(), C.c_double()
         check(lib.unet_plan_flops(self.handle, C.byref(f), C.byref(g)))
         self.flops_fwd, self.flops_bwd = f.value, g.value

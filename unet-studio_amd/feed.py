@@ -38,9 +38,7 @@ EXPORTS = ["unet_feed_scratch_bytes", "unet_feed_label_max", "unet_feed_prepare"
 
 # ---- the device calls ----------------------------------------------------------------------------------------------------------
 def feed_scratch_bytes(voxels):
-    n = C.c_size_t()
-    E.check(E.lib.unet_feed_scratch_bytes(int(voxels), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_feed_scratch_bytes, int(voxels))
 
 
 def _f32(a, name):
@@ -213,9 +211,8 @@ class TrainingFeed:
                 prepare(lab, t1w, normalize=not self.is_label, shift_by=shift, scratch=self._scratch("feed", feed_scratch_bytes(S)))
         # simulate_modality (train.cpp:459-462), seed = seed_id as an unsigned int
         r = G.sim_to_struct(G.make_simulate_recipe((W, H, D), self.model.out_count if is_template else None, index))
-        n = C.c_size_t()
-        E.check(E.lib.unet_simulate_modality_scratch_bytes(C.byref(r), C.byref(n)))
-        G.simulate(r, t1w, lab.view(-1) if is_template else None, self._scratch("sim", n.value))
+        need = E.size_query(E.lib.unet_simulate_modality_scratch_bytes, C.byref(r))
+        G.simulate(r, t1w, lab.view(-1) if is_template else None, self._scratch("sim", need))
         # visual_perception_augmentation(param.options, ..., param.is_label, model->dim, seed_id) (train.cpp:472)
         a = G.to_struct(G.make_recipe(self.options, (W, H, D), self.model.in_count, self.is_label, index, label_depth=D))
         G.augment(a, x.view(-1), lab.view(-1), self._scratch("aug", G.scratch_bytes(a)))

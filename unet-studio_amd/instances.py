@@ -8,15 +8,16 @@
 
 The reference stops at voxel counts (evaluate.cpp, qc.cpp), so these are this project's definitions (parity NOT pinned).  Every
 device value is an integer: the device is pinned to the numpy restatements of tests/test_instances_host.py bit for bit.
-label(connectivity=18 | 26) and lesion_scores(connectivity=...) go through connectivity.py (include/unet_connectivity.h).  Out of
+label is the one body of the labelling: with connectivity 18 or 26 (lesion_scores(connectivity=...) too), and for
+connectivity.label, it runs unet_conn_label (include/unet_connectivity.h).  Out of
 scope: an optimal one-to-one assignment between instances, and wiring either call into EvaluateUNet or the post-processing chain."""
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import connectivity as CN
 from . import engine as E
+from .components import check_connectivity
 from .engine import UNetError
 
 E._sig("unet_inst_scratch_bytes", C.c_int, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_size_t))
@@ -26,6 +27,9 @@ E._sig("unet_inst_match_scratch_bytes", C.c_int, C.c_int64, C.POINTER(C.c_size_t
 E._sig("unet_inst_match", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
        C.c_size_t, C.c_void_p)
 E._sig("unet_inst_remove_small", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p)
+E._sig("unet_conn_label_scratch_bytes", C.c_int, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_size_t))
+E._sig("unet_conn_label", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_void_p, C.c_void_p,
+       C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 # every symbol include/unet_instances.h declares
 EXPORTS = ["unet_inst_scratch_bytes", "unet_inst_label", "unet_inst_match_scratch_bytes", "unet_inst_match", "unet_inst_remove_small"]
 
@@ -42,15 +46,16 @@ KEY_UNUSED = (1 << 63) - 1                           # above every pair (ia < 2^
 
 
 def inst_scratch_bytes(voxels, n_classes, max_instances):
-    n = C.c_size_t()
-    E.check(E.lib.unet_inst_scratch_bytes(int(voxels), int(n_classes), int(max_instances), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_inst_scratch_bytes, int(voxels), int(n_classes), int(max_instances))
+
+
+def conn_label_scratch_bytes(voxels, n_classes, max_instances):
+    """unet_conn_label_scratch_bytes (connectivity.label_scratch_bytes): the same size under the newer header's name"""
+    return E.size_query(E.lib.unet_conn_label_scratch_bytes, int(voxels), int(n_classes), int(max_instances))
 
 
 def match_scratch_bytes(max_pairs):
-    n = C.c_size_t()
-    E.check(E.lib.unet_inst_match_scratch_bytes(int(max_pairs), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_inst_match_scratch_bytes, int(max_pairs))
 
 
 def _out(t, n, dtype, dev, who, name):
@@ -69,32 +74,30 @@ def _label_map(labels, who):
 
 
 def label(labels, n_classes, classes=None, max_instances=DEFAULT_MAX_INSTANCES, impl=LABEL_DEFAULT, scratch=None, out=None, stream=None,
-          connectivity=6):
+          connectivity=6, _who=None):
     """unet_inst_label on the current stream (or the raw `stream`).  labels: a (D, H, W) uint16 device tensor (uint8 is cast).
     classes: the listed classes, None for 1..n_classes-1.  Returns (inst, rows, info) on the device: inst int32 (D, H, W), 0 or the
     dense id of the voxel's 6-connected component; rows int64 {max_instances + 1, 12}: class, voxels, sums of x, y, z, minima, maxima,
     smallest linear index (row 0 and the rows above N are empty: 0, 0, 0, 0, 0, (W, H, D), -1, -1, -1, -1); info int64[2] = (N,
     min(N, max_instances)).  out: (inst, rows, info) to write into.  No host synchronisation.  connectivity: 6 (this header's
-    call), 18 or 26 (connectivity.label: the same outputs, scratch size and impl values)."""
-    if CN.check(connectivity, "instances.label") != 6:
-        return CN.label(labels, n_classes, classes, connectivity, max_instances, impl=impl, scratch=scratch, out=out, stream=stream)
+    call), 18 or 26 (unet_conn_label: the same outputs, scratch size and impl values).  _who: connectivity.label's message prefix;
+    with it unet_conn_label runs at 6 too."""
+    c = check_connectivity(connectivity, _who or "instances.label")
+    conn = _who is not None or c != 6                             # which header's calls, and whose name the listed classes' message carries
     lab = _label_map(labels, "label")
     D, H, W = (int(v) for v in lab.shape)
     nc, M = int(n_classes), int(max_instances)
-    need = inst_scratch_bytes(D * H * W, nc, M)                     # the range checks, before any device work
-    classes = list(range(1, nc)) if classes is None else [int(v) for v in classes]
-    for v in classes:
-        if not 0 <= v < 1 << 32:
-            raise UNetError("instances.label: listed class %d is not in [1, %d]" % (v, nc - 1))
+    need = (conn_label_scratch_bytes if conn else inst_scratch_bytes)(D * H * W, nc, M)   # the range checks, before any device work
+    classes = E.listed_classes("connectivity.label" if conn else "instances.label", classes, nc)
     dev = lab.device
     o = out if out is not None else (None, None, None)
     inst = _out(o[0], D * H * W, torch.int32, dev, "label", "inst")
     rows = _out(o[1], (M + 1) * COLUMNS, torch.int64, dev, "label", "rows")
     info = _out(o[2], 2, torch.int64, dev, "label", "info")
     scratch = E.scratch(scratch, need, dev)
-    arr = (C.c_uint32 * max(1, len(classes)))(*classes)
-    E.check(E.lib.unet_inst_label(W, H, D, lab.data_ptr(), nc, arr, len(classes), inst.data_ptr(), rows.data_ptr(), M, info.data_ptr(),
-                                  int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(lab, stream)))
+    head = (W, H, D, lab.data_ptr(), nc, E.u32_array(classes), len(classes), inst.data_ptr(), rows.data_ptr(), M, info.data_ptr())
+    tail = (int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(lab, stream))
+    E.check(E.lib.unet_conn_label(*head, c, *tail) if conn else E.lib.unet_inst_label(*head, *tail))
     return inst.view(D, H, W), rows.view(M + 1, COLUMNS), info
 
 
@@ -259,7 +262,7 @@ def lesion_scores(pred, ref, n_classes, classes=None, rule="any", threshold=0.0,
     """`detection` of a predicted label map against a reference one, both (D, H, W) uint8 / uint16 device tensors of one shape: two
     `label` calls, one `match`, then the host arithmetic.  Returns detection's dict.  connectivity: 6, 18 or 26, what joins the
     voxels of one lesion in both maps (26 is what lesion-wise scores in the literature count)."""
-    CN.check(connectivity, "instances.lesion_scores")
+    check_connectivity(connectivity, "instances.lesion_scores")
     if not (torch.is_tensor(pred) and torch.is_tensor(ref) and tuple(pred.shape) == tuple(ref.shape)):
         raise UNetError("instances.lesion_scores: pred and ref must be device tensors of one shape")
     inst_r, rows_r = _label_all(ref, n_classes, classes, max_instances, impl, scratch, connectivity)

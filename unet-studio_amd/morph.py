@@ -6,7 +6,8 @@
                              border 1 a closing never removes a voxel and an opening never adds one
   fill_holes                 the 6-connected components of the complement that touch no face of the volume are set
                              (scipy.ndimage.binary_fill_holes with its default structure), through the exact labelling of components.py;
-                             connectivity=18 | 26 chooses the background's connectivity through connectivity.py
+                             connectivity=18 | 26 chooses the background's connectivity (unet_conn_holes of
+                             include/unet_connectivity.h, from the same body; connectivity.fill_holes is that body too)
   dilate_label, erode_label, open_label, close_label, fill_holes_label     the same on one value of a uint16 label map, in place
   run                        a list of such ops on a label map; postproc.run_postproc(morphology=...) and EvaluateUNet(morphology=...)
                              run it on the `label` output after single_component
@@ -19,8 +20,8 @@ import ctypes as C
 
 import torch
 
-from . import connectivity as CN
 from . import engine as E
+from .components import check_connectivity
 from .engine import UNetError
 
 _I, _P = C.c_int, C.c_void_p
@@ -31,6 +32,8 @@ E._sig("unet_morph_count", _I, _I, _I, _I, _P, _P, _P)
 E._sig("unet_morph_step", _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P)
 E._sig("unet_morph_holes", _I, _I, _I, _I, _P, _P, _P, _I, _P, C.c_size_t, _P)
 E._sig("unet_morph_apply", _I, _I, _I, _I, _P, _P, _I, _I, _P, _P)
+E._sig("unet_conn_holes_scratch_bytes", _I, _I, _I, _I, C.POINTER(C.c_size_t))
+E._sig("unet_conn_holes", _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, C.c_size_t, _P)
 # every symbol include/unet_morph.h declares
 EXPORTS = ["unet_morph_scratch_bytes", "unet_morph_pack", "unet_morph_unpack", "unet_morph_count", "unet_morph_step", "unet_morph_holes",
            "unet_morph_apply"]
@@ -63,9 +66,13 @@ class Mask:
 def morph_scratch_bytes(shape):
     """unet_morph_scratch_bytes for a (D, H, W) grid: one size serves every call"""
     D, H, W = (int(v) for v in shape)
-    n = C.c_size_t()
-    E.check(E.lib.unet_morph_scratch_bytes(W, H, D, C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_morph_scratch_bytes, W, H, D)
+
+
+def conn_holes_scratch_bytes(shape):
+    """unet_conn_holes_scratch_bytes for a (D, H, W) grid (connectivity.holes_scratch_bytes): the same size under the newer header's name"""
+    D, H, W = (int(v) for v in shape)
+    return E.size_query(E.lib.unet_conn_holes_scratch_bytes, W, H, D)
 
 
 def _scratch(scratch, shape, dev):
@@ -114,17 +121,13 @@ def pack(labels, n_classes, classes=None, scratch=None, out=None):
     lab = _label_map(labels, "pack")
     D, H, W = (int(v) for v in lab.shape)
     nc = int(n_classes)
-    classes = list(range(1, nc)) if classes is None else [int(v) for v in classes]
-    for v in classes:
-        if not 0 <= v < 1 << 32:
-            raise UNetError("morph.pack: listed class %d is not in [1, %d]" % (v, nc - 1))
+    classes = E.listed_classes("morph.pack", classes, nc)
     dev = lab.device
     scratch = _scratch(scratch, (D, H, W), dev)
     m = out if out is not None else Mask(torch.empty((D, H, (W + 63) // 64), dtype=torch.int64, device=dev), (D, H, W))
     if _mask(m, "pack", "out").shape != (D, H, W) or m.bits.device != dev:
         raise UNetError("morph.pack: out must be a Mask of shape %s on labels' device" % ((D, H, W),))
-    arr = (C.c_uint32 * max(1, len(classes)))(*classes)
-    E.check(E.lib.unet_morph_pack(W, H, D, lab.data_ptr(), lab.element_size(), nc, arr, len(classes), m.bits.data_ptr(),
+    E.check(E.lib.unet_morph_pack(W, H, D, lab.data_ptr(), lab.element_size(), nc, E.u32_array(classes), len(classes), m.bits.data_ptr(),
                                   scratch.data_ptr(), scratch.nbytes, E.stream(lab)))
     return m
 
@@ -176,18 +179,19 @@ def close(m, connectivity=6, iterations=1, impl=IMPL_DEFAULT, scratch=None):
     return erode(dilate(m, connectivity, iterations, impl, scratch), connectivity, iterations, impl, scratch, border=1)
 
 
-def fill_holes(m, impl=IMPL_DEFAULT, scratch=None, out=None, connectivity=6):
+def fill_holes(m, impl=IMPL_DEFAULT, scratch=None, out=None, connectivity=6, _who=None):
     """unet_morph_holes: (Mask, info); info a device int64[2] tensor: the voxels filled, the holes.  out may be m.  connectivity: the
-    background's, 6 (this header's call), 18 or 26 (connectivity.fill_holes: the same scratch size and impl values)"""
-    _mask(m, "fill_holes")
-    if CN.check(connectivity, "morph.fill_holes") != 6:
-        return CN.fill_holes(m, connectivity, impl=impl, scratch=scratch, out=out)
+    background's, 6 (this header's call), 18 or 26 (unet_conn_holes: the same scratch size and impl values).  _who:
+    connectivity.fill_holes' message prefix; with it unet_conn_holes runs at 6 too."""
     D, H, W = _mask(m, "fill_holes").shape
+    c = check_connectivity(connectivity, _who or "morph.fill_holes")
+    conn = _who is not None or c != 6                             # which header's calls
     out = _out_mask(out, m, "fill_holes")
-    scratch = _scratch(scratch, m.shape, m.bits.device)
+    scratch = E.scratch(scratch, (conn_holes_scratch_bytes if conn else morph_scratch_bytes)(m.shape), m.bits.device)
     info = torch.empty(2, dtype=torch.int64, device=m.bits.device)
-    E.check(E.lib.unet_morph_holes(W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), info.data_ptr(), int(impl), scratch.data_ptr(), scratch.nbytes,
-                                   E.stream(m.bits)))
+    head = (W, H, D, m.bits.data_ptr(), out.bits.data_ptr(), info.data_ptr())
+    tail = (int(impl), scratch.data_ptr(), scratch.nbytes, E.stream(m.bits))
+    E.check(E.lib.unet_conn_holes(*head, c, *tail) if conn else E.lib.unet_morph_holes(*head, *tail))
     return out, info
 
 
@@ -256,7 +260,7 @@ def open_label(labels, value, connectivity=6, iterations=1, impl=IMPL_DEFAULT, s
 def fill_holes_label(labels, classes, value, n_classes, impl=IMPL_DEFAULT, scratch=None, changed=None, connectivity=6):
     """the holes of the voxels of the listed classes: a hole voxel that reads 0 becomes value; one that holds an unlisted class is
     left alone.  connectivity: the background's, 6, 18 or 26"""
-    CN.check(connectivity, "morph.fill_holes_label")
+    check_connectivity(connectivity, "morph.fill_holes_label")
     lab = _label_map(labels, "fill_holes_label", (torch.uint16,))
     v = _value(value, "fill_holes_label")
     scratch = _scratch(scratch, lab.shape, lab.device)

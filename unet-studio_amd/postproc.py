@@ -133,9 +133,7 @@ def needs_scratch(steps):
 
 
 def postproc_scratch_bytes(out_c, voxels):
-    n = C.c_size_t()
-    E.check(E.lib.unet_postproc_scratch_bytes(int(out_c), int(voxels), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_postproc_scratch_bytes, int(out_c), int(voxels))
 
 
 def _ptr(t):

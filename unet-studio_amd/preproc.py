@@ -130,9 +130,7 @@ def orientation_map(steps, model_dim, model_vs):
 
 # ---- the device calls ------------------------------------------------------------------------------------------------------------
 def preproc_scratch_bytes(values):
-    n = C.c_size_t()
-    E.check(E.lib.unet_preproc_scratch_bytes(int(values), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_preproc_scratch_bytes, int(values))
 
 
 def _vol(a, name):

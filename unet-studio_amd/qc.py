@@ -52,9 +52,7 @@ class QcStat:
 
 # ---- the device half ----------------------------------------------------------------------------------------------------------
 def qc_scratch_bytes(out_c, voxels, collapse_before=0):
-    n = C.c_size_t()
-    E.check(E.lib.unet_qc_scratch_bytes(int(out_c), int(voxels), int(collapse_before), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_qc_scratch_bytes, int(out_c), int(voxels), int(collapse_before))
 
 
 def _device_f32(a, name, device=None):

@@ -37,9 +37,7 @@ DEFAULT_STAGES = [(4, 0, 2), (2, 1, 4), (1, 2, 6)]
 
 
 def reg_scratch_bytes(subject_voxels, n_tissues, max_iterations=1):
-    n = C.c_size_t()
-    E.check(E.lib.unet_reg_scratch_bytes(int(subject_voxels), int(n_tissues), int(max_iterations), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_reg_scratch_bytes, int(subject_voxels), int(n_tissues), int(max_iterations))
 
 
 def centre_init(subject_shape, subject_vs, template_shape, template_vs):

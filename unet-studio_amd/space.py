@@ -123,9 +123,7 @@ def _map_struct(map):
 
 # ---- the device calls ------------------------------------------------------------------------------------------------------------
 def space_scratch_bytes(dst_voxels, channels):
-    n = C.c_size_t()
-    E.check(E.lib.unet_space_scratch_bytes(int(dst_voxels), int(channels), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_space_scratch_bytes, int(dst_voxels), int(channels))
 
 
 def _f32(a, name):

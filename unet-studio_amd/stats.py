@@ -41,9 +41,7 @@ N, NAN, BELOW, ABOVE, SUM_Q, SUM_QQ, MIN_Q, MAX_Q, MIN_KEY, MAX_KEY = range(10)
 
 def stats_scratch_bytes(voxels, n_labels, n_quantiles=0):
     """One size for the three calls (n_quantiles 0 for moments and hist): the running tables, nothing per voxel."""
-    n = C.c_size_t()
-    E.check(E.lib.unet_stats_scratch_bytes(int(voxels), int(n_labels), int(n_quantiles), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_stats_scratch_bytes, int(voxels), int(n_labels), int(n_quantiles))
 
 
 def _inputs(labels, image, n_labels, who):

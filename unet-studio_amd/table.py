@@ -34,9 +34,7 @@ COUNT, SUM_X, SUM_Y, SUM_Z, MIN_X, MIN_Y, MIN_Z, MAX_X, MAX_Y, MAX_Z = range(10)
 
 def table_scratch_bytes(voxels, n_labels):
     """One size for both calls: the running table, nothing per voxel."""
-    n = C.c_size_t()
-    E.check(E.lib.unet_table_scratch_bytes(int(voxels), int(n_labels), C.byref(n)))
-    return n.value
+    return E.size_query(E.lib.unet_table_scratch_bytes, int(voxels), int(n_labels))
 
 
 def _map(t, name, who, dev=None):
