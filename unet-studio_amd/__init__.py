@@ -13,6 +13,7 @@ from .space import NativeVolume, model_to_image_map, to_model_space  # noqa: F40
 from . import tiles  # noqa: F401  (the module: tiles.EXPORTS the symbols of include/unet_tiles.h)
 from .tiles import canvas_dims, plan_tiles  # noqa: F401
 from . import mirror  # noqa: F401  (the module: mirror.EXPORTS the symbols of include/unet_mirror.h)
+from . import ensemble  # noqa: F401  (the module: ensemble.EXPORTS the symbols of include/unet_ensemble.h)
 from .evaluate import EvaluateUNet  # noqa: F401
 from .augment import AugmentedVolumes, PrefetchedVolumes, visual_perception_augmentation  # noqa: F401
 from . import nz  # noqa: F401

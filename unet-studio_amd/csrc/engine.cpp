@@ -2234,6 +2234,48 @@ int unet_mirror_postproc(const float* stack, int out_c, int w, int h, int d, int
     });
 }
 
+// ---- the model ensemble: members' probabilities folded into a running state, then read out (include/unet_ensemble.h) ----
+static std::string ens_args_error(const char* who, int out_c, int64_t voxels) {
+    const std::string e = std::string(who) + ": ";
+    if (out_c < 2) return e + "out_c must be at least 2 (channel 0 is the background)";
+    if (out_c > 65536) return e + "more than 65535 foreground classes do not fit a uint16 label";
+    if (voxels <= 0) return e + "voxels must be positive";
+    if (voxels >= ((int64_t)1 << 31)) return e + "a volume must stay below 2^31 voxels";
+    return std::string();
+}
+int unet_ens_state_bytes(int out_c, int64_t voxels, size_t* bytes) {
+    const std::string e = ens_args_error("unet_ens_state_bytes", out_c, voxels);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_ens_state_bytes: null output");
+    *bytes = ens_state_bytes(out_c, voxels);
+    return 0;
+}
+int unet_ens_accumulate(const float* logits, int out_c, int64_t voxels, float weight, int first, void* state, size_t state_bytes,
+                        void* stream) {
+    const std::string e = ens_args_error("unet_ens_accumulate", out_c, voxels);
+    if (!e.empty()) return fail(e);
+    if (!logits) return fail("unet_ens_accumulate: null logits");
+    if (!state) return fail("unet_ens_accumulate: null state");
+    if (!(weight > 0.f && weight <= 1.f)) return fail("unet_ens_accumulate: weight must be finite and in (0, 1] (the weights are normalised)");
+    if (state_bytes < ens_state_bytes(out_c, voxels)) return fail("unet_ens_accumulate: state too small (see unet_ens_state_bytes)");
+    if ((uintptr_t)logits % 4 || (uintptr_t)state % 4) return fail("unet_ens_accumulate: logits and state must be 4-byte aligned");
+    return run_on_device_of(logits, stream, [&](hipStream_t s) {
+        launch_ens_accumulate(logits, out_c, voxels, weight, first != 0, (float*)state, s);
+    });
+}
+int unet_ens_finalize(const void* state, size_t state_bytes, int out_c, int64_t voxels, float threshold, float* label_prob,
+                      float* fg_prob, uint16_t* label, float* entropy, float* mutual_info, void* stream) {
+    const std::string e = ens_args_error("unet_ens_finalize", out_c, voxels);
+    if (!e.empty()) return fail(e);
+    if (!state) return fail("unet_ens_finalize: null state");
+    if (state_bytes < ens_state_bytes(out_c, voxels)) return fail("unet_ens_finalize: state too small (see unet_ens_state_bytes)");
+    if ((uintptr_t)state % 4) return fail("unet_ens_finalize: state must be 4-byte aligned");
+    if (!label_prob && !fg_prob && !label && !entropy && !mutual_info) return fail("unet_ens_finalize: no output wanted");
+    return run_on_device_of(state, stream, [&](hipStream_t s) {
+        launch_ens_finalize((const float*)state, out_c, voxels, threshold, label_prob, fg_prob, label, entropy, mutual_info, s);
+    });
+}
+
 // ---- the pre-processing commands of a model (include/unet_preproc.h) ----
 static const char* preproc_volume_error(const void* src, const void* dst, int w, int h, int d, int channels) {
     if (!src || !dst) return "unet_preproc: null device pointer";

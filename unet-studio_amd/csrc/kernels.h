@@ -10,6 +10,7 @@
 #include "../../include/unet_components.h"
 #include "../../include/unet_connectivity.h"
 #include "../../include/unet_distance.h"
+#include "../../include/unet_ensemble.h"
 #include "../../include/unet_feed.h"
 #include "../../include/unet_hip.h"
 #include "../../include/unet_instances.h"
@@ -390,6 +391,13 @@ void launch_mirror_combine(const float* stack, int C, int W, int H, int D, int n
 void launch_mirror_postproc(const float* stack, int C, int W, int H, int D, int n_members, const int* masks, int swap_axis,
                             const int* pairs, int n_pairs, float thr, float* lp, float* fg, uint16_t* lab, uint8_t* agreement,
                             hipStream_t s);
+
+// kernels_ensemble.hip: one member's probabilities folded into the running state, and the closing pass (include/unet_ensemble.h);
+// the arguments are checked by the caller
+size_t ens_state_bytes(int C, int64_t S);
+void launch_ens_accumulate(const float* logits, int C, int64_t S, float w, int first, float* state, hipStream_t s);
+void launch_ens_finalize(const float* state, int C, int64_t S, float thr, float* lp, float* fg, uint16_t* lab, float* ent, float* mi,
+                         hipStream_t s);
 
 // kernels_preproc.hip: the pre-processing commands of a model (include/unet_preproc.h); w, h, d are the source's dimensions
 int64_t preproc_filter_blocks(int w, int h, int d, int channels);

@@ -65,7 +65,22 @@ create_mask / argmax group combines the logits it reads, and `outputs` may then 
 of the K members voted for the mean's top class (with it, from 4 members on, the mean is stored once: that measured faster).  A NativeVolume, a run without a chain and every tile take the mean logits
 (one gather pass) and then today's path unchanged; "agreement" is refused for a NativeVolume and under tiles.  The member stack
 costs K * out_count * voxels * 4 bytes on the device (8 members of 6 x 128^3: 403 MB), is reused across volumes, and the time is K
-forwards per window (the filter packs are reused from the second on)."""
+forwards per window (the filter packs are reused from the second on).
+
+With `ensemble` (a list of further models; `self.model` is member 0) every volume is run through each member in order and the
+members' softmax probabilities are averaged per voxel (ensemble.py, include/unet_ensemble.h; the definitions are this project's).
+All members must share in_count, out_count, dim and voxel_size; the "model" options (postproc, preproc, orientation, fov_strategy,
+single_component) are member 0's.  `ensemble_weights` (one positive number per member, member 0 first; None: equal) are normalised
+to sum to 1.  Each member's logits are made exactly as the paths above make them on the grid the chain runs on -- the forward, the
+mirrored members' mean with `mirror_axes`, the blended canvas under tiles, the linear resample onto a NativeVolume's grid -- and
+folded into one state of (out_count + 2) * voxels * 4 bytes that is reused across volumes and does not grow with the number of
+members; the chain then starts from that state (its leading softmax / create_mask / argmax group reads the mean probabilities;
+softmax may not recur later), and single_component, morphology and the atlas stage follow unchanged.  `outputs` may then also name
+"entropy" and "mutual_info", float32 (d, h, w), for plain arrays, NativeVolumes and tiles alike: the entropy of the mean prediction
+in nats (the members disagree, or every member is unsure) and that entropy minus the members' mean entropy (the members disagree).
+"entropy" without further models runs the same path with one member; "mutual_info" needs more than one; both need a chain;
+"agreement" is refused with either.  The time is one forward (K with mirroring, one per tile) per member.  With `ensemble=None`
+and neither output wanted nothing changes."""
 import collections
 
 import numpy as np
@@ -74,6 +89,7 @@ import torch
 from . import components as CMP
 from . import connectivity as CN
 from . import engine as E
+from . import ensemble as EN
 from . import mirror as MR
 from . import morph as MO
 from . import postproc as P
@@ -85,7 +101,8 @@ from . import tiles as TL
 
 
 # what _check hands the loop: the parsed options of one start()
-_Checked = collections.namedtuple("_Checked", "steps chain_outputs staged masks swap pre ori ori_map listed cmp_conn tiled overlap ops atl")
+_Checked = collections.namedtuple("_Checked", "steps chain_outputs staged masks swap pre ori ori_map listed cmp_conn tiled overlap ops atl "
+                                             "members weights uncertainty")
 # one entry past the input stage: x on the device ({1, in_count, d, h, w}; {in_count, cd, ch, cw} with a plan), the map `back` from a
 # voxel of a NativeVolume's grid `native` (d, h, w) to the grid the forward runs on (None for a plain array), the tile plan and canvas
 # (w, h, d) when it runs in more than one tile, and `size`, the entry's own grid (d, h, w), where its results land
@@ -94,11 +111,13 @@ _Entry = collections.namedtuple("_Entry", "x back native plan canvas size")
 
 class _Run:
     """What one start() carries from volume to volume: the uint8 scratch buffers by stage (normalize's reduction, the chain's, the
-    component labelling's, the morphology's, the region table's), the volume sizes whose filter packs this run has already made
-    (the weights are frozen), and the mirrored members' logits, reused across windows and volumes."""
+    component labelling's, the morphology's, the region table's, the ensemble's state), per model of the ensemble the volume sizes
+    whose filter packs this run has already made (the weights are frozen; the packs are the model's), and the mirrored members'
+    logits, reused across windows and volumes."""
 
-    def __init__(self, device):
-        self.device, self.buffers, self.packed_sizes, self.member_stack = device, {}, set(), None
+    def __init__(self, device, n_models=1):
+        self.device, self.buffers, self.member_stack = device, {}, None
+        self.packed_sizes = [set() for _ in range(n_models)]
 
     def scratch(self, stage, need):
         buf = self.buffers[stage] = E.scratch(self.buffers.get(stage), need, self.device)
@@ -123,8 +142,10 @@ def _land(out, pending):
 class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
                  single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None, morphology=None,
-                 single_component_connectivity=6, mirror_axes=None, mirror_swap=None):
+                 single_component_connectivity=6, mirror_axes=None, mirror_swap=None, ensemble=None, ensemble_weights=None):
         self.model = model
+        self.ensemble = ensemble               # a list of further models (self.model is member 0), None: one model
+        self.ensemble_weights = ensemble_weights   # one positive weight per member, member 0 first; None: equal
         self.postproc = postproc
         self.preproc = preproc                 # a chain string, "model" for model.preproc, None / "": no pre-processing
         self.orientation = orientation         # a flip / swap chain, "model" for model.orientation, None / "": none
@@ -161,21 +182,27 @@ class EvaluateUNet:
             except E.UNetError as e:
                 self.error_msg, self.aborted, self.running = str(e), True, False
                 return out
-            run = _Run(self.device)
+            for member in cfg.members[1:]:                 # each member once; member 0 above
+                member.prepare_for_inference(self.device)
+            run = _Run(self.device, len(cfg.members))
             with torch.no_grad():                          # evaluate.cpp:221
                 while self.cur_prog < len(out) and not self.aborted:
                     self.status = "inferencing"
                     for i, io in enumerate(out[self.cur_prog]):
                         entry = self._input(cfg, run, io)
-                        result, stack, members, size = self._forward(cfg, run, entry.x, entry.plan,
-                                                                     fused=entry.native is None and cfg.steps is not None)
+                        state = result = stack = members = size = None
+                        if cfg.weights is not None:                # every member's probabilities folded into one state
+                            state = self._ensemble_state(cfg, run, entry)
+                        else:
+                            result, stack, members, size = self._forward(cfg, run, entry.x, entry.plan,
+                                                                         fused=entry.native is None and cfg.steps is not None)
                         extra = {}
                         if cfg.steps is not None:
-                            results = self._chain(cfg, run, entry, result, stack, members, size)
+                            results = self._chain(cfg, run, entry, result, stack, members, size, state)
                             if cfg.atl is not None and cfg.staged:
                                 extra = self._atlas_stage(cfg, run, io, entry, results)
                             h, w = entry.size[1:]
-                            results = {k: (v, (v.numel() // (h * w), h, w) if k in P.OUTPUTS or k in ("atlas", "agreement") else tuple(v.shape))
+                            results = {k: (v, (v.numel() // (h * w), h, w) if k in EN.OUTPUTS or k in ("atlas", "agreement") else tuple(v.shape))
                                        for k, v in results.items() if k in self.outputs or k == "tissue_hist"}
                         else:
                             if entry.native is not None:                                 # handle_fov_post alone: the logits on the native grid
@@ -200,7 +227,9 @@ class EvaluateUNet:
         chain = m.postproc if self.postproc == "model" else self.postproc
         staged = tuple(o for o in self.outputs if o in ("atlas", "regions"))              # the atlas stage's outputs
         want_agr = "agreement" in self.outputs                                            # the mirror stage's output
-        chain_outputs = tuple(o for o in self.outputs if o not in staged and o != "agreement")
+        uncertainty = tuple(o for o in self.outputs if o in EN.UNCERTAINTY)               # the ensemble's outputs
+        chain_outputs = tuple(o for o in self.outputs if o not in staged and o != "agreement" and o not in uncertainty)
+        members, weights = self._check_ensemble(chain, uncertainty, want_agr)
         masks = MR.parse_axes(self.mirror_axes)
         mirrored = len(masks) > 1
         swap = None
@@ -225,6 +254,8 @@ class EvaluateUNet:
             steps = P.parse_chain(chain, self.params)
             P.check_chain(steps)
             P.check_outputs(steps, chain_outputs)
+            if weights is not None:
+                P.check_ensemble_chain(steps)
             if atl is not None and not isinstance(atl, REG.Atlas):
                 raise E.UNetError("atlas must be a register.Atlas")
         # run_preproc / handle_orientation's failure (evaluate.cpp:201-204)
@@ -245,7 +276,37 @@ class EvaluateUNet:
         ops = MO.check_ops(self.morphology, m.out_count) if self.morphology else []
         if steps is None or "label" not in chain_outputs:  # both act on the label output only
             listed, ops = [], []
-        return _Checked(steps, chain_outputs, staged, masks, swap, pre, ori, ori_map, listed, cmp_conn, tiled, overlap, ops, atl)
+        return _Checked(steps, chain_outputs, staged, masks, swap, pre, ori, ori_map, listed, cmp_conn, tiled, overlap, ops, atl,
+                        members, weights, uncertainty)
+
+    def _check_ensemble(self, chain, uncertainty, want_agr):
+        """The ensemble's options: ([member 0, further models ...], the normalised weights).  The weights are None when this run
+        takes the one-model paths: no further model and neither entropy nor mutual_info wanted."""
+        m = self.model
+        further = self.ensemble if self.ensemble is not None else []
+        if not isinstance(further, (list, tuple)):
+            raise E.UNetError("ensemble must be a list of further models, got %r" % (further,))
+        members = [m] + list(further)
+        for k, other in enumerate(members[1:], 1):
+            for what in ("in_count", "out_count", "dim", "voxel_size"):
+                if not hasattr(other, what):
+                    raise E.UNetError("ensemble: member %d is not a model (it has no %s)" % (k, what))
+                a, b = getattr(other, what), getattr(m, what)
+                a, b = (tuple(a), tuple(b)) if what in ("dim", "voxel_size") else (a, b)
+                if a != b:
+                    raise E.UNetError("ensemble: member %d has %s %s, member 0 has %s" % (k, what, a, b))
+        if len(members) == 1 and not uncertainty:
+            if self.ensemble_weights is not None:
+                raise E.UNetError("ensemble_weights needs ensemble")
+            return members, None
+        weights = EN.normalize_weights(self.ensemble_weights, len(members))
+        if "mutual_info" in uncertainty and len(members) == 1:
+            raise E.UNetError("output mutual_info needs more than one member (ensemble)")
+        if want_agr:
+            raise E.UNetError("output agreement is not available with ensemble (it counts one model's mirrored views)")
+        if not chain:
+            raise E.UNetError("%s needs a postproc chain" % ("output " + uncertainty[0] if uncertainty else "ensemble"))
+        return members, weights
 
     def _input(self, cfg, run, io):
         """one entry of model_io -> _Entry: the input on the device, the way back and the grids"""
@@ -317,18 +378,19 @@ class EvaluateUNet:
             scratch = run.scratch("preproc", PRE.preproc_scratch_bytes(self.model.in_count * pdims[0] * pdims[1] * pdims[2]))
         return PRE.run_preproc(x, cfg.pre, scratch=scratch)
 
-    def _forward_mirrored(self, cfg, run, x1):
-        """x1 {1, in_count, d, h, w} on the device -> the stack {K, out_count, d, h, w} of the members' level-0 logits"""
-        m = self.model
+    def _forward_mirrored(self, cfg, run, x1, k=0):
+        """x1 {1, in_count, d, h, w} on the device -> the stack {K, out_count, d, h, w} of the mirrored members' level-0 logits
+        from model k of the ensemble"""
+        m = cfg.members[k]
         need = MR.stack_bytes(cfg.masks, m.out_count, x1[0, 0].numel()) // 4
         if run.member_stack is None or run.member_stack.numel() < need:
             run.member_stack = torch.empty(need, dtype=torch.float32, device=self.device)
-        return MR.forward_members(m, x1[0], cfg.masks, run.packed_sizes, out=run.member_stack)
+        return MR.forward_members(m, x1[0], cfg.masks, run.packed_sizes[k], out=run.member_stack)
 
-    def _forward_tiles(self, cfg, run, xc, plan):
+    def _forward_tiles(self, cfg, run, xc, plan, k=0):
         """xc {in_count, cd, ch, cw} on the device -> the stack {tiles, out_count, D, H, W} of level-0 logits, one forward
-        per integer crop in tile-index order"""
-        m = self.model
+        of model k of the ensemble per integer crop in tile-index order"""
+        m = cfg.members[k]
         mW, mH, mD = (int(v) for v in m.dim)
         origins = TL.tile_origins(plan)
         stack = torch.empty((len(origins), m.out_count, mD, mH, mW), dtype=torch.float32, device=self.device)
@@ -336,42 +398,60 @@ class EvaluateUNet:
             crop = xc[:, oz:oz + mD, oy:oy + mH, ox:ox + mW].contiguous().unsqueeze(0)
             size = tuple(crop.shape[2:])
             if len(cfg.masks) > 1:                         # the members' mean, straight into the tile's slot
-                MR.combine(self._forward_mirrored(cfg, run, crop), cfg.masks, cfg.swap, out={"mean": stack[t]})
+                MR.combine(self._forward_mirrored(cfg, run, crop, k), cfg.masks, cfg.swap, out={"mean": stack[t]})
                 continue
-            stack[t].copy_(m.forward(crop, packs_current=size in run.packed_sizes)[0].view(m.out_count, mD, mH, mW))
-            run.packed_sizes.add(size)
+            stack[t].copy_(m.forward(crop, packs_current=size in run.packed_sizes[k])[0].view(m.out_count, mD, mH, mW))
+            run.packed_sizes[k].add(size)
         return stack
 
-    def _forward(self, cfg, run, x, plan, fused):
-        """The input on the device -> (result, stack, members, size): the logits on the grid `size` the forward ran on, or, when the
-        chain's leading group reads them itself (fused), the tile stack or the mirrored members' stack in their place."""
+    def _forward(self, cfg, run, x, plan, fused, k=0):
+        """The input on the device -> (result, stack, members, size): model k's logits on the grid `size` the forward ran on, or,
+        when the chain's leading group reads them itself (fused), the tile stack or the mirrored members' stack in their place."""
         size = tuple(x.shape[-3:])
         result = stack = members = None
         if plan is not None:                               # one forward per tile (evaluate.cpp:223-230)
-            stack = self._forward_tiles(cfg, run, x, plan)
+            stack = self._forward_tiles(cfg, run, x, plan, k)
             if not fused:                                  # the canvas logits, as if the model's grid were the canvas
                 result, stack = TL.blend(stack, plan, size), None
         elif len(cfg.masks) > 1:                           # one forward per member
-            members = self._forward_mirrored(cfg, run, x)
+            members = self._forward_mirrored(cfg, run, x, k)
             if not fused:                                  # the mean logits, then today's path
                 result, members = MR.combine(members, cfg.masks, cfg.swap)[0], None
         else:
-            result = self.model.forward(x, packs_current=size in run.packed_sizes)[0]     # evaluate.cpp:226-227
-            run.packed_sizes.add(size)
+            result = cfg.members[k].forward(x, packs_current=size in run.packed_sizes[k])[0]     # evaluate.cpp:226-227
+            run.packed_sizes[k].add(size)
         return result, stack, members, size
 
-    def _chain(self, cfg, run, entry, result, stack, members, size):
-        """run_postproc on the grid the results come back on (evaluate.cpp:274), on the compute stream: {output: device tensor}"""
+    def _ensemble_state(self, cfg, run, entry):
+        """Every member's logits, made as the one-model paths make them on the grid the chain runs on (the forward, the mirrored
+        members' mean, the blended canvas, the linear resample onto a NativeVolume's grid), folded in member order into the run's
+        one state, which is returned"""
+        out_c = self.model.out_count
+        d, h, w = entry.size
+        state = run.scratch("ensemble", EN.state_bytes(out_c, d * h * w))
+        for k, weight in enumerate(cfg.weights):
+            logits, _, _, size = self._forward(cfg, run, entry.x, entry.plan, fused=False, k=k)
+            logits = logits.view(out_c, *size)
+            if entry.native is not None:                                                 # handle_fov_post: onto the scan's grid
+                logits = SP.resample(logits, entry.native, entry.back, "linear")
+            EN.accumulate(logits, state, weight, k == 0)
+        return state
+
+    def _chain(self, cfg, run, entry, result, stack, members, size, state=None):
+        """run_postproc on the grid the results come back on (evaluate.cpp:274), on the compute stream: {output: device tensor}.
+        state: the ensemble's, already on that grid, in place of everything a one-model run reads"""
         m = self.model
         d, h, w = entry.size
         voxels = d * h * w if entry.native is not None or entry.plan is not None or result is None else result.numel() // m.out_count
         want_agr = "agreement" in self.outputs
         return P.run_postproc(
-            result if stack is None else None, cfg.steps, outputs=cfg.chain_outputs + (("agreement",) if want_agr else ()),
+            result if stack is None else None, cfg.steps,
+            outputs=cfg.chain_outputs + (("agreement",) if want_agr else ()) + (cfg.uncertainty if state is not None else ()),
             scratch=run.scratch("chain", P.postproc_scratch_bytes(m.out_count, voxels)) if P.needs_scratch(cfg.steps) else None,
             mirror=None if members is None else (members, cfg.masks, cfg.swap),
-            native=None if entry.native is None else (entry.back, entry.native),
+            native=None if entry.native is None or state is not None else (entry.back, entry.native),
             tiles=None if stack is None else (stack, entry.plan, size),
+            ensemble=None if state is None else (state, m.out_count, entry.size),
             single_component=cfg.listed or None, single_component_connectivity=cfg.cmp_conn,
             component_scratch=run.scratch("components", CMP.components_scratch_bytes(voxels, m.out_count)) if cfg.listed else None,
             morphology=cfg.ops or None,

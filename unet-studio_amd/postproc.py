@@ -244,9 +244,47 @@ def _mirror_source(mirror, logits, native, want_agr):
                   lambda: MR.combine(stack, masks, swap, want_mean=False, want_agreement=True)[1])
 
 
+def check_ensemble_chain(steps):
+    """An accumulated ensemble has probabilities, no logits: only the softmax / create_mask / argmax group that starts the chain
+    may read it; raises UNetError.  Host only."""
+    group = ("softmax", "create_mask", "argmax")
+    if not steps or steps[0][0] not in group:
+        raise UNetError("with ensemble the chain must start with its softmax / create_mask / argmax group")
+    j = 0
+    while j < len(steps) and steps[j][0] in group:
+        j += 1
+    if any(n == "softmax" for n, _ in steps[j:]):
+        raise UNetError("with ensemble softmax may not recur after %s (an accumulated ensemble has no logits)" % steps[j][0])
+
+
+def _ensemble_source(ensemble, logits, native, tiles, mirror, steps, uncertainty):
+    from . import ensemble as EN
+    from . import space as SP
+    if logits is not None or native is not None or tiles is not None or mirror is not None:
+        raise UNetError("run_postproc: ensemble comes in place of logits and does not combine with native, tiles or mirror "
+                        "(apply those per member before accumulating)")
+    try:
+        state, out_c, shape = ensemble
+    except (TypeError, ValueError):
+        raise UNetError("run_postproc: ensemble must be (state, out_c, (d, h, w)), got %r" % (ensemble,))
+    out_c = int(out_c)
+    D, H, W = SP._shape3(shape, "ensemble shape")
+    check_ensemble_chain(steps)
+    EN._state(state, out_c, D * H * W)
+
+    def no_logits():
+        raise UNetError("run_postproc: an accumulated ensemble has no logits")
+
+    def head(thr, wanted):
+        extra = {o: torch.empty((D, H, W), dtype=torch.float32, device=state.device) for o in uncertainty}
+        EN.finalize(state, out_c, (D, H, W), thr, tuple(wanted) + tuple(extra), out={**wanted, **extra})
+        return extra
+    return Source(out_c, (D, H, W), state.device, head, no_logits, None)
+
+
 def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, native=None, single_component=None,
                  component_scratch=None, tiles=None, morphology=None, morphology_scratch=None, single_component_connectivity=6,
-                 mirror=None):
+                 mirror=None, ensemble=None):
     """Runs the chain on one volume's logits ({1, C, D, H, W} or {C, D, H, W}, contiguous fp32 device tensor) on the current stream.
     chain: a string (parse_chain) or parsed steps.  Returns {output: device tensor} for the wanted outputs the chain produces.
     scratch: a uint8 device tensor of at least postproc_scratch_bytes(C, D*H*W) bytes to reuse (one is made when needed).
@@ -268,20 +306,33 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
     logits (mirror.py, include/unet_mirror.h).  A fused group that starts the chain combines the logits it reads and never stores
     them (mirror.postproc_mirror), except when agreement is wanted from MIRROR_PAIR_FROM members on, where the stored mean measured
     faster; a later group reads the mean logits, made once when first needed.  Not with tiles or native.
-    Only with mirror may `outputs` name "agreement", the uint8 {D, H, W} map of how many members voted for the mean's top class."""
+    Only with mirror may `outputs` name "agreement", the uint8 {D, H, W} map of how many members voted for the mean's top class.
+    ensemble: (state, out_c, (D, H, W)) in place of logits (pass None): the volume is an accumulated ensemble of several models'
+    probabilities (ensemble.py, include/unet_ensemble.h).  The chain must start with its softmax / create_mask / argmax group, which
+    is ensemble.finalize into the wanted planes; an accumulated ensemble has no logits, so softmax may not recur after a command
+    that changed the state (a later lone argmax reads the current planes as ever).  Not with native, tiles or mirror: the caller
+    applies those per member before accumulating.  Only with ensemble may `outputs` name "entropy" and "mutual_info", float32
+    {D, H, W}; "agreement" is refused with it."""
     steps = parse_chain(chain, params) if isinstance(chain, str) else list(chain)
     check_chain(steps)
     outputs = tuple(outputs)
     want_agr = "agreement" in outputs                  # not a chain output (OUTPUTS): the mirror call produces it
+    if want_agr and ensemble is not None:
+        raise UNetError("output agreement is not available with ensemble (it counts one model's mirrored views)")
     if want_agr and mirror is None:
         raise UNetError("output agreement needs mirror")
-    outputs = tuple(o for o in outputs if o != "agreement")
+    uncertainty = tuple(o for o in outputs if o in ("entropy", "mutual_info"))   # not chain outputs: the ensemble's finalize makes them
+    if uncertainty and ensemble is None:
+        raise UNetError("output %s needs ensemble" % uncertainty[0])
+    outputs = tuple(o for o in outputs if o != "agreement" and o not in uncertainty)
     check_outputs(steps, outputs)
     from . import connectivity as CN
     CN.check(single_component_connectivity, "single_component")   # refused before any device work
     if tiles is not None and mirror is not None:
         raise UNetError("run_postproc: mirror does not combine with tiles or native")
-    if tiles is not None:
+    if ensemble is not None:
+        src = _ensemble_source(ensemble, logits, native, tiles, mirror, steps, uncertainty)
+    elif tiles is not None:
         src = _tile_source(tiles, logits, native)
     elif mirror is not None:
         src = _mirror_source(mirror, logits, native, want_agr)
@@ -358,6 +409,11 @@ def run_postproc(logits, chain, params=None, outputs=OUTPUTS, scratch=None, nati
         res["agreement"] = src.agreement()
     if want_agr:
         outputs += ("agreement",)
+    missing = tuple(o for o in uncertainty if o not in res)
+    if missing:                                        # the leading group had nothing to write: the maps alone
+        from . import ensemble as EN
+        res.update(EN.finalize(ensemble[0], out_c, (D, H, W), 0.5, missing))
+    outputs += uncertainty
     if listed and "label" in outputs:
         from . import components as CMP
         CMP.keep_largest(res["label"], listed, out_c, scratch=component_scratch, connectivity=single_component_connectivity)
