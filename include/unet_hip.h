@@ -192,6 +192,13 @@ int unet_sgd_step_packed(const unet_plan* plan, float* params_flat, float* grads
  * in the element type of `dtype`; weights/bias/grads fp32 in torch layout ([Cout,Cin,k,k,k]; conv_trans
  * [Cin,Cout,2,2,2]).  impl: UNET_IMPL_*.  scratch: at least unet_op_scratch_bytes() bytes. ---- */
 int unet_op_scratch_bytes(int cin, int cout, int D, int H, int W, size_t* bytes);
+/* Which kernel family each direction of a conv (transposed = 0) or conv_trans (transposed = 1; ks and stride ignored) of this
+ * shape runs on in the entry points below, for one plain source: out = {forward, dgrad, wgrad}.  Read-only, launches nothing.
+ * forward: 0 split-K deep-level kernel (falls back to 1 where its launcher declines), 1 bf16 MFMA, 2 head (plans only),
+ *          3 first-conv MFMA, 4 first-conv fp32 MFMA, 5 fp32 MFMA, 6 direct
+ * dgrad:   0 bf16 MFMA, 1 fp32 MFMA, 2 direct
+ * wgrad:   0 first-conv MFMA, 1 bf16 MFMA, 2 fp32 MFMA, 3 register-accumulating small kernels, 4 direct */
+int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]);
 int unet_op_conv3d_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D,
                        int H, int W, int ks, int stride, void* scratch, void* stream);
 /* conv3d with the read-side fusion of the engine: the input is seen as act(x*scale[c]+shift[c]) (scale/shift fp32 [cin] or

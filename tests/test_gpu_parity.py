@@ -14,6 +14,10 @@ import unet_studio_amd as U  # noqa: E402
 from oracle import aten_ref as A  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
+import conv_cases as CC  # noqa: E402
+# outputs are NaN-filled views between guard bands (Guarded) and the scratch is 0xFF bytes (NaN in bf16 and in fp32): see tests/gpu_exact.py
+from gpu_exact import Guarded, check_all, poisoned_scratch as scratch  # noqa: E402
+
 E = U.engine
 DEV = "cuda:0"
 TOL = {"fp32": 1e-4, "bf16": 4e-2}
@@ -39,12 +43,6 @@ def from_cl(t):  # device [D,H,W,C] -> numpy [C,D,H,W] fp32
     return np.ascontiguousarray(np.transpose(t.float().cpu().numpy(), (3, 0, 1, 2)))
 
 
-def scratch(cin, cout, D=1, H=1, W=1):
-    b = C.c_size_t()
-    E.check(E.lib.unet_op_scratch_bytes(cin, cout, D, H, W, C.byref(b)))
-    return torch.empty(b.value, dtype=torch.uint8, device=DEV)
-
-
 def rnd(shape, seed, scale=1.0):
     return (np.random.default_rng(seed).standard_normal(shape) * scale).astype(np.float32)
 
@@ -53,49 +51,8 @@ def q(x, dt):  # what the engine sees after rounding its input to the element ty
     return x if dt == "fp32" else torch.from_numpy(x).to(torch.bfloat16).float().numpy()
 
 
-CONV_CASES = [  # cin, cout, (D,H,W), ks, stride
-    (1, 16, (9, 10, 12), 3, 1), (16, 16, (8, 8, 16), 3, 1), (5, 7, (6, 7, 9), 3, 1), (16, 32, (8, 10, 12), 3, 2),
-    (3, 4, (7, 9, 11), 3, 2), (16, 6, (5, 6, 7), 1, 1), (32, 16, (4, 8, 16), 3, 1), (24, 40, (5, 5, 6), 3, 1),
-    # MFMA-eligible shapes: every tile configuration (W >= 12, 5..11, <= 4), both channel-chunk widths, NT 1/2/4, ragged edges
-    (32, 32, (9, 7, 20), 3, 1), (64, 64, (6, 9, 8), 3, 1), (48, 16, (5, 6, 4), 3, 1), (16, 48, (12, 12, 13), 3, 1),
-    (128, 64, (4, 4, 4), 3, 1), (16, 16, (3, 5, 7), 3, 1), (32, 16, (16, 16, 32), 3, 1),
-    # stride-2 MFMA wgrad: every tile configuration (Wo >= 12, 5..11, <= 4), PJ 1/2/4, odd input sizes
-    (16, 32, (12, 16, 32), 3, 2), (32, 64, (9, 11, 13), 3, 2), (64, 16, (8, 8, 8), 3, 2), (16, 16, (5, 7, 25), 3, 2),
-    # output-stationary wgrad that adds straight into the gradient (tile side 4^3 / 8^3: no slab, no reduce): stride 2 with an 8^3
-    # output from an even and from an odd input (4 tiles along z per block), stride 1 at 8^3 with several (ca, cb) pairs
-    (32, 32, (16, 16, 16), 3, 2), (16, 32, (15, 15, 15), 3, 2), (48, 32, (8, 8, 8), 3, 1),
-    # stride-2 forward with 32-channel chunks (outputs of 8^3 voxels or fewer): eight and four chunks, both tiles, several row tiles
-    (256, 64, (8, 8, 8), 3, 2), (128, 48, (16, 16, 16), 3, 2), (96, 32, (13, 12, 15), 3, 2),
-    # register-accumulating small wgrads: first conv (Cin = 1; W % 4 != 0 falls back to the row kernel) and 1x1x1 heads
-    (1, 8, (6, 5, 8), 3, 1), (1, 16, (5, 6, 7), 3, 1), (1, 32, (17, 9, 16), 3, 1), (64, 6, (4, 5, 6), 1, 1), (256, 6, (3, 4, 5), 1, 1),
-    (32, 3, (5, 6, 7), 1, 1), (16, 8, (33, 8, 9), 1, 1),
-    # small-volume MFMA kernel: 8 chunks (two per wave, fragment refill), 16 chunks (two super-stages), 4^3 tile
-    (256, 16, (8, 8, 8), 3, 1), (512, 32, (5, 6, 7), 3, 1), (256, 32, (4, 4, 4), 3, 1), (96, 32, (3, 4, 10), 3, 1),
-    # sliding-window MFMA wgrad (bf16, stride 1, W >= 24): every (ca-tiles, cb-tiles) pairing 1x1 / 2x1 / 1x2 / 2x2, several pair
-    # groups per launch, ragged footprints in y and x, z segments of unequal length, volumes narrower than one 32-voxel row
-    (16, 16, (9, 11, 37), 3, 1), (32, 16, (13, 9, 33), 3, 1), (16, 32, (5, 12, 40), 3, 1), (32, 32, (6, 9, 40), 3, 1),
-    (64, 32, (8, 8, 24), 3, 1), (48, 16, (4, 10, 70), 3, 1), (16, 16, (40, 8, 32), 3, 1), (32, 64, (11, 5, 29), 3, 1),
-    # ... above 32^3 voxels (at or below, the kernel uses single pairs): the 2x2, 2x1 and 1x2 pair blocks
-    (32, 32, (20, 40, 48), 3, 1), (32, 16, (24, 30, 48), 3, 1), (16, 32, (18, 40, 48), 3, 1),
-    # sliding window for a single 16-channel chunk (bf16; forward Cin = 16, dgrad Cout = 16; W >= 12, D >= 8): one and two row tiles,
-    # ragged footprints, z segments of unequal length
-    (16, 16, (11, 9, 19), 3, 1), (16, 32, (10, 17, 33), 3, 1), (32, 16, (9, 10, 18), 3, 1), (16, 16, (37, 8, 16), 3, 1),
-    # stride-2 sliding-window kernels (kernels_mfma_s2.hip; bf16, output >= 16 wide, >= 4 deep): forward with 16- and 32-channel planes and
-    # 1 / 2 / 4 row tiles per block, dgrad with 32 and 64 dy channels and 1..3 row-tile blocks, odd input sizes (last fine plane / row /
-    # voxel without a partner), ragged footprints, z segments of unequal length; Cin 48 / Cout 16 fall back to the halo-tile kernel
-    (16, 32, (16, 20, 40), 3, 2), (32, 64, (9, 13, 35), 3, 2), (16, 16, (8, 8, 32), 3, 2), (32, 48, (11, 10, 33), 3, 2),
-    (16, 64, (12, 9, 38), 3, 2), (48, 32, (8, 12, 32), 3, 2), (32, 32, (37, 7, 31), 3, 2),
-    # ... and their sliding-window weight gradient (kernels_mfma_s2_wgrad.hip; output >= 24 wide): (ca, cb) pairings 1x2 / 2x2 / 2x1, several
-    # pair groups, ragged 32-voxel K-steps, odd input sizes, z segments of unequal length
-    (16, 32, (9, 12, 64), 3, 2), (32, 32, (12, 9, 50), 3, 2), (32, 16, (8, 8, 48), 3, 2), (16, 64, (21, 7, 70), 3, 2),
-    # split-K kernels of the deep levels (kernels_mfma_deep.hip; bf16, Cin % 32 == 0): 27-tap kinds at <= 64 output voxels (ragged
-    # last 64-voxel group, one- and two-voxel extents, K splits of 8..32, one and two row tiles per block), stride 2 from odd extents,
-    # and their dgrads (stride-2 dgrad up to a 512-voxel coarse grid)
-    (64, 48, (3, 4, 5), 3, 1), (128, 32, (2, 2, 2), 3, 1), (512, 64, (1, 2, 3), 3, 1), (32, 128, (4, 4, 3), 3, 1),
-    (32, 64, (7, 6, 5), 3, 2), (128, 128, (8, 8, 8), 3, 2), (64, 32, (3, 2, 2), 3, 2), (32, 32, (13, 15, 16), 3, 2),
-    # fp32 matrix-core conv (fp32 engine, volumes >= 4096 voxels): NT 1 / 2, ragged tile edges in z, y and x, 8-channel chunk tail
-    (16, 16, (16, 16, 32), 3, 1), (32, 64, (17, 19, 21), 3, 1), (24, 48, (9, 23, 22), 3, 1), (64, 32, (18, 17, 16), 3, 1),
-]
+# the shapes, grouped by the kernel family each group is there for: tests/conv_cases.py (the flat lists are the sections in order)
+CONV_CASES = CC.CONV_CASES
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -112,29 +69,31 @@ def test_conv3d_ops(case, dt, impl):
     sc = scratch(cin, cout, D, H, W)
     wd, bd = torch.from_numpy(w).to(DEV), torch.from_numpy(b).to(DEV)
     xd = to_cl(x, dt)
-    yd = torch.empty((*od, cout), dtype=TDT[dt], device=DEV)
+    yd = Guarded((*od, cout), TDT[dt])
     E.check(E.lib.unet_op_conv3d_fwd(EDT[dt], impl, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), yd.data_ptr(), cin, cout, D, H, W,
                                      ks, st, sc.data_ptr(), stream()))
-    assert rel(from_cl(yd), y_ref) < (1e-5 if dt == "fp32" else 1e-2)
+    check_all("forward", ("y", yd), ("scratch", sc))
+    assert rel(from_cl(yd.t), y_ref) < (1e-5 if dt == "fp32" else 1e-2)
     # dgrad / wgrad
     dy = q(rnd((cout, *od), 4), dt)
     dx_ref = np.empty_like(x); dw_ref = np.zeros_like(w); db_ref = np.zeros_like(b)
     l.orc_conv3d_bwd_data(O._f(dy), O._f(w), O._f(dx_ref), cin, cout, D, H, W, ks, st)
     l.orc_conv3d_bwd_weight(O._f(x), O._f(dy), O._f(dw_ref), O._f(db_ref), cin, cout, D, H, W, ks, st)
     dyd = to_cl(dy, dt)
-    dxd = torch.empty((D, H, W, cin), dtype=TDT[dt], device=DEV)
+    dxd = Guarded((D, H, W, cin), TDT[dt])
     E.check(E.lib.unet_op_conv3d_bwd_data(EDT[dt], impl, dyd.data_ptr(), wd.data_ptr(), dxd.data_ptr(), cin, cout, D, H, W, ks, st,
                                           sc.data_ptr(), stream()))
-    assert rel(from_cl(dxd), dx_ref) < (1e-5 if dt == "fp32" else 1e-2)
-    dwd = torch.ones_like(wd); dbd = torch.ones_like(bd)  # += semantics: start from 1
+    check_all("dgrad", ("dx", dxd), ("scratch", sc))
+    assert rel(from_cl(dxd.t), dx_ref) < (1e-5 if dt == "fp32" else 1e-2)
+    dwd = Guarded(wd.shape, torch.float32, 1.0); dbd = Guarded(bd.shape, torch.float32, 1.0)  # += semantics: start from 1
     E.check(E.lib.unet_op_conv3d_bwd_weight(EDT[dt], impl, xd.data_ptr(), dyd.data_ptr(), dwd.data_ptr(), dbd.data_ptr(), cin, cout,
                                             D, H, W, ks, st, sc.data_ptr(), stream()))
-    assert rel(dwd.cpu().numpy() - 1.0, dw_ref) < (2e-5 if dt == "fp32" else 1e-2)
-    assert rel(dbd.cpu().numpy() - 1.0, db_ref) < (2e-5 if dt == "fp32" else 1e-2)
+    check_all("wgrad", ("dw", dwd), ("db", dbd), ("scratch", sc))
+    assert rel(dwd.t.cpu().numpy() - 1.0, dw_ref) < (2e-5 if dt == "fp32" else 1e-2)
+    assert rel(dbd.t.cpu().numpy() - 1.0, db_ref) < (2e-5 if dt == "fp32" else 1e-2)
 
 
-@pytest.mark.parametrize("case", [(1, 16, (9, 13, 21)), (1, 32, (4, 8, 16)), (32, 16, (6, 9, 20)), (16, 16, (5, 8, 17)),
-                                  (16, 16, (9, 13, 21)), (16, 32, (12, 9, 20)), (16, 16, (33, 8, 16))])
+@pytest.mark.parametrize("case", CC.PLAIN_STATS_CASES)
 def test_conv3d_plain_with_statistics(case):
     """plain input (what a plan feeds its convs: activated copies), bf16, statistics epilogue: the first-conv MFMA kernel
     (Cin = 1) and the persistent kernel"""
@@ -145,13 +104,14 @@ def test_conv3d_plain_with_statistics(case):
     l.orc_conv3d_fwd(O._f(x), O._f(w), O._f(b), O._f(y_ref), cin, cout, D, H, W, 3, 1)
     sc = scratch(cin, cout, D, H, W)
     wd, bd, xd = torch.from_numpy(w).to(DEV), torch.from_numpy(b).to(DEV), to_cl(x, "bf16")
-    yd = torch.empty((D, H, W, cout), dtype=torch.bfloat16, device=DEV)
-    stats = torch.empty((cout, 2), dtype=torch.float32, device=DEV)
+    yd = Guarded((D, H, W, cout), torch.bfloat16)
+    stats = Guarded((cout, 2), torch.float32)
     E.check(E.lib.unet_op_conv3d_fwd_fused(U.DTYPE_BF16, U.IMPL_AUTO, xd.data_ptr(), None, None, 0, wd.data_ptr(), bd.data_ptr(),
                                            yd.data_ptr(), stats.data_ptr(), cin, cout, D, H, W, 3, 1, sc.data_ptr(), stream()))
-    y = from_cl(yd)
+    check_all("plain + statistics", ("y", yd), ("stats", stats), ("scratch", sc))
+    y = from_cl(yd.t)
     assert rel(y, y_ref) < 1e-2
-    st = stats.cpu().numpy()
+    st = stats.t.cpu().numpy()
     assert np.allclose(st[:, 0], y.reshape(cout, -1).sum(1), rtol=1e-4, atol=1e-2)
     assert np.allclose(st[:, 1], (y.reshape(cout, -1) ** 2).sum(1), rtol=1e-4, atol=1e-2)
 
@@ -159,25 +119,26 @@ def test_conv3d_plain_with_statistics(case):
 def test_conv3d_pack_then_kernel_only():
     """unet_op_conv3d_pack + unet_op_conv3d_fwd_packed (what bench.py times as the dominant kernel) = unet_op_conv3d_fwd;
     shapes the MFMA kernels do not cover are refused"""
-    cin, cout, D, H, W = 32, 16, 6, 9, 20
+    cin, cout, (D, H, W) = CC.PACKED_CASE
     l = O.lib()
     x = q(rnd((cin, D, H, W), 1), "bf16"); w = rnd((cout, cin, 3, 3, 3), 2, 0.2); b = rnd((cout,), 3)
     y_ref = np.empty((cout, D, H, W), np.float32)
     l.orc_conv3d_fwd(O._f(x), O._f(w), O._f(b), O._f(y_ref), cin, cout, D, H, W, 3, 1)
     wp, part = scratch(cin, cout, D, H, W), scratch(cin, cout, D, H, W)
     wd, bd, xd = torch.from_numpy(w).to(DEV), torch.from_numpy(b).to(DEV), to_cl(x, "bf16")
-    yd = torch.empty((D, H, W, cout), dtype=torch.bfloat16, device=DEV)
+    yd = Guarded((D, H, W, cout), torch.bfloat16)
     E.check(E.lib.unet_op_conv3d_pack(U.DTYPE_BF16, wd.data_ptr(), wp.data_ptr(), cin, cout, D, H, W, 3, 1, stream()))
     E.check(E.lib.unet_op_conv3d_fwd_packed(U.DTYPE_BF16, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), yd.data_ptr(), part.data_ptr(),
                                             cin, cout, D, H, W, 3, 1, stream()))
-    assert rel(from_cl(yd), y_ref) < 1e-2
+    check_all("pack + kernel only", ("y", yd), ("wp", wp), ("part", part))
+    assert rel(from_cl(yd.t), y_ref) < 1e-2
     assert E.lib.unet_op_conv3d_pack(U.DTYPE_F32, wd.data_ptr(), wp.data_ptr(), cin, cout, D, H, W, 3, 1, stream()) != 0
     assert b"MFMA" in E.lib.unet_last_error()
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 @pytest.mark.parametrize("impl", [U.IMPL_DIRECT, U.IMPL_AUTO])
-@pytest.mark.parametrize("case", [(16, 16, (6, 9, 20), 3, 1, 2), (32, 32, (8, 8, 8), 3, 2, 3), (16, 32, (5, 6, 4), 3, 1, 1), (5, 7, (4, 5, 6), 3, 1, 2)])
+@pytest.mark.parametrize("case", CC.FUSED_CASES)
 def test_conv3d_fused_prologue_epilogue(case, dt, impl):
     """norm + activation applied by the consumer while it reads (zero padding AFTER the activation), and the
     {sum, sum of squares} of the stored output that the next norm needs (unet.cpp:74-98 fused into unet.cpp:59-72)"""
@@ -195,34 +156,21 @@ def test_conv3d_fused_prologue_epilogue(case, dt, impl):
     sc = scratch(cin, cout, D, H, W)
     wd, bd, xd = torch.from_numpy(w).to(DEV), torch.from_numpy(b).to(DEV), to_cl(x, dt)
     sd, hd = torch.from_numpy(scale).to(DEV), torch.from_numpy(shift).to(DEV)
-    yd = torch.empty((*od, cout), dtype=TDT[dt], device=DEV)
-    stats = torch.empty((cout, 2), dtype=torch.float32, device=DEV)
+    yd = Guarded((*od, cout), TDT[dt])
+    stats = Guarded((cout, 2), torch.float32)
     E.check(E.lib.unet_op_conv3d_fwd_fused(EDT[dt], impl, xd.data_ptr(), sd.data_ptr(), hd.data_ptr(), act, wd.data_ptr(), bd.data_ptr(),
                                            yd.data_ptr(), stats.data_ptr(), cin, cout, D, H, W, ks, st, sc.data_ptr(), stream()))
-    y = from_cl(yd)
+    check_all("fused", ("y", yd), ("stats", stats), ("scratch", sc))
+    y = from_cl(yd.t)
     assert rel(y, y_ref) < (1e-5 if dt == "fp32" else 1.5e-2)
-    got = stats.cpu().numpy().astype(np.float64)
+    got = stats.t.cpu().numpy().astype(np.float64)
     yy = y.astype(np.float64).reshape(cout, -1)
     assert np.allclose(got[:, 0], yy.sum(1), rtol=1e-4, atol=1e-3 * np.abs(yy).sum(1).max())
     assert np.allclose(got[:, 1], (yy * yy).sum(1), rtol=1e-4)
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("case", [(16, 16, (4, 5, 6)), (7, 3, (3, 4, 5)), (32, 16, (4, 4, 8)),
-                                  # MFMA conv_trans (Cin % 32 == 0): every tile configuration, ragged edges
-                                  (64, 32, (3, 5, 19)), (32, 32, (4, 4, 4)), (128, 64, (2, 3, 2)), (32, 48, (5, 9, 7)),
-                                  # output-stationary conv_trans wgrad (coarse side 4^3 above, 8^3 here: 4 tiles along z per block)
-                                  (32, 48, (8, 8, 8)),
-                                  # conv_trans dgrad with 32-channel chunks (Cout % 32 == 0 on coarse grids of 8^3 or less): both tiles
-                                  (64, 64, (5, 6, 7)), (32, 96, (8, 8, 8)), (256, 256, (4, 4, 4)),
-                                  # split-K kernels of the deep levels (coarse grids of <= 512 voxels, Cin % 32 == 0): ragged groups, one-voxel extents
-                                  (64, 32, (3, 3, 5)), (32, 16, (1, 2, 3)), (256, 128, (2, 2, 2)), (96, 64, (7, 8, 8)),
-                                  # sliding-window conv_trans kernels (kernels_mfma_s2.hip; coarse grid >= 16 wide, >= 4 deep): forward with 1 / 2 / 4
-                                  # k-steps and 1..4 row-tile blocks, dgrad with 16- and 32-channel planes and 2 / 4 row tiles per block, ragged edges
-                                  (32, 16, (4, 6, 16)), (64, 32, (5, 9, 19)), (128, 64, (4, 4, 16)), (32, 48, (6, 7, 17)), (64, 16, (7, 5, 20)),
-                                  (32, 32, (9, 4, 18)),
-                                  # ... and their sliding-window weight gradient (coarse grid >= 24 wide): pairings 1x2 / 2x2, several pair groups, ragged
-                                  (32, 16, (4, 5, 24)), (64, 32, (5, 3, 33)), (32, 32, (4, 4, 26)), (32, 48, (9, 6, 25))])
+@pytest.mark.parametrize("case", CC.CONVT_CASES)
 def test_convt_ops(case, dt):
     cin, cout, (D, H, W) = case
     l = O.lib()
@@ -231,24 +179,27 @@ def test_convt_ops(case, dt):
     l.orc_convt_fwd(O._f(x), O._f(w), O._f(b), O._f(y_ref), cin, cout, D, H, W)
     sc = scratch(cin, cout, D, H, W)
     wd, bd, xd = torch.from_numpy(w).to(DEV), torch.from_numpy(b).to(DEV), to_cl(x, dt)
-    yd = torch.empty((2 * D, 2 * H, 2 * W, cout), dtype=TDT[dt], device=DEV)
+    yd = Guarded((2 * D, 2 * H, 2 * W, cout), TDT[dt])
     E.check(E.lib.unet_op_convt_fwd(EDT[dt], 0, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), yd.data_ptr(), cin, cout, D, H, W,
                                     sc.data_ptr(), stream()))
-    assert rel(from_cl(yd), y_ref) < (1e-5 if dt == "fp32" else 1e-2)
+    check_all("forward", ("y", yd), ("scratch", sc))
+    assert rel(from_cl(yd.t), y_ref) < (1e-5 if dt == "fp32" else 1e-2)
     dy = q(rnd(y_ref.shape, 4), dt)
     dx_ref = np.empty_like(x); dw_ref = np.zeros_like(w); db_ref = np.zeros_like(b)
     l.orc_convt_bwd_data(O._f(dy), O._f(w), O._f(dx_ref), cin, cout, D, H, W)
     l.orc_convt_bwd_weight(O._f(x), O._f(dy), O._f(dw_ref), O._f(db_ref), cin, cout, D, H, W)
     dyd = to_cl(dy, dt)
-    dxd = torch.empty((D, H, W, cin), dtype=TDT[dt], device=DEV)
+    dxd = Guarded((D, H, W, cin), TDT[dt])
     E.check(E.lib.unet_op_convt_bwd_data(EDT[dt], 0, dyd.data_ptr(), wd.data_ptr(), dxd.data_ptr(), cin, cout, D, H, W,
                                          sc.data_ptr(), stream()))
-    assert rel(from_cl(dxd), dx_ref) < (1e-5 if dt == "fp32" else 1e-2)
-    dwd = torch.ones_like(wd); dbd = torch.ones_like(bd)   # += semantics: start from 1
+    check_all("dgrad", ("dx", dxd), ("scratch", sc))
+    assert rel(from_cl(dxd.t), dx_ref) < (1e-5 if dt == "fp32" else 1e-2)
+    dwd = Guarded(wd.shape, torch.float32, 1.0); dbd = Guarded(bd.shape, torch.float32, 1.0)   # += semantics: start from 1
     E.check(E.lib.unet_op_convt_bwd_weight(EDT[dt], 0, xd.data_ptr(), dyd.data_ptr(), dwd.data_ptr(), dbd.data_ptr(), cin, cout,
                                            D, H, W, sc.data_ptr(), stream()))
-    assert rel(dwd.cpu().numpy() - 1.0, dw_ref) < (2e-5 if dt == "fp32" else 1e-2)
-    assert rel(dbd.cpu().numpy() - 1.0, db_ref) < (2e-5 if dt == "fp32" else 1e-2)
+    check_all("wgrad", ("dw", dwd), ("db", dbd), ("scratch", sc))
+    assert rel(dwd.t.cpu().numpy() - 1.0, dw_ref) < (2e-5 if dt == "fp32" else 1e-2)
+    assert rel(dbd.t.cpu().numpy() - 1.0, db_ref) < (2e-5 if dt == "fp32" else 1e-2)
 
 
 def load_case(golden_dir, name):

@@ -1646,6 +1646,19 @@ static DeepScratch op_deep() {
     return d;
 }
 
+// what the entry points below ask choose_conv for one plain source of cin channels, as integers; launches nothing
+int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]) {
+    try {
+        if (!out) throw std::runtime_error("unet_op_conv_choice: null output");
+        if (cin < 1 || cout < 1 || D < 1 || H < 1 || W < 1) throw std::runtime_error("unet_op_conv_choice: sizes must be positive");
+        const ConvGeom g = transposed ? op_geom(cin, cout, D, H, W, 2, 2, true) : op_geom(cin, cout, D, H, W, ks, stride, false);
+        SrcDesc sd; sd.C = cin;
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, transposed != 0);
+        out[0] = (int)c.fwd; out[1] = (int)c.dgrad; out[2] = (int)c.wgrad;
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
 int unet_op_conv3d_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D, int H,
                        int W, int ks, int stride, void* scratch, void* stream) {
     OP_TRY({

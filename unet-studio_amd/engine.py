@@ -87,6 +87,7 @@ _sig("unet_allreduce_grads_all", _i, _pp, _i, _pp, C.c_int64, C.c_int64, _pp)
 _sig("unet_comm_broadcast", _i, _vp, _vp, C.c_int64, _i, _vp)
 _sig("unet_comm_join", _i, _vp, _vp)
 _sig("unet_op_scratch_bytes", _i, _i, _i, _i, _i, _i, C.POINTER(_sz))
+_sig("unet_op_conv_choice", _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i))
 _sig("unet_op_conv3d_fwd", _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp)
 _sig("unet_op_conv3d_pack", _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp)
 _sig("unet_op_conv3d_fwd_packed", _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp)
@@ -109,7 +110,7 @@ EXPORTS = [
     "unet_plan_buffer_shape", "unet_plan_output_count", "unet_plan_output_shape", "unet_plan_workspace_bytes",
     "unet_plan_flops", "unet_plan_describe", "unet_plan_op_count", "unet_plan_op_info", "unet_profile_begin", "unet_profile_end", "unet_forward", "unet_backward", "unet_backward_part", "unet_plan_backward_buckets", "unet_loss_scratch_bytes", "unet_loss", "unet_forward_loss", "unet_forward_loss_mode", "unet_sum_buffers",
     "unet_sgd_step", "unet_sgd_step_packed", "unet_pack_filters", "unet_stream_create_cu_range", "unet_stream_destroy", "unet_plan_side_cu_range", "unet_set_error", "unet_comm_unique_id", "unet_comm_create", "unet_comm_create_all", "unet_comm_destroy", "unet_comm_rank",
-    "unet_allreduce_grads", "unet_allreduce_grads_all", "unet_comm_broadcast", "unet_comm_join", "unet_op_scratch_bytes", "unet_op_conv3d_fwd", "unet_op_conv3d_fwd_fused", "unet_op_conv3d_pack", "unet_op_conv3d_fwd_packed", "unet_op_conv3d_bwd_data", "unet_op_conv3d_fwd_norm", "unet_op_conv3d_bwd_data_norm", "unet_op_conv3d_bwd_weight",
+    "unet_allreduce_grads", "unet_allreduce_grads_all", "unet_comm_broadcast", "unet_comm_join", "unet_op_scratch_bytes", "unet_op_conv_choice", "unet_op_conv3d_fwd", "unet_op_conv3d_fwd_fused", "unet_op_conv3d_pack", "unet_op_conv3d_fwd_packed", "unet_op_conv3d_bwd_data", "unet_op_conv3d_fwd_norm", "unet_op_conv3d_bwd_data_norm", "unet_op_conv3d_bwd_weight",
     "unet_op_convt_fwd", "unet_op_convt_bwd_data", "unet_op_convt_bwd_weight", "unet_op_pack_ndhwc", "unet_op_unpack_ncdhw",
 ]
 
