@@ -1,6 +1,9 @@
 // Plan + executor + C ABI (include/unet_hip.h).  The plan is immutable after creation; every call
 // works on caller-owned device memory (parameters, gradients, workspace) and a caller-owned stream,
 // so concurrent calls on one plan are safe when they use different workspaces (qc.cpp:273-297).
+// What a call has to remember between its launches (which gradient buffers hold a value, which dgrad
+// epilogue left or finished a norm backward) lives in the call: a backward issued in parts rebuilds it
+// from the graph and the launchers' outcome queries (kernels.h: DgradOutcome), never from an earlier call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,13 +106,9 @@ struct unet_plan {
     std::vector<size_t> w_fwd, w_dgrad;      // per op (conv / conv_trans): packed fp32 weights
     std::vector<size_t> wm_fwd, wm_dgrad;    // per op: MFMA fragment-order bf16 filters (SIZE_MAX: op not on the MFMA path)
     std::vector<int> n_consumers;            // per tensor: ops that read it
-    std::vector<int> first_consumer;         // per tensor: lowest op index that reads it (-1: none) -- in the backward its LAST gradient writer
-    // norm-backward partial rows a dgrad epilogue left in a workspace's partial() for the tensor's view_backward, which may run in a later
-    // unet_backward_part call on the same workspace (the bucketed backward must make the same choices as the whole one): workspace -> {tensor, rows}
-    mutable std::mutex bn_mu;
-    mutable std::unordered_map<const void*, std::pair<int, int>> bn_pending;
-    // ... and the tensors whose whole norm backward a deep-level dgrad already ran in its epilogue (kernels_mfma_deep.hip): workspace -> tensors
-    mutable std::unordered_map<const void*, std::vector<int>> bn_done;
+    // per tensor: lowest op index that reads it (-1: none) -- in the backward its LAST gradient writer, the only dgrad that is offered the
+    // tensor's norm (Exec::backward: its epilogue may leave that norm backward's partial rows in partial(), or run all of it)
+    std::vector<int> first_consumer;
     std::vector<ConvChoice> conv;            // per op: the kernel family of each direction (conv / conv_trans; conv_select.h)
     size_t wgrad_off = 0;
     // sliding-window wgrads keep their slabs until ONE batched reduce per backward (part): per-op slab regions + the job table
@@ -175,6 +174,13 @@ struct unet_plan {
     // the sources by their channel counts: what the kernel choice and the scratch sizes read
     void src_chans(const Op& op, SrcDesc* sd) const {
         for (int k = 0; k < op.nsrc; ++k) sd[k].C = g.tensors[op.src[k]].C;
+    }
+    // the pointers of the caller's parameters (or their gradients) form one flat buffer in parameter order: both hosts allocate them
+    // so, and the batched launches (filter packs, slab reduce) address everything from ptrs[0]
+    bool is_flat(const float* const* ptrs) const {
+        for (size_t i = 0; i < g.params.size(); ++i)
+            if (ptrs[i] != ptrs[0] + p_off[i]) return false;
+        return true;
     }
     // Which weight-gradient launches are "polite" (one 4-wave block per CU: mfma_util.h polite_lds): every one that runs on the side
     // stream.  The backward walks the ops from the last to the first -- the decoder's top levels (their gradients are HELD, see
@@ -490,6 +496,31 @@ void norm_bwd_passes(int dtype, void* g, const void* u, int C, int64_t S, const 
     launch_norm_bwd_finalize(partial, rows, C, S, gamma, stat, coef, dgamma, dbeta, s, dtype == UNET_DTYPE_F32);
     if (!no_apply) launch_norm_bwd_apply(dtype, g, u, C, S, stat, coef, act, s);
 }
+// The input gradient of a conv / conv_trans on the matrix cores (Dgrad::mfma), shared by the executor and the single-op surface: the
+// deep levels' split-K kernel where its outcome query says it takes the shape, else the halo-tile / sliding-window family.  nb
+// (optional): the norm whose view the one destination is, offered to the kernel's epilogue; partial: where its statistics rows go.
+// Returns who finishes that norm backward -- known BEFORE the launch (launch == false: nothing is enqueued, the answer alone: the dry
+// replay of a backward in parts), and what a launcher then reports must be that prediction.
+DgradOutcome mfma_dgrad(const ConvGeom& g, bool transposed, const void* dy, const void* wm, const DstGrad* dst, int ndst, const DeepNormBwd* nb,
+                        float* partial, const DeepScratch& deep, hipStream_t s, bool launch = true) {
+    const bool norm = nb != nullptr;
+    DgradOutcome want = deep_dgrad_outcome(g, transposed, dst, ndst, norm, deep);
+    const bool on_deep = want.served;
+    if (!on_deep) {
+        if (transposed) want.served = true;     // (launch_mfma_convt_dgrad: every shape, no norm epilogue)
+        else want = mfma_conv_dgrad_outcome(g, dst, ndst, norm);
+    }
+    if (!launch) return want;
+    DgradOutcome got = want;
+    if (on_deep) got = launch_deep_dgrad(g, transposed, dy, wm, dst, ndst, nb, deep, s);
+    else if (transposed) launch_mfma_convt_dgrad(g, dy, wm, dst, ndst, s);
+    else {
+        const BnBwdStats bn = {norm ? nb->u : nullptr, norm ? nb->stat : nullptr, partial, norm ? nb->act : 0, dst[0].C};
+        got = launch_mfma_conv_dgrad(g, dy, wm, dst, ndst, s, norm ? &bn : nullptr);
+    }
+    if (!(got == want)) throw std::runtime_error("dgrad: the launch did not do what its outcome query predicted");
+    return want;
+}
 
 struct Exec {
     const unet_plan& p;
@@ -548,9 +579,7 @@ struct Exec {
         bool packed = false, pack_pending = false, pack2_pending = false;
         if (p.jobs_dev && packs_current) { packed = true; deep_on = true; }
         else if (p.jobs_dev) {
-            bool flat = true;
-            for (size_t i = 0; i < g.params.size() && flat; ++i) flat = params[i] == params[0] + p.p_off[i];
-            if (flat) {
+            if (p.is_flat(params)) {
                 // training forward: the pack runs on the plan's side stream beside the input pack, the first conv (which reads the
                 // fp32 filter) and its norm; the first kernel that needs packed filters waits for it.  (Eval forwards stay on the
                 // caller's stream: they are re-entrant per workspace, the side stream and its events are per plan.)
@@ -723,25 +752,14 @@ struct Exec {
 
     // g[t] holds dL/d(view of t); turn it into dL/d(raw t) (and accumulate the norm's affine gradients)
     // no_apply: stop after the finalize (coef(T.norm) is final; dgamma / dbeta accumulated) -- the element-wise pass is fused into the one
-    // consumer of dL/d(raw t) (the first conv's weight gradient)
-    void view_backward(int t, const float* const* params, float* const* gparams, bool no_apply = false) {
+    // consumer of dL/d(raw t) (the first conv's weight gradient).  rows > 0: the statistics rows that the dgrad which produced this
+    // gradient left in partial()
+    void view_backward(int t, const float* const* params, float* const* gparams, bool no_apply, int rows) {
         const Tensor& T = p.g.tensors[t];
         if (T.norm >= 0) {
             const Norm& n = p.g.norms[T.norm];
-            // the statistics pass, unless the dgrad that produced this gradient already left its partial rows (bn_rows_tensor == t)
-            int have = 0;
-            {
-                std::lock_guard<std::mutex> lk(p.bn_mu);
-                auto d = p.bn_done.find(ws);
-                if (d != p.bn_done.end()) {
-                    auto f = std::find(d->second.begin(), d->second.end(), t);
-                    if (f != d->second.end()) { d->second.erase(f); return; }    // dL/d(raw), the affine gradients and coef() are already there
-                }
-                auto it = p.bn_pending.find(ws);
-                if (it != p.bn_pending.end()) { if (it->second.first == t) have = it->second.second; p.bn_pending.erase(it); }
-            }
             norm_bwd_passes(p.dtype, gptr(t), tptr(t), T.C, T.voxels(), stat(T.norm), T.act, params[n.gamma], coef(T.norm),
-                            gparams[n.gamma], gparams[n.beta], partial(), have, no_apply, s);
+                            gparams[n.gamma], gparams[n.beta], partial(), rows, no_apply, s);
         } else if (T.act != ACT_NONE) {
             launch_act_bwd(p.dtype, gptr(t), tptr(t), T.act, T.numel(), s);
         }
@@ -758,11 +776,8 @@ struct Exec {
         // (A.forward, B.forward, B.backward, A.backward) a consumed-once flag let A's backward run ahead of A's packs.  The event's latest
         // record is behind every earlier pack on the side stream, and waiting on a never-recorded or completed event costs nothing.
         if (p.side) HIP_OK(hipStreamWaitEvent(s, p.ev_packd, 0));
-        {   // the deep levels' kernels: only behind a forward that made its packs with the batched launch (which cleared the counters)
-            bool flat = p.jobs_dev != nullptr;
-            for (size_t k = 0; k < g.params.size() && flat; ++k) flat = params[k] == params[0] + p.p_off[k];
-            deep_on = flat;
-        }
+        // the deep levels' kernels: only behind a forward that made its packs with the batched launch (which cleared the counters)
+        deep_on = p.jobs_dev && p.is_flat(params);
         std::vector<char> init(g.tensors.size(), 0);
         auto dst_of = [&](int t) {
             DstGrad d;
@@ -784,11 +799,14 @@ struct Exec {
             HIP_OK(hipStreamWaitEvent(sb, p.ev_fork, 0));
         };
         if (op_lo < 0) op_lo = 0;
-        if (op_hi >= (int)g.ops.size()) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_pending.erase(ws); p.bn_done.erase(ws); }   // a new backward starts
+        // The hand-off from a dgrad to the view_backward of its destination (a norm layer's view), rebuilt by the dry replay like init[]:
+        // ONE slot for the statistics rows an epilogue left in partial() -- the next norm view_backward consumes it when it is that
+        // tensor's, else drops it (its own statistics pass overwrites partial()) -- and, per tensor, "its whole norm backward already ran"
+        int bn_tensor = -1, bn_rows = 0;
+        std::vector<char> norm_done(g.tensors.size(), 0);
         // gradients in one flat buffer (both hosts allocate them so): the sliding-window wgrads only write their slabs here and ONE
         // batched reduce at the end of this call adds them all into the gradients
-        bool gflat = p.wz_jobs_dev != nullptr;
-        for (size_t k = 0; k < g.params.size() && gflat; ++k) gflat = gparams[k] == gparams[0] + p.p_off[k];
+        const bool gflat = p.wz_jobs_dev && p.is_flat(gparams);
         std::vector<char> wz_ran(p.wz_jobs.size(), 0);
         int wz_pending = 0;
         // slabs of the weight gradients launched so far -> gradients: one launch per run of consecutive jobs (normally one).  Flushed
@@ -909,7 +927,14 @@ struct Exec {
             if (!dry && p.conv[i].wgrad == Wgrad::first_mfma && g.tensors[t].norm >= 0 && !g.tensors[op.src[0]].needs_grad && sb != s &&
                 p.wz_off[i] != SIZE_MAX && g.tensors[t].C % 8 == 0)
                 first_fused = !env().no_first_wgrad_fuse;
-            if (!dry) { ProfScope ps(i, UNET_PROF_NORM_BWD, s); view_backward(t, params, gparams, first_fused); }
+            {
+                const bool has_norm = g.tensors[t].norm >= 0;
+                const bool done = has_norm && norm_done[t];    // dL/d(raw), the affine gradients and coef() are already there
+                int rows = 0;
+                if (done) norm_done[t] = 0;
+                else if (has_norm) { if (bn_tensor == t) rows = bn_rows; bn_tensor = -1; }
+                if (!dry) { ProfScope ps(i, UNET_PROF_NORM_BWD, s); if (!done) view_backward(t, params, gparams, first_fused, rows); }
+            }
             switch (op.kind) {
                 case OP_CONV:
                 case OP_CONVT: {
@@ -947,7 +972,7 @@ struct Exec {
                         }
                     }
                     ProfScope pd(i, UNET_PROF_DGRAD, s);
-                    if (!dry && any) switch (p.conv[i].dgrad) {
+                    if (any) switch (p.conv[i].dgrad) {
                         case Dgrad::mfma: {
                             // The source is a norm layer's view read by this conv alone: its gradient is complete when this dgrad
                             // has written it, so the statistics pass of that norm's backward (a second read of the gradient and of the
@@ -965,24 +990,18 @@ struct Exec {
                                 const Norm& n = g.norms[Ts.norm];
                                 nb = {tptr(ts), stat(Ts.norm), params[n.gamma], coef(Ts.norm), gparams[n.gamma], gparams[n.beta], Ts.act};
                             }
-                            if (op.kind == OP_CONVT) {
-                                int norm_done = 0;
-                                if (deep_on && launch_deep_convt_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr, deep(), &norm_done, s)) {
-                                    if (norm_done) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_done[ws].push_back(ts); }
-                                } else
-                                    launch_mfma_convt_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, s);
-                                break;
-                            }
-                            BnBwdStats bn = {tptr(ts), Ts.norm >= 0 ? stat(Ts.norm) : nullptr, partial(), Ts.act, Ts.C};
-                            int rows = 0;
-                            const int served = deep_on ? launch_deep_conv_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr, deep(), s) : 0;
-                            if (served == 2) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_done[ws].push_back(ts); }
-                            if (!served) rows = launch_mfma_conv_dgrad(cg, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, s, can ? &bn : nullptr);
-                            if (rows > 0) { std::lock_guard<std::mutex> lk(p.bn_mu); p.bn_pending[ws] = {ts, rows}; }
+                            // (dry: the outcome alone, which the launch of an earlier part reported then)
+                            const DgradOutcome o = mfma_dgrad(cg, op.kind == OP_CONVT, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr,
+                                                              partial(), deep(), s, !dry);
+                            if (o.norm_done) norm_done[ts] = 1;
+                            if (o.rows > 0) { bn_tensor = ts; bn_rows = o.rows; }
                             break;
                         }
-                        case Dgrad::f32_mfma: launch_conv_f32_mfma_dgrad(cg, (const float*)gptr(t), wd, dg, op.nsrc, s); break;
+                        case Dgrad::f32_mfma:
+                            if (!dry) launch_conv_f32_mfma_dgrad(cg, (const float*)gptr(t), wd, dg, op.nsrc, s);
+                            break;
                         case Dgrad::direct:
+                            if (dry) break;
                             if (op.kind == OP_CONVT) launch_convt_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
                             else launch_conv_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
                             break;
@@ -1503,9 +1522,7 @@ int unet_pack_filters(const unet_plan* p, const float* const* params, void* work
     try {
         if (!p || !params || !workspace || !made) throw std::runtime_error("unet_pack_filters: null argument");
         *made = 0;
-        if (!p->jobs_dev || p->pack_jobs.empty()) return 0;
-        for (size_t i = 0; i < p->g.params.size(); ++i)
-            if (params[i] != params[0] + p->p_off[i]) return 0;
+        if (!p->jobs_dev || p->pack_jobs.empty() || !p->is_flat(params)) return 0;
         DeviceGuard dg(p->device);
         launch_mfma_pack_batched(params[0], workspace, p->jobs_dev, (int)p->pack_jobs.size(), with_dgrad ? p->pack_blocks : p->pack_fwd_blocks,
                                  (hipStream_t)stream, 0, 0, p->deep_part_bytes ? (int*)((char*)workspace + p->deep_cnt_off) : nullptr, p->deep_ncnt);
@@ -1750,7 +1767,7 @@ int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w,
         if (c == Dgrad::mfma) {
             void* wm = (char*)scratch + OpScratch(cin, cout).pack;
             launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
-            if (!launch_deep_conv_dgrad(g, dy, wm, &d, 1, nullptr, op_deep(), s)) launch_mfma_conv_dgrad(g, dy, wm, &d, 1, s);
+            mfma_dgrad(g, false, dy, wm, &d, 1, nullptr, nullptr, op_deep(), s);
         } else {
             op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
             if (c == Dgrad::f32_mfma) launch_conv_f32_mfma_dgrad(g, (const float*)dy, wd, &d, 1, s);
@@ -1802,21 +1819,10 @@ int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w,
         float* part = (float*)((char*)scratch + L.partials);
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = accumulate ? 1 : 0;
         const DeepNormBwd nb = {u, stat, gamma, coef, dgamma, dbeta, act};
-        bool done = false;
-        int rows = 0;
-        if (transposed) {
-            launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
-            int norm_done = 0;
-            if (launch_deep_convt_dgrad(g, dy, wm, &d, 1, &nb, op_deep(), &norm_done, s)) done = norm_done != 0;
-            else launch_mfma_convt_dgrad(g, dy, wm, &d, 1, s);
-        } else {
-            launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
-            const BnBwdStats bn = {u, stat, part, act, cin};
-            const int served = launch_deep_conv_dgrad(g, dy, wm, &d, 1, &nb, op_deep(), s);
-            done = served == 2;
-            if (!served) rows = launch_mfma_conv_dgrad(g, dy, wm, &d, 1, s, &bn);
-        }
-        if (!done) norm_bwd_passes(UNET_DTYPE_BF16, dx, u, cin, (int64_t)D * H * W, stat, act, gamma, coef, dgamma, dbeta, part, rows, false, s);
+        if (transposed) launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
+        else launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
+        const DgradOutcome o = mfma_dgrad(g, transposed != 0, dy, wm, &d, 1, &nb, part, op_deep(), s);
+        if (!o.norm_done) norm_bwd_passes(UNET_DTYPE_BF16, dx, u, cin, (int64_t)D * H * W, stat, act, gamma, coef, dgamma, dbeta, part, o.rows, false, s);
     })
 }
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D,
@@ -1864,7 +1870,7 @@ int unet_op_convt_bwd_data(int dtype, int impl, const void* dy, const float* w, 
         if (choose_conv(dtype, impl, g, &sd, 1, false, true).dgrad == Dgrad::mfma) {
             void* wm = (char*)scratch + OpScratch(cin, cout).pack;
             launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
-            if (!launch_deep_convt_dgrad(g, dy, wm, &d, 1, nullptr, op_deep(), nullptr, s)) launch_mfma_convt_dgrad(g, dy, wm, &d, 1, s);
+            mfma_dgrad(g, true, dy, wm, &d, 1, nullptr, nullptr, op_deep(), s);
         } else {
             op_pack(w, cin, cout, 8, true, scratch, &wf, &wd, s);
             launch_convt_dgrad_direct(dtype, g, dy, wd, &d, 1, s);

@@ -265,20 +265,32 @@ void launch_bias_grad(int dtype, const void* dy, int C, int64_t S, float* db, vo
 // dgrad of a 3x3x3 conv, stride 1 or 2 (g = forward geometry)
 bool mfma_conv_dgrad_supported(int dtype, const ConvGeom& g, const SrcDesc* src, int nsrc);
 size_t mfma_conv_dgrad_w_bytes(const ConvGeom& g);
-// bn (optional): also leave the norm-backward statistics of the destination tensor's view (what launch_norm_bwd_partial computes) in
-// bn->partial; returns the number of partial rows written, 0 when the shape is not served by a kernel with that epilogue (the caller
-// then runs launch_norm_bwd_partial as usual).  Only for a single destination that is written, not accumulated.
+// What a dgrad launch does about the norm backward of its destination's view.  Every family below has an *_outcome function that
+// launches nothing and answers from the forward geometry, the destinations (count, channels, accumulate flags, null or not), whether a
+// norm is offered and the DeepScratch sizes; its launcher decides and sizes its grid by the same function and returns what it ran, so
+// a caller can know before the launch (or without one: the dry replay of a backward in parts) who finishes that norm backward.
+struct DgradOutcome {
+    bool served = false;     // false: the family does not take the shape, nothing was launched
+    bool norm_done = false;  // the destination's whole norm backward ran in the epilogue: dL/d(raw), coef, the affine gradients
+    int rows = 0;            // norm-backward partial rows (what launch_norm_bwd_partial computes) left in the partials buffer
+    bool operator==(const DgradOutcome& o) const { return served == o.served && norm_done == o.norm_done && rows == o.rows; }
+};
+// bn (optional): the norm whose view the destination is; the kernels with a statistics epilogue then leave its rows in bn->partial
+// (else the caller runs launch_norm_bwd_partial as usual).  The stride-1 kernels only for a single destination that is written, not
+// accumulated.  Always served.
 struct BnBwdStats { const void* u; const float* stat; float* partial; int act, C; };
-int launch_mfma_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
-                           const BnBwdStats* bn = nullptr);
+DgradOutcome mfma_conv_dgrad_outcome(const ConvGeom& g, const DstGrad* dst, int ndst, bool norm);
+DgradOutcome launch_mfma_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
+                                    const BnBwdStats* bn = nullptr);
 // kernels_mfma_s2.hip: sliding-window / LDS-DMA kernels for the contractions that cross a resolution boundary, coarse grid >= 16 wide
 // (the launchers below try them first; 0 / false = shape not served, the halo-tile kernel k_mfma_conv_p runs instead).
-// launch_s2_conv_fwd returns the number of statistics rows; launch_s2_conv_dgrad the number of norm-backward partial rows it left in
-// bn->partial (its destination may be ACCUMULATED into: the old values and the raw tensor travel by LDS-DMA too), -1 without bn
+// launch_s2_conv_fwd returns the number of statistics rows; launch_s2_conv_dgrad leaves the norm-backward partial rows in bn->partial
+// when bn is given (its destination may be ACCUMULATED into: the old values and the raw tensor travel by LDS-DMA too)
 int launch_s2_conv_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const void* w_mfma, const float* bias, void* out, float* stats_partial,
                        hipStream_t s);
-int launch_s2_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_s2_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
-                         const BnBwdStats* bn);
+DgradOutcome s2_conv_dgrad_outcome(const ConvGeom& g, const DstGrad* dst, int ndst, bool norm);
+DgradOutcome launch_s2_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_s2_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
+                                  const BnBwdStats* bn);
 int s2_conv_dgrad_rows_max();
 bool launch_s2_convt_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const void* w_mfma, const float* bias, void* out, hipStream_t s);
 bool launch_s2_convt_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, hipStream_t s);
@@ -290,7 +302,7 @@ int launch_s2_wgrad(int ks, const void* fine, const void* fine2, int C0, int Ca,
                     int cW, bool want_bias, int bias_from_a, void* scratch, hipStream_t s, int polite);
 // kernels_mfma_deep.hip: the deep levels (output grids of DEEP_MAX_VOXELS voxels or fewer): split-K implicit GEMM straight from global
 // memory, finished by the block that arrives last; with nf / nb the norm layer behind (forward) or in front of (backward) the conv runs
-// in that epilogue too.  The launchers below are tried first by the engine; false / 0 = shape not served.  DeepScratch: fp32 partial tiles
+// in that epilogue too.  The launchers below are tried first by the engine; false / !served = shape not served.  DeepScratch: fp32 partial tiles
 // and the arrival counters (ints, ZERO before the first launch; every launch leaves them zero) of one workspace.
 constexpr int64_t DEEP_MAX_VOXELS = 512;
 struct DeepScratch { float* part = nullptr; size_t part_bytes = 0; int* cnt = nullptr; int ncnt = 0; };
@@ -306,11 +318,11 @@ bool launch_deep_conv_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const
                           const DeepNormFwd* nf, const DeepScratch& sc, hipStream_t s);
 bool launch_deep_convt_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const void* w_mfma, const float* bias, void* out,
                            const DeepScratch& sc, hipStream_t s);
-// 0: not served; 1: gradient written / accumulated; 2: ... and the destination's norm backward done in place (nb given, one destination)
-int launch_deep_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, const DeepNormBwd* nb,
-                           const DeepScratch& sc, hipStream_t s);
-bool launch_deep_convt_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, const DeepNormBwd* nb,
-                             const DeepScratch& sc, int* norm_done, hipStream_t s);
+// dgrad of a conv k3 or (transposed) a conv_trans k2 s2: the gradient is written / accumulated; with nb and one destination that takes
+// every row, its norm backward is done in place
+DgradOutcome deep_dgrad_outcome(const ConvGeom& g, bool transposed, const DstGrad* dst, int ndst, bool norm, const DeepScratch& sc);
+DgradOutcome launch_deep_dgrad(const ConvGeom& g, bool transposed, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst,
+                               const DeepNormBwd* nb, const DeepScratch& sc, hipStream_t s);
 // ConvTranspose3d 2x2x2 stride 2: forward (1x1 GEMM + depth-to-space scatter) and dgrad (2x2x2 stride-2 conv of dL/dy)
 bool mfma_convt_supported(int dtype, const ConvGeom& g, const SrcDesc* src, int nsrc);
 size_t mfma_convt_w_bytes(const ConvGeom& g);

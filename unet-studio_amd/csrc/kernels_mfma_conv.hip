@@ -1113,17 +1113,8 @@ static int launch_conv_z(const MfmaConvArgs& a0, hipStream_t s) {
         if (a0.out[k] && (size_t)a0.oD * a0.oH * a0.oW * a0.outC[k] * 2 >= ((size_t)1 << 31)) return 0;
     ZWork zw;
     zw.cols_x = (g.Wo + 15) / 16; zw.cols_y = (g.Ho + 7) / 8;
-    const int cols = zw.cols_x * zw.cols_y, gy = g.Cout / 16;
-    int want = 512 / gy;                               // two blocks per CU in total
-    if (want < 1) want = 1;
-    int nseg = (want + cols - 1) / cols;               // z segments per column so that items >= the wanted block count
-    if (nseg < 1) nseg = 1;
-    int zlen = (g.Do + nseg - 1) / nseg;
-    if (zlen < 4) zlen = 4;                            // at least 4 output planes per 2 warm-up planes
-    nseg = (g.Do + zlen - 1) / zlen;
-    zw.nseg = nseg; zw.zlen = zlen;
-    const int items = cols * nseg;
-    const int gx = items < want ? items : want;
+    const int gy = g.Cout / 16;
+    const int gx = z_split(zw, g.Do, gy, 4);           // at least 4 output planes per 2 warm-up planes
     constexpr int lds = 4 * 10 * 20 * 64;
     static std::atomic<uint64_t> attr_done{0};
     set_max_lds_once(attr_done, (const void*)k_mfma_conv_z, lds);
@@ -1366,38 +1357,49 @@ int launch_mfma_conv_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const 
 }
 // dgrad (g = forward geometry).  stride 1: 27-tap conv of dL/dy with the flipped filter.  stride 2: 8-tap conv of
 // dL/dy on the coarse grid producing all 8 output parities at once (rows = 8*Cin), scattered to 2*m + parity.
-int launch_mfma_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
-                           const BnBwdStats* bn) {
+static MfmaConvArgs dgrad_args(const ConvGeom& g, const DstGrad* dst, int ndst) {   // everything but dy and the filter: the stride-1 GEMM view
     MfmaConvArgs a = base_args();
-    a.src[0].ptr = dy; a.src[0].C = g.Cout;
-    a.w = w_mfma_dgrad;
+    a.src[0].C = g.Cout;
     set_dst(a, dst, ndst);
     a.g.Cin = g.Cout; a.g.D = g.Do; a.g.H = g.Ho; a.g.W = g.Wo; a.g.ks = 3; a.g.stride = 1;
     a.oD = g.D; a.oH = g.H; a.oW = g.W;
+    if (g.stride == 1) { a.g.Cout = g.Cin; a.g.Do = g.D; a.g.Ho = g.H; a.g.Wo = g.W; }
+    return a;
+}
+// UNET_NO_DGRAD_BNSTATS / UNET_NO_DGRAD_BNSTATS_SMALL (read once per process): no statistics epilogue in any dgrad / in k_mfma_conv_small's
+static bool bnstats_off() { static const bool off = getenv("UNET_NO_DGRAD_BNSTATS") != nullptr; return off; }
+static bool bnstats_small_off() { static const bool off = getenv("UNET_NO_DGRAD_BNSTATS_SMALL") != nullptr; return off; }
+// The kernels with the norm-backward statistics epilogue: k_mfma_conv_z16 (one 16-channel chunk), k_mfma_conv_small (the 16^3 and smaller
+// levels; the sliding-window kernels need Cin == 32 and never take these) when they WRITE one destination, k_s2_scatter (which may accumulate)
+DgradOutcome mfma_conv_dgrad_outcome(const ConvGeom& g, const DstGrad* dst, int ndst, bool norm) {
+    DgradOutcome o;
+    o.served = true;
+    if (bnstats_off()) norm = false;
+    if (g.stride != 1) { o.rows = s2_conv_dgrad_outcome(g, dst, ndst, norm).rows; return o; }
+    if (!(norm && ndst == 1 && dst[0].ptr && !dst[0].accumulate && dst[0].C == g.Cin)) return o;
+    const MfmaConvArgs a = dgrad_args(g, dst, ndst);
+    if (pick_ck(g.Cout, true) == 16) o.rows = conv_z16_blocks(a);
+    else if (!bnstats_small_off() && a.g.Cin != 32 && small_s1k3(a.g, 32)) o.rows = tile_count(a.g, tile_s1k3(a.g, 32));
+    return o;
+}
+DgradOutcome launch_mfma_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
+                                    const BnBwdStats* bn) {
+    const bool norm = bn && bn->partial && bn->C == dst[0].C;
+    const DgradOutcome o = mfma_conv_dgrad_outcome(g, dst, ndst, norm);
+    MfmaConvArgs a = dgrad_args(g, dst, ndst);
+    a.src[0].ptr = dy;
+    a.w = w_mfma_dgrad;
     if (g.stride == 1) {
-        a.g.Cout = g.Cin; a.g.Do = g.D; a.g.Ho = g.H; a.g.Wo = g.W;
-        static const bool no_bn = getenv("UNET_NO_DGRAD_BNSTATS") != nullptr;
-        if (bn && !no_bn && ndst == 1 && dst[0].ptr && !dst[0].accumulate && bn->C == g.Cin && pick_ck(g.Cout, true) == 16 && conv_z16_applies(a)) {
-            a.bn_u = bn->u; a.bn_stat = bn->stat; a.bn_partial = bn->partial; a.bn_act = bn->act; a.bn_C = bn->C;
-            return launch_conv_z16(a, s);
-        }
-        // ... and of k_mfma_conv_small (the 16^3 and smaller levels; the sliding-window kernels need Cin == 32 and never take these)
-        static const bool no_bn_small = getenv("UNET_NO_DGRAD_BNSTATS_SMALL") != nullptr;
-        if (bn && !no_bn && !no_bn_small && ndst == 1 && dst[0].ptr && !dst[0].accumulate && bn->C == g.Cin && pick_ck(g.Cout, true) == 32 &&
-            a.g.Cin != 32 && small_s1k3(a.g, 32)) {
-            a.bn_u = bn->u; a.bn_stat = bn->stat; a.bn_partial = bn->partial; a.bn_act = bn->act; a.bn_C = bn->C;
-            return launch_s1k3(a, 32, s);
-        }
-        launch_s1k3(a, pick_ck(g.Cout, true), s);
-    } else {
-        static const bool no_bn2 = getenv("UNET_NO_DGRAD_BNSTATS") != nullptr;
-        const int rows = launch_s2_conv_dgrad(g, dy, w_mfma_dgrad, dst, ndst, s, no_bn2 ? nullptr : bn);
-        if (rows) return rows > 0 ? rows : 0;
-        a.g.Cout = 8 * g.Cin; a.sc_C = g.Cin;
-        a.g.Do = (g.D + 1) / 2; a.g.Ho = (g.H + 1) / 2; a.g.Wo = (g.W + 1) / 2;   // coarse positions m with 2m or 2m+1 inside the volume
-        launch_k2sc(a, s);
+        if (o.rows > 0) { a.bn_u = bn->u; a.bn_stat = bn->stat; a.bn_partial = bn->partial; a.bn_act = bn->act; a.bn_C = bn->C; }
+        const int gx = launch_s1k3(a, pick_ck(g.Cout, true), s);
+        return {true, false, a.bn_partial ? gx : 0};
     }
-    return 0;
+    const DgradOutcome s2 = launch_s2_conv_dgrad(g, dy, w_mfma_dgrad, dst, ndst, s, norm && !bnstats_off() ? bn : nullptr);
+    if (s2.served) return s2;
+    a.g.Cout = 8 * g.Cin; a.sc_C = g.Cin;
+    a.g.Do = (g.D + 1) / 2; a.g.Ho = (g.H + 1) / 2; a.g.Wo = (g.W + 1) / 2;   // coarse positions m with 2m or 2m+1 inside the volume
+    launch_k2sc(a, s);
+    return {true, false, 0};
 }
 
 // ================= public: ConvTranspose3d 2x2x2 stride 2 =================

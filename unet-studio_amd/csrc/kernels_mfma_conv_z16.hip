@@ -508,17 +508,8 @@ int launch_conv_z32(const MfmaConvArgs& a0, hipStream_t s) {
     for (int k = 0; k < a0.nsrc; ++k) if (a0.src[k].C % 8) return 0;
     ZWork zw;
     zw.cols_x = (g.Wo + 15) / 16; zw.cols_y = (g.Ho + 7) / 8;
-    const int cols = zw.cols_x * zw.cols_y, gy = g.Cout / 16;
-    int want = 512 / gy;
-    if (want < 1) want = 1;
-    int nseg = (want + cols - 1) / cols;
-    if (nseg < 1) nseg = 1;
-    int zlen = (g.Do + nseg - 1) / nseg;
-    if (zlen < 4) zlen = 4;
-    nseg = (g.Do + zlen - 1) / zlen;
-    zw.nseg = nseg; zw.zlen = zlen;
-    const int items = cols * nseg;
-    const int gx = items < want ? items : want;
+    const int gy = g.Cout / 16;
+    const int gx = z_split(zw, g.Do, gy, 4);           // at least 4 output planes per 2 warm-up planes
     constexpr int lds = 6 * 10 * 18 * 64;
     static std::atomic<uint64_t> attr_done{0};
     set_max_lds_once(attr_done, (const void*)k_mfma_conv_z32, lds);
@@ -526,31 +517,24 @@ int launch_conv_z32(const MfmaConvArgs& a0, hipStream_t s) {
     return gx;
 }
 
-bool conv_z16_applies(const MfmaConvArgs& a0) {
+int conv_z16_blocks(const MfmaConvArgs& a0, ZWork* zw_out) {
     const ConvGeom& g = a0.g;
-    if (sliding_window_off() || g.Cin != 16 || g.ks != 3 || g.stride != 1 || g.Wo < 12 || g.Do < 8 || g.D != g.Do || g.H != g.Ho || g.W != g.Wo) return false;
-    if (g.Cout != 16 && g.Cout != 32) return false;
+    if (sliding_window_off() || g.Cin != 16 || g.ks != 3 || g.stride != 1 || g.Wo < 12 || g.Do < 8 || g.D != g.Do || g.H != g.Ho || g.W != g.Wo) return 0;
+    if (g.Cout != 16 && g.Cout != 32) return 0;
     for (int k = 0; k < 2; ++k)   // outputs are addressed with 31-bit byte offsets through a buffer descriptor
-        if (a0.out[k] && (size_t)a0.oD * a0.oH * a0.oW * a0.outC[k] * 2 >= ((size_t)1 << 31)) return false;
-    if (a0.nout > 1 && a0.outC[0] % 16) return false;
-    return true;
-}
-int launch_conv_z16(const MfmaConvArgs& a0, hipStream_t s) {
-    const ConvGeom& g = a0.g;
-    if (!conv_z16_applies(a0)) return 0;
+        if (a0.out[k] && (size_t)a0.oD * a0.oH * a0.oW * a0.outC[k] * 2 >= ((size_t)1 << 31)) return 0;
+    if (a0.nout > 1 && a0.outC[0] % 16) return 0;
     ZWork zw;
     zw.cols_x = (g.Wo + 15) / 16; zw.cols_y = (g.Ho + 7) / 8;
-    const int cols = zw.cols_x * zw.cols_y;
-    const int gy = g.Cout / 16;                        // one row tile per block (two row tiles: 256 VGPRs and spills)
-    const int want = 512 / gy;                         // two blocks per CU in total
-    int nseg = (want + cols - 1) / cols;
-    if (nseg < 1) nseg = 1;
-    int zlen = (g.Do + nseg - 1) / nseg;
-    if (zlen < 4) zlen = 4;
-    nseg = (g.Do + zlen - 1) / zlen;
-    zw.nseg = nseg; zw.zlen = zlen;
-    const int items = cols * nseg;
-    const int gx = items < want ? items : want;
+    // one row tile per block (two row tiles: 256 VGPRs and spills); at least 4 output planes per 2 warm-up planes
+    const int gx = z_split(zw, g.Do, g.Cout / 16, 4);
+    if (zw_out) *zw_out = zw;
+    return gx;
+}
+int launch_conv_z16(const MfmaConvArgs& a0, hipStream_t s) {
+    ZWork zw;
+    const int gx = conv_z16_blocks(a0, &zw), gy = a0.g.Cout / 16;
+    if (!gx) return 0;
     constexpr int lds = 6 * 10 * 18 * 32;
     if (a0.bn_partial) k_mfma_conv_z16<1, true><<<dim3((unsigned)gx, (unsigned)gy), 256, lds + 6 * 8 * 16 * 32, s>>>(a0, zw);
     else k_mfma_conv_z16<1, false><<<dim3((unsigned)gx, (unsigned)gy), 256, lds, s>>>(a0, zw);

@@ -462,26 +462,35 @@ static int deep_ksplit(int KS, int MG, int NG, int NTT, int Vpad, const DeepScra
     while ((int64_t)MG * NG * ks < 256 && KS / (4 * ks) > 3 && fits(2 * ks)) ks *= 2;
     return ks;
 }
+// The grid of a launch over the GEMM view g with T taps, and whether the scratch holds it (partial tiles; one arrival counter per
+// tile, or per row-tile group when a norm epilogue owns whole channels).  Launches nothing: deep_launch and the dgrad outcome
+// queries both decide by it.
+struct DeepGrid { int V, Vpad, MG, nchunk, ksplit, kper, ntw, NG; bool fits; };
+static DeepGrid deep_grid(const ConvGeom& g, int T, bool norm_epi, const DeepScratch& sc) {
+    DeepGrid d;
+    d.V = g.Do * g.Ho * g.Wo; d.Vpad = (d.V + 63) / 64 * 64; d.MG = d.Vpad / 64;
+    d.nchunk = g.Cin / 32;
+    const int KS = T * d.nchunk, NTT = g.Cout / 16;
+    d.ntw = (NTT % 2 == 0 && (int64_t)d.MG * (NTT / 2) >= 128) ? 2 : 1;   // two row tiles per block only when the grid stays wide
+    d.NG = NTT / d.ntw;
+    d.ksplit = deep_ksplit(KS, d.MG, d.NG, NTT, d.Vpad, sc);
+    d.kper = (KS + d.ksplit - 1) / d.ksplit;
+    d.ksplit = (KS + d.kper - 1) / d.kper;
+    d.fits = (size_t)d.ksplit * NTT * d.Vpad * 16 * 4 <= sc.part_bytes && (norm_epi ? d.NG : d.MG * d.NG) <= sc.ncnt;
+    return d;
+}
 template <int S, int KD, int PAD, bool SC>
 static bool deep_launch(MfmaConvArgs c, int epi, const DeepNormFwd* nf, const DeepNormBwd* nb, const DeepScratch& sc, hipStream_t s) {
+    const DeepGrid d = deep_grid(c.g, KD * KD * KD, epi != DEEP_PLAIN, sc);
+    if (!d.fits) return false;
     DeepArgs a;
     a.c = c;
-    const ConvGeom& g = c.g;
-    a.V = g.Do * g.Ho * g.Wo; a.Vpad = (a.V + 63) / 64 * 64; a.MG = a.Vpad / 64;
-    a.nchunk = g.Cin / 32;
-    const int T = KD * KD * KD, KS = T * a.nchunk, NTT = g.Cout / 16;
-    const int ntw = (NTT % 2 == 0 && (int64_t)a.MG * (NTT / 2) >= 128) ? 2 : 1;   // two row tiles per block only when the grid stays wide
-    const int NG = NTT / ntw;
-    a.ksplit = deep_ksplit(KS, a.MG, NG, NTT, a.Vpad, sc);
-    a.kper = (KS + a.ksplit - 1) / a.ksplit;
-    a.ksplit = (KS + a.kper - 1) / a.kper;
-    if ((size_t)a.ksplit * NTT * a.Vpad * 16 * 4 > sc.part_bytes) return false;
-    const int ncnt = epi == DEEP_PLAIN ? a.MG * NG : NG;
-    if (ncnt > sc.ncnt) return false;
+    a.V = d.V; a.Vpad = d.Vpad; a.MG = d.MG; a.nchunk = d.nchunk; a.ksplit = d.ksplit; a.kper = d.kper;
+    const int ntw = d.ntw;
     a.part = sc.part; a.cnt = sc.cnt;
     if (nf) a.nf = *nf;
     if (nb) a.nb = *nb;
-    const unsigned grid = (unsigned)(a.MG * NG * a.ksplit);
+    const unsigned grid = (unsigned)(a.MG * d.NG * a.ksplit);
 #define DEEP_GO(EPI)                                                                                  \
     do {                                                                                              \
         if (ntw == 2) k_deep_conv<S, KD, PAD, SC, EPI, 2><<<grid, 256, 0, s>>>(a);                    \
@@ -547,38 +556,36 @@ bool launch_deep_convt_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, cons
     a.sc_C = g.Cout; a.oD = g.Do; a.oH = g.Ho; a.oW = g.Wo;
     return deep_launch<1, 1, 0, true>(a, DEEP_PLAIN, nullptr, nullptr, sc, s);
 }
-// returns 0: shape not served; 1: gradient written / accumulated; 2: ... and the destination's norm backward is done (nb given, one destination)
-int launch_deep_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, const DeepNormBwd* nb,
-                           const DeepScratch& sc, hipStream_t s) {
-    if (!sc.part || deep_off() || g.ks != 3 || g.Cout % 32 || g.Cin % 16) return 0;
-    MfmaConvArgs a = deep_base();
-    a.src[0].ptr = dy; a.src[0].C = g.Cout;
-    a.w = w_mfma_dgrad;
-    for (int k = 0; k < 2; ++k) {
-        a.out[k] = k < ndst ? dst[k].ptr : nullptr;
-        a.outC[k] = k < ndst ? dst[k].C : 0;
-        a.out_acc[k] = k < ndst ? dst[k].accumulate : 0;
-    }
-    a.nout = ndst;
-    a.g.Cin = g.Cout; a.g.D = g.Do; a.g.H = g.Ho; a.g.W = g.Wo; a.g.ks = 3; a.g.stride = 1;
-    a.oD = g.D; a.oH = g.H; a.oW = g.W;
-    if (g.stride == 1) {
-        if ((int64_t)g.D * g.H * g.W > DEEP_K3_MAX_VOXELS) return 0;
-        a.g.Cout = g.Cin; a.g.Do = g.D; a.g.Ho = g.H; a.g.Wo = g.W;
-        const bool fuse = nb && ndst == 1 && dst[0].ptr && dst[0].C == g.Cin;
-        return deep_launch<1, 3, 1, false>(a, fuse ? DEEP_BWD_NORM : DEEP_PLAIN, nullptr, fuse ? nb : nullptr, sc, s) ? (fuse ? 2 : 1) : 0;
-    }
+// ---- the input gradients of a conv k3 (stride 1: 27 taps; stride 2: the scatter kind) and of a conv_trans k2 s2 (transposed) ----
+// the GEMM view of the dgrad with forward geometry g; false: no kernel here takes the shape
+static bool deep_dgrad_view(const ConvGeom& g, bool transposed, ConvGeom* v) {
+    if (deep_off() || g.Cout % 32 || g.Cin % 16 || (!transposed && g.ks != 3)) return false;
+    *v = ConvGeom();
+    v->Cin = g.Cout; v->Cout = g.Cin; v->D = g.Do; v->H = g.Ho; v->W = g.Wo; v->Do = g.D; v->Ho = g.H; v->Wo = g.W;
+    const int64_t fine = (int64_t)g.D * g.H * g.W;
+    if (transposed) { v->ks = 2; v->stride = 2; return g.W <= 8 && fine <= DEEP_MAX_VOXELS; }
+    if (g.stride == 1) return fine <= DEEP_K3_MAX_VOXELS;
     // stride 2: 8 taps over dL/dy on the coarse grid, rows = 8 output parities x Cin, scattered to 2 * m + parity
-    a.g.Cout = 8 * g.Cin; a.sc_C = g.Cin;
-    a.g.Do = (g.D + 1) / 2; a.g.Ho = (g.H + 1) / 2; a.g.Wo = (g.W + 1) / 2;
-    if ((int64_t)a.g.Do * a.g.Ho * a.g.Wo > DEEP_MAX_VOXELS) return 0;
-    return deep_launch<1, 2, 0, true>(a, DEEP_PLAIN, nullptr, nullptr, sc, s) ? 1 : 0;
+    v->Cout = 8 * g.Cin;
+    v->Do = (g.D + 1) / 2; v->Ho = (g.H + 1) / 2; v->Wo = (g.W + 1) / 2;
+    return (int64_t)v->Do * v->Ho * v->Wo <= DEEP_MAX_VOXELS;
 }
-bool launch_deep_convt_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst, const DeepNormBwd* nb,
-                             const DeepScratch& sc, int* norm_done, hipStream_t s) {
-    if (norm_done) *norm_done = 0;
-    if (!sc.part || deep_off() || g.Cout % 32 || g.Cin % 16 || g.W > 8 || (int64_t)g.D * g.H * g.W > DEEP_MAX_VOXELS) return false;
+// The norm epilogue: for one destination that takes every row (written or accumulated), by the kinds that do not scatter.
+DgradOutcome deep_dgrad_outcome(const ConvGeom& g, bool transposed, const DstGrad* dst, int ndst, bool norm, const DeepScratch& sc) {
+    DgradOutcome o;
+    ConvGeom v;
+    if (!sc.part || !deep_dgrad_view(g, transposed, &v)) return o;
+    const bool k3 = !transposed && g.stride == 1, scatter = !transposed && !k3;
+    const bool fuse = !scatter && norm && ndst == 1 && dst[0].ptr && dst[0].C == g.Cin;
+    o.served = deep_grid(v, k3 ? 27 : 8, fuse, sc).fits;
+    o.norm_done = o.served && fuse;
+    return o;
+}
+DgradOutcome launch_deep_dgrad(const ConvGeom& g, bool transposed, const void* dy, const void* w_mfma_dgrad, const DstGrad* dst, int ndst,
+                               const DeepNormBwd* nb, const DeepScratch& sc, hipStream_t s) {
+    const DgradOutcome o = deep_dgrad_outcome(g, transposed, dst, ndst, nb != nullptr, sc);
     MfmaConvArgs a = deep_base();
+    if (!o.served || !deep_dgrad_view(g, transposed, &a.g)) return DgradOutcome();
     a.src[0].ptr = dy; a.src[0].C = g.Cout;
     a.w = w_mfma_dgrad;
     for (int k = 0; k < 2; ++k) {
@@ -587,13 +594,14 @@ bool launch_deep_convt_dgrad(const ConvGeom& g, const void* dy, const void* w_mf
         a.out_acc[k] = k < ndst ? dst[k].accumulate : 0;
     }
     a.nout = ndst;
-    a.g.Cin = g.Cout; a.g.Cout = g.Cin; a.g.D = g.Do; a.g.H = g.Ho; a.g.W = g.Wo; a.g.Do = g.D; a.g.Ho = g.H; a.g.Wo = g.W;
-    a.g.ks = 2; a.g.stride = 2;
     a.oD = g.D; a.oH = g.H; a.oW = g.W;
-    const bool fuse = nb && ndst == 1 && dst[0].ptr && dst[0].C == g.Cin;
-    if (!deep_launch<2, 2, 0, false>(a, fuse ? DEEP_BWD_NORM : DEEP_PLAIN, nullptr, fuse ? nb : nullptr, sc, s)) return false;
-    if (norm_done) *norm_done = fuse ? 1 : 0;
-    return true;
+    const int epi = o.norm_done ? DEEP_BWD_NORM : DEEP_PLAIN;
+    if (!o.norm_done) nb = nullptr;
+    bool ran;   // (first instantiations in this order keep the kernels' order in the code object, which asm_loads_check_deep.json records)
+    if (!transposed && g.stride == 1) ran = deep_launch<1, 3, 1, false>(a, epi, nullptr, nb, sc, s);
+    else if (!transposed) { a.sc_C = g.Cin; ran = deep_launch<1, 2, 0, true>(a, DEEP_PLAIN, nullptr, nullptr, sc, s); }
+    else ran = deep_launch<2, 2, 0, false>(a, epi, nullptr, nb, sc, s);
+    return ran ? o : DgradOutcome();
 }
 
 }  // namespace unet

@@ -323,19 +323,15 @@ __global__ void __launch_bounds__(256, 2) k_s2_scatter(S2ScatterArgs a) {
 
 // ---- launch ----
 static bool s2_off() { return sliding_window_off(); }     // UNET_NO_SLIDING_WINDOW: k_mfma_conv_p for every shape
-static void s2_work(S2ScatterArgs& a, int gy, int* gx) {
-    a.cols_x = (a.cW + 15) / 16; a.cols_y = (a.cH + 1) / 2;
-    const int cols = a.cols_x * a.cols_y;
-    int want = 512 / gy;
-    if (want < 1) want = 1;
-    int nseg = (want + cols - 1) / cols;
-    if (nseg < 1) nseg = 1;
-    int zlen = (a.cD + nseg - 1) / nseg;
-    if (zlen < 2) zlen = 2;
-    if (zlen > a.cD) zlen = a.cD;
-    a.nseg = (a.cD + zlen - 1) / zlen; a.zlen = zlen;
-    const int items = cols * a.nseg;
-    *gx = items < want ? items : want;
+// the work split over the coarse grid a.cD x a.cH x a.cW (columns of BY x 16 voxels x z segments; scatter and gather arguments alike);
+// returns gridDim.x
+template <int BY, class Args>
+static int s2_work(Args& a, int gy) {
+    ZWork zw;
+    zw.cols_x = (a.cW + 15) / 16; zw.cols_y = (a.cH + BY - 1) / BY;
+    const int gx = z_split(zw, a.cD, gy, 2);
+    a.cols_x = zw.cols_x; a.cols_y = zw.cols_y; a.nseg = zw.nseg; a.zlen = zw.zlen;
+    return gx;
 }
 template <int TR, int KS, bool ACC, bool BNS>
 static void launch_scatter_t(const S2ScatterArgs& a, int gx, int gy, hipStream_t s) {
@@ -348,23 +344,38 @@ static void launch_scatter_t(const S2ScatterArgs& a, int gx, int gy, hipStream_t
     k_s2_scatter<TR, KS, ACC, BNS><<<dim3((unsigned)gx, (unsigned)gy), 256, lds, s>>>(a);
 }
 
-// Conv3d(k3, s2) input gradient (g = forward geometry).  Returns 0 when the shape is not served (the caller uses k_mfma_conv_p),
-// else the number of norm-backward partial rows written when bn was given (the grid's x size), or -1 when it ran without statistics.
-int launch_s2_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_s2_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
-                         const BnBwdStats* bn) {
-    if (s2_off() || g.ks != 3 || g.stride != 2 || ndst != 1 || !dst[0].ptr || dst[0].C != g.Cin) return 0;
-    if (g.Cin % 16 || (g.Cout != 32 && g.Cout != 64) || g.Wo < 16 || g.Do < 4) return 0;
-    if ((size_t)g.D * g.H * g.W * g.Cin * 2 >= ((size_t)1 << 31)) return 0;       // 31-bit buffer offsets
+// Conv3d(k3, s2) input gradient (g = forward geometry).  The decision and the work split, shared by the outcome query and the launcher:
+// a's coarse grid and split, *gx = gridDim.x = the norm-backward partial rows when the destination's norm is offered
+static DgradOutcome s2_dgrad_plan(const ConvGeom& g, const DstGrad* dst, int ndst, bool norm, S2ScatterArgs& a, int* gx) {
+    DgradOutcome o;
+    if (s2_off() || g.ks != 3 || g.stride != 2 || ndst != 1 || !dst[0].ptr || dst[0].C != g.Cin) return o;
+    if (g.Cin % 16 || (g.Cout != 32 && g.Cout != 64) || g.Wo < 16 || g.Do < 4) return o;
+    if ((size_t)g.D * g.H * g.W * g.Cin * 2 >= ((size_t)1 << 31)) return o;       // 31-bit buffer offsets
+    a.cD = g.Do; a.cH = g.Ho; a.cW = g.Wo;
+    *gx = s2_work<2>(a, g.Cin / 16);
+    o.served = true;
+    o.rows = norm ? *gx : 0;
+    return o;
+}
+DgradOutcome s2_conv_dgrad_outcome(const ConvGeom& g, const DstGrad* dst, int ndst, bool norm) {
     S2ScatterArgs a;
-    a.src = dy; a.srcC = g.Cout; a.cD = g.Do; a.cH = g.Ho; a.cW = g.Wo;
+    int gx = 0;
+    return s2_dgrad_plan(g, dst, ndst, norm, a, &gx);
+}
+// not served: the caller uses k_mfma_conv_p.  The destination may be ACCUMULATED into, with or without the statistics rows
+DgradOutcome launch_s2_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_s2_dgrad, const DstGrad* dst, int ndst, hipStream_t s,
+                                  const BnBwdStats* bn) {
+    S2ScatterArgs a;
+    int gx = 0;
+    const bool bns = bn && bn->partial && bn->C == g.Cin;
+    const DgradOutcome o = s2_dgrad_plan(g, dst, ndst, bns, a, &gx);
+    if (!o.served) return o;
+    a.src = dy; a.srcC = g.Cout;
     a.w = w_s2_dgrad; a.bias = nullptr;
     a.out = dst[0].ptr; a.outC = g.Cin; a.fD = g.D; a.fH = g.H; a.fW = g.W; a.ntt = g.Cin / 16;
     const bool acc = dst[0].accumulate != 0;
-    const bool bns = bn && bn->partial && bn->C == g.Cin;
     if (bns) { a.bn_u = bn->u; a.bn_stat = bn->stat; a.bn_partial = bn->partial; a.bn_act = bn->act; a.bn_C = bn->C; }
-    int gx = 0;
     const int gy = g.Cin / 16;
-    s2_work(a, gy, &gx);
     const int ks = g.Cout / 32;
 #define S2_GO(KS_)                                                                   \
     do {                                                                             \
@@ -375,7 +386,7 @@ int launch_s2_conv_dgrad(const ConvGeom& g, const void* dy, const void* w_s2_dgr
     } while (0)
     if (ks == 1) S2_GO(1); else S2_GO(2);
 #undef S2_GO
-    return bns ? gx : -1;
+    return o;
 }
 int s2_conv_dgrad_rows_max() { return 512; }
 
@@ -388,9 +399,7 @@ bool launch_s2_convt_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const 
     a.src = src[0].ptr; a.srcC = g.Cin; a.cD = g.D; a.cH = g.H; a.cW = g.W;
     a.w = w_mfma; a.bias = bias;
     a.out = out; a.outC = g.Cout; a.fD = g.Do; a.fH = g.Ho; a.fW = g.Wo; a.ntt = g.Cout / 16;
-    int gx = 0;
-    const int gy = g.Cout / 16;
-    s2_work(a, gy, &gx);
+    const int gy = g.Cout / 16, gx = s2_work<2>(a, gy);
     if (g.Cin == 32) launch_scatter_t<1, 1, false, false>(a, gx, gy, s);
     else if (g.Cin == 64) launch_scatter_t<1, 2, false, false>(a, gx, gy, s);
     else launch_scatter_t<1, 4, false, false>(a, gx, gy, s);
@@ -616,20 +625,6 @@ __global__ void __launch_bounds__(256, 2) k_s2_gather(S2GatherArgs a) {
     }
 }
 
-static void s2_gather_work(S2GatherArgs& a, int gy, int* gx) {
-    a.cols_x = (a.cW + 15) / 16; a.cols_y = (a.cH + 3) / 4;
-    const int cols = a.cols_x * a.cols_y;
-    int want = 512 / gy;
-    if (want < 1) want = 1;
-    int nseg = (want + cols - 1) / cols;
-    if (nseg < 1) nseg = 1;
-    int zlen = (a.cD + nseg - 1) / nseg;
-    if (zlen < 2) zlen = 2;
-    if (zlen > a.cD) zlen = a.cD;
-    a.nseg = (a.cD + zlen - 1) / zlen; a.zlen = zlen;
-    const int items = cols * a.nseg;
-    *gx = items < want ? items : want;
-}
 template <int KS, int CIN, int WM>
 static void launch_gather_t(const S2GatherArgs& a, int gx, int gy, hipStream_t s) {
     constexpr int HY = 8 + (KS == 3 ? 1 : 0), HXV = (KS == 3 ? 17 : 16) + 16, UNITS = HY * HXV * (CIN / 8), UPW = (UNITS + 3) / 4;
@@ -669,8 +664,7 @@ int launch_s2_conv_fwd(const ConvGeom& g, const SrcDesc* src, int nsrc, const vo
     a.fD = g.D; a.fH = g.H; a.fW = g.W;
     a.w = w_mfma; a.bias = bias; a.out = out; a.outC = g.Cout; a.cD = g.Do; a.cH = g.Ho; a.cW = g.Wo; a.stats = stats_partial;
     const int wm = s2_wm(g.Cout, 3, g.Cin), gy = g.Cout / (16 * wm);
-    int gx = 0;
-    s2_gather_work(a, gy, &gx);
+    const int gx = s2_work<4>(a, gy);
     launch_gather<3>(a, g.Cin, wm, gx, gy, s);
     return gx;
 }
@@ -684,8 +678,7 @@ bool launch_s2_convt_dgrad(const ConvGeom& g, const void* dy, const void* w_mfma
     a.fD = g.Do; a.fH = g.Ho; a.fW = g.Wo;
     a.w = w_mfma_dgrad; a.bias = nullptr; a.out = dst[0].ptr; a.outC = g.Cin; a.cD = g.D; a.cH = g.H; a.cW = g.W; a.stats = nullptr;
     const int wm = s2_wm(g.Cin, 2, g.Cout), gy = g.Cin / (16 * wm);
-    int gx = 0;
-    s2_gather_work(a, gy, &gx);
+    const int gx = s2_work<4>(a, gy);
     launch_gather<2>(a, g.Cout, wm, gx, gy, s);
     return true;
 }

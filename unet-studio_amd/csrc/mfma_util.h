@@ -92,10 +92,25 @@ struct MfmaConvArgs {
 
 // work split of the sliding-window kernels: (y, x) columns of the footprint x z segments of zlen output planes
 struct ZWork { int nseg, zlen, cols_x, cols_y; };
+// The z split of zw's columns over `planes` output planes for blocks of gy row tiles each: segments of at least min_zlen planes (the
+// warm-up planes of a segment are overhead), enough of them for 512 blocks in all (two per CU).  Sets nseg and zlen, returns gridDim.x
+// (= the number of statistics rows of a kernel with a statistics epilogue)
+inline int z_split(ZWork& zw, int planes, int gy, int min_zlen) {
+    const int cols = zw.cols_x * zw.cols_y;
+    int want = 512 / gy;
+    if (want < 1) want = 1;
+    const int nseg = (want + cols - 1) / cols;
+    int zlen = (planes + nseg - 1) / nseg;
+    if (zlen < min_zlen) zlen = min_zlen;
+    if (zlen > planes) zlen = planes;
+    zw.nseg = (planes + zlen - 1) / zlen; zw.zlen = zlen;
+    const int items = cols * zw.nseg;
+    return items < want ? items : want;
+}
 // sliding window for a single 16-channel chunk (kernels_mfma_conv_z16.hip); returns 0 if the geometry does not qualify, else the
 // number of statistics rows (gridDim.x)
 int launch_conv_z16(const MfmaConvArgs& a, hipStream_t s);
-bool conv_z16_applies(const MfmaConvArgs& a);               // the geometry test of launch_conv_z16 alone
+int conv_z16_blocks(const MfmaConvArgs& a, ZWork* zw = nullptr);   // the geometry test and work split of launch_conv_z16 alone: its return value
 int launch_conv_z32(const MfmaConvArgs& a, hipStream_t s);     // the same for a single 32-channel chunk
 // kernels_mfma_wgrad_zd.hip: k_mfma_wgrad_z's 4-wave configurations with LDS-DMA staging (called by launch_mfma_wgrad_z with its own work split)
 bool launch_wgrad_zd(const ConvGeom& g, const SrcDesc* src, int nsrc, const void* dy, float* slab, float* bias_slab, int wk, int pa, int pb, int cols_x,
