@@ -190,7 +190,10 @@ int unet_sgd_step_packed(const unet_plan* plan, float* params_flat, float* grads
 
 /* ---- single-op surface (unit tests, parity per kernel).  Activations are channels-last [D][H][W][C]
  * in the element type of `dtype`; weights/bias/grads fp32 in torch layout ([Cout,Cin,k,k,k]; conv_trans
- * [Cin,Cout,2,2,2]).  impl: UNET_IMPL_*.  scratch: at least unet_op_scratch_bytes() bytes. ---- */
+ * [Cin,Cout,2,2,2]).  impl: UNET_IMPL_*.  scratch: at least unet_op_scratch_bytes() bytes.
+ * The conv / conv_trans entries choose the kernel family as a plan does (choose_conv, csrc/conv_select.h) and launch it through the
+ * functions a plan's executor launches it through (conv_fwd, conv_dgrad, conv_wgrad in csrc/engine.cpp); unet_op_conv3d_fwd_fused
+ * alone keeps off the deep levels' split-K kernel and runs the fp32 first conv on the direct kernel. ---- */
 int unet_op_scratch_bytes(int cin, int cout, int D, int H, int W, size_t* bytes);
 /* Which kernel family each direction of a conv (transposed = 0) or conv_trans (transposed = 1; ks and stride ignored) of this
  * shape runs on in the entry points below, for one plain source: out = {forward, dgrad, wgrad}.  Read-only, launches nothing.

@@ -1,6 +1,7 @@
 """GPU (-m gpu): a conv and the norm layer next to it, per layer, against a float64 reference of the same layer.
 
-unet_op_conv3d_fwd_norm and unet_op_conv3d_bwd_data_norm (include/unet_hip.h) run what the executor runs for such a layer: on the
+unet_op_conv3d_fwd_norm and unet_op_conv3d_bwd_data_norm (include/unet_hip.h) launch the conv through the functions the executor
+launches it through (conv_fwd, conv_dgrad in csrc/engine.cpp) and the norm's own launches through norm_fwd_passes / norm_bwd_passes: on the
 deep levels one split-K launch of kernels_mfma_deep.hip with the norm in the epilogue of the block that draws the last ticket
 (DEEP_FWD_NORM: conv, statistics, running statistics, activated copy; DEEP_BWD_NORM: dgrad, the norm's backward sums, coef,
 dgamma / dbeta, dL/d(raw)), elsewhere the MFMA conv and the norm's separate launches (k_norm_finalize_apply8, k_norm_bwd_*).  The

@@ -15,7 +15,9 @@ struct ConvChoice {
     Fwd fwd = Fwd::direct;
     Dgrad dgrad = Dgrad::direct;
     Wgrad wgrad = Wgrad::direct;
-    bool mfma_fwd() const { return fwd == Fwd::deep || fwd == Fwd::mfma; }   // the forward reads the bf16 MFMA filter pack
+    // which filter form the forward reads: the bf16 MFMA pack, the fp32 torch-layout parameter itself, else the fp32 tap-major copy
+    bool mfma_fwd() const { return fwd == Fwd::deep || fwd == Fwd::mfma; }
+    bool param_fwd() const { return fwd == Fwd::head || fwd == Fwd::first_mfma || fwd == Fwd::first_f32_mfma; }
 };
 
 // src: the sources as the op reads them (channel counts; a norm + activation applied on read rules out the matrix-core kernels that take

@@ -522,6 +522,100 @@ DgradOutcome mfma_dgrad(const ConvGeom& g, bool transposed, const void* dy, cons
     return want;
 }
 
+// conv_fwd, conv_dgrad and conv_wgrad: the launch of each direction of a conv / conv_trans from its ConvChoice member (conv_select.h),
+// shared by the executor and the single-op surface and the only places of this file that map Fwd / Dgrad / Wgrad to launchers.  The
+// callers keep the scheduling: the stream, when which filter form is packed, the forks, where the slabs lie.
+struct FwdRan {
+    int rows = 0;            // statistics partial rows the launch left in `part`
+    bool dbl = false;        // ... as fp64 rows (the fp32 matrix-core convs)
+    bool norm_done = false;  // the deep kernel ran the whole norm layer `nf` in its epilogue
+};
+// The three filter forms a family may read: w the fp32 torch-layout parameter, wf its fp32 tap-major copy (launch_pack_conv_w /
+// launch_pack_convt_w), wm the bf16 MFMA pack -- only the one f reads (ConvChoice::mfma_fwd / param_fwd) need be there.  out_ncdhw
+// (optional; head and direct): the fp32 NCDHW result; a head then writes no channels-last copy.  part (optional): where the
+// statistics rows of `out` go.  nf (optional): the norm + activation behind the conv, offered to the deep kernel's epilogue.  An
+// empty DeepScratch keeps the deep levels' split-K kernels out (they decline: the mfma kernels run).
+FwdRan conv_fwd(Fwd f, bool transposed, int dtype, const ConvGeom& g, const SrcDesc* src, int nsrc, const float* w, const float* wf,
+                const void* wm, const float* bias, void* out, float* out_ncdhw, float* part, const DeepNormFwd* nf, const DeepScratch& deep,
+                hipStream_t s) {
+    FwdRan r;
+    int rows = 0;
+    switch (f) {
+        case Fwd::deep:
+        case Fwd::mfma:
+            if (transposed) {
+                if (!launch_deep_convt_fwd(g, src, nsrc, wm, bias, out, deep, s)) launch_mfma_convt_fwd(g, src, nsrc, wm, bias, out, s);
+                return r;
+            }
+            // the deep levels: split-K kernel, the norm layer behind the conv in its epilogue (statistics, running statistics,
+            // activated copy: the caller's norm passes have nothing left to do)
+            if (f == Fwd::deep && launch_deep_conv_fwd(g, src, nsrc, wm, bias, out, nf, deep, s)) {
+                r.norm_done = nf != nullptr;
+                return r;
+            }
+            rows = launch_mfma_conv_fwd(g, src, nsrc, wm, bias, out, part, s);
+            break;
+        case Fwd::head:
+            launch_head_fwd(dtype, g, src[0], w, bias, out_ncdhw ? nullptr : out, out_ncdhw, s);
+            return r;
+        case Fwd::first_mfma:
+            rows = launch_conv_first_mfma(g, src, w, bias, out, part, s);
+            break;
+        case Fwd::first_f32_mfma:
+            // fp32 engine, Cin = 1: the first conv on the fp32 matrix cores (filter read in torch layout), statistics in its epilogue
+            rows = launch_conv_first_f32_mfma(g, src, w, bias, (float*)out, (double*)part, s);
+            r.dbl = true;
+            break;
+        case Fwd::f32_mfma:
+            if (transposed) { launch_convt_f32_mfma(g, src, wf, bias, (float*)out, s); return r; }
+            // fp32 engine: the same IEEE fp32 products and sums as the VALU kernel below, on the fp32 matrix cores
+            rows = launch_conv_f32_mfma(g, src, nsrc, wf, bias, (float*)out, s, (double*)part);
+            r.dbl = true;
+            break;
+        case Fwd::direct:
+            if (transposed) launch_convt_fwd_direct(dtype, g, src, nsrc, wf, bias, out, s);
+            else launch_conv_fwd_direct(dtype, g, src, nsrc, wf, bias, out, out_ncdhw, s);
+            return r;
+    }
+    r.rows = part ? rows : 0;
+    return r;
+}
+// The input gradient: wm the bf16 MFMA dgrad pack, wd the fp32 tap-major dgrad copy (the one d reads).  nb, partial, deep and the
+// returned outcome as mfma_dgrad's: only the matrix-core family has norm epilogues, the others leave the whole norm backward to
+// the caller.  launch == false: the outcome alone.
+DgradOutcome conv_dgrad(Dgrad d, bool transposed, int dtype, const ConvGeom& g, const void* dy, const void* wm, const float* wd,
+                        const DstGrad* dst, int ndst, const DeepNormBwd* nb, float* partial, const DeepScratch& deep, hipStream_t s,
+                        bool launch = true) {
+    if (d == Dgrad::mfma) return mfma_dgrad(g, transposed, dy, wm, dst, ndst, nb, partial, deep, s, launch);
+    DgradOutcome o;
+    o.served = true;
+    if (!launch) return o;
+    if (d == Dgrad::f32_mfma) launch_conv_f32_mfma_dgrad(g, (const float*)dy, wd, dst, ndst, s);
+    else if (transposed) launch_convt_dgrad_direct(dtype, g, dy, wd, dst, ndst, s);
+    else launch_conv_dgrad_direct(dtype, g, dy, wd, dst, ndst, s);
+    return o;
+}
+// The weight (+ bias) gradient, added into dw / db.  scratch: the slab region (the direct kernels take nullptr: no split of the voxel
+// range); defer: the matrix-core slab kernels only write their slab, the caller's batched reduce sums it; polite: see kernels.h
+// (the bf16 matrix-core kernels; the same value as given to *_scratch_bytes / *_splits); nbf (optional): the first conv applies the
+// norm backward's element-wise pass as it stages dy.
+void conv_wgrad(Wgrad w, bool transposed, int dtype, const ConvGeom& g, const SrcDesc* src, int nsrc, const void* dy, float* dw, float* db,
+                void* scratch, hipStream_t s, bool defer, int polite, const NormBwdFuse* nbf) {
+    switch (w) {
+        case Wgrad::first_mfma: launch_conv_first_wgrad_mfma(g, src, dy, dw, db, scratch, s, defer, nbf); break;
+        case Wgrad::mfma:
+            if (transposed) launch_mfma_convt_wgrad(g, src, dy, dw, scratch, s, defer, db, polite);
+            else launch_mfma_conv_wgrad(g, src, nsrc, dy, dw, db, scratch, s, defer, polite);
+            break;
+        case Wgrad::f32_mfma: launch_wgrad_f32_mfma(g, src, nsrc, (const float*)dy, dw, db, scratch, s); break;
+        case Wgrad::small: launch_conv_wgrad_small(dtype, g, src, nsrc, dy, dw, db, scratch, s); break;
+        case Wgrad::direct:
+            if (transposed) launch_convt_wgrad_direct(dtype, g, src, nsrc, dy, dw, db, scratch, s);
+            else launch_conv_wgrad_direct(dtype, g, src, nsrc, dy, dw, db, scratch, s);
+            break;
+    }
+}
+
 struct Exec {
     const unet_plan& p;
     char* ws;
@@ -537,8 +631,9 @@ struct Exec {
     }
     int* deep_cnt() const { return p.deep_part_bytes ? (int*)(ws + p.deep_cnt_off) : nullptr; }
 
+    void* at(size_t off) const { return off == SIZE_MAX ? nullptr : ws + off; }   // a region the plan may not have laid out
     void* tptr(int t) const { return ws + p.t_off[t]; }
-    void* gptr(int t) const { return p.g_off[t] == SIZE_MAX ? nullptr : ws + p.g_off[t]; }
+    void* gptr(int t) const { return at(p.g_off[t]); }
     float* stat(int n) const { return (float*)(ws + p.n_stat[n]); }
     float* coef(int n) const { return (float*)(ws + p.n_coef[n]); }
     float* partial() const { return (float*)(ws + p.partial_off); }
@@ -628,6 +723,7 @@ struct Exec {
                 case OP_CONV:
                 case OP_CONVT: {
                     if (op.out_level >= 0 && !(outs && outs[op.out_level])) break;  // result not wanted
+                    const bool convt = op.kind == OP_CONVT;
                     SrcDesc sd[2] = {src(op.src[0]), op.nsrc > 1 ? src(op.src[1]) : SrcDesc()};
                     ConvGeom cg = geom(op);
                     float* wf = (float*)(ws + p.w_fwd[i]);
@@ -636,76 +732,40 @@ struct Exec {
                     const ConvChoice& c = p.conv[i];
                     const Tensor& T = g.tensors[op.dst];
                     const bool want_stats = T.norm >= 0 && !(g.norms[T.norm].batch && mode == 0);
-                    if (op.kind == OP_CONVT) {
-                        if (c.mfma_fwd()) {
-                            need_packs((int)i);
-                            if (!packed) launch_mfma_pack_convt_w(params[op.weight], ws + p.wm_fwd[i], mode == 1 ? ws + p.wm_dgrad[i] : nullptr, cg, s);
-                            if (!(deep_on && launch_deep_convt_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), deep(), s)))
-                                launch_mfma_convt_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), s);
-                            break;
-                        }
-                        if (!packs_current) launch_pack_convt_w(params[op.weight], wf, wd, op.cin, op.cout, s);
-                        if (c.fwd == Fwd::f32_mfma) launch_convt_f32_mfma(cg, sd, wf, params[op.bias], (float*)tptr(op.dst), s);
-                        else launch_convt_fwd_direct(p.dtype, cg, sd, op.nsrc, wf, params[op.bias], tptr(op.dst), s);
-                        break;
+                    // the bf16 filter packs: the batched launch above, else made here
+                    if (c.mfma_fwd()) {
+                        need_packs((int)i);
+                        void* const wmd = (mode == 1 && c.dgrad == Dgrad::mfma) ? ws + p.wm_dgrad[i] : nullptr;
+                        if (!packed && convt) launch_mfma_pack_convt_w(params[op.weight], ws + p.wm_fwd[i], wmd, cg, s);
+                        else if (!packed) launch_mfma_pack_conv_w(params[op.weight], ws + p.wm_fwd[i], wmd, cg, s);
                     }
-                    float* const part = want_stats ? partial() : nullptr;
-                    int rows = 0;              // statistics partial rows the conv left in part
-                    switch (c.fwd) {
-                        case Fwd::deep:
-                        case Fwd::mfma:
-                            need_packs((int)i);
-                            if (!packed)
-                                launch_mfma_pack_conv_w(params[op.weight], ws + p.wm_fwd[i],
-                                                        (mode == 1 && c.dgrad == Dgrad::mfma) ? ws + p.wm_dgrad[i] : nullptr, cg, s);
-                            if (mode == 1 && c.dgrad != Dgrad::mfma && !packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
-                            // the deep levels: split-K kernel, the norm layer behind the conv in its epilogue (statistics, running statistics,
-                            // activated copy: the OP_NORM that follows has nothing left to do)
-                            if (c.fwd == Fwd::deep && deep_on) {
-                                DeepNormFwd nf;
-                                const bool fuse = T.norm >= 0 && p.a_off[op.dst] != SIZE_MAX;
-                                if (fuse) {
-                                    const Norm& n = g.norms[T.norm];
-                                    nf = {params[n.gamma], params[n.beta], n.eps, stat(T.norm), n.batch ? buffers[n.buffer] : nullptr,
-                                          n.batch ? buffers[n.buffer + 1] : nullptr, 0.1, (n.batch && mode == 0) ? 1 : 0, T.act, ws + p.a_off[op.dst]};
-                                }
-                                if (launch_deep_conv_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), fuse ? &nf : nullptr, deep(), s)) {
-                                    if (fuse) fused_done[T.norm] = 1;
-                                    break;
-                                }
-                            }
-                            rows = launch_mfma_conv_fwd(cg, sd, op.nsrc, ws + p.wm_fwd[i], params[op.bias], tptr(op.dst), part, s);
-                            break;
-                        case Fwd::head:   // results[level] straight from the source tensor (the channels-last copy only if nobody asked for the level)
-                            launch_head_fwd(p.dtype, cg, sd[0], params[op.weight], params[op.bias], outs[op.out_level] ? nullptr : tptr(op.dst),
-                                            outs[op.out_level], s);
-                            break;
-                        case Fwd::first_mfma:
-                            rows = launch_conv_first_mfma(cg, sd, params[op.weight], params[op.bias], tptr(op.dst), part, s);
-                            // the fp32 [tap][cin][cout] copies are read by the direct dgrad only: not made when the input needs no gradient
-                            if (mode == 1 && !packs_current && g.tensors[op.src[0]].needs_grad)
-                                launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
-                            break;
-                        case Fwd::first_f32_mfma:
-                            // fp32 engine, Cin = 1: the first conv on the fp32 matrix cores (filter read in torch layout), statistics in its epilogue
-                            rows = launch_conv_first_f32_mfma(cg, sd, params[op.weight], params[op.bias], (float*)tptr(op.dst), (double*)part, s);
-                            if (mode == 1 && !packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
-                            break;
-                        case Fwd::f32_mfma:
-                            // fp32 engine: the same IEEE fp32 products and sums as the VALU kernel below, on the fp32 matrix cores
-                            if (!packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
-                            rows = launch_conv_f32_mfma(cg, sd, op.nsrc, wf, params[op.bias], (float*)tptr(op.dst), s, (double*)part);
-                            break;
-                        case Fwd::direct:
-                            if (!packs_current) launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
-                            launch_conv_fwd_direct(p.dtype, cg, sd, op.nsrc, wf, params[op.bias], tptr(op.dst),
-                                                   op.out_level >= 0 ? outs[op.out_level] : nullptr, s);
-                            break;
+                    // the fp32 tap-major copies [wf | wd]: for a forward that reads wf, and in training for a dgrad off the bf16 matrix cores,
+                    // which reads wd (not a head's: its fused backward reads the parameter; the bf16 first conv's only when its input needs a
+                    // gradient).  Behind the launch where the forward reads the parameter itself: off the first conv's path
+                    const bool copies = !packs_current && ((!c.mfma_fwd() && !c.param_fwd()) ||
+                                                           (mode == 1 && c.dgrad != Dgrad::mfma && c.fwd != Fwd::head &&
+                                                            (c.fwd != Fwd::first_mfma || g.tensors[op.src[0]].needs_grad)));
+                    auto pack_copies = [&]() {
+                        if (convt) launch_pack_convt_w(params[op.weight], wf, wd, op.cin, op.cout, s);
+                        else launch_pack_conv_w(params[op.weight], wf, wd, op.cin, op.cout, k3, s);
+                    };
+                    if (copies && !c.param_fwd()) pack_copies();
+                    // the deep levels' split-K kernel takes the norm layer behind the conv into its epilogue: the OP_NORM that follows has
+                    // nothing left to do
+                    DeepNormFwd nf;
+                    const bool fuse = deep_on && T.norm >= 0 && p.a_off[op.dst] != SIZE_MAX;
+                    if (fuse) {
+                        const Norm& n = g.norms[T.norm];
+                        nf = {params[n.gamma], params[n.beta], n.eps, stat(T.norm), n.batch ? buffers[n.buffer] : nullptr,
+                              n.batch ? buffers[n.buffer + 1] : nullptr, 0.1, (n.batch && mode == 0) ? 1 : 0, T.act, ws + p.a_off[op.dst]};
                     }
-                    if (want_stats) {   // (the fp32 matrix-core convs leave fp64 rows)
-                        fused_blocks[T.norm] = rows;
-                        fused_dbl[T.norm] = c.fwd == Fwd::first_f32_mfma || c.fwd == Fwd::f32_mfma;
-                    }
+                    // (results[level] is written by the conv itself)
+                    const FwdRan r = conv_fwd(c.fwd, convt, p.dtype, cg, sd, op.nsrc, params[op.weight], wf, at(p.wm_fwd[i]), params[op.bias],
+                                              tptr(op.dst), op.out_level >= 0 ? outs[op.out_level] : nullptr, want_stats ? partial() : nullptr,
+                                              fuse ? &nf : nullptr, deep(), s);
+                    if (copies && c.param_fwd()) pack_copies();
+                    if (r.norm_done) fused_done[T.norm] = 1;
+                    else if (want_stats) { fused_blocks[T.norm] = r.rows; fused_dbl[T.norm] = r.dbl; }
                     break;
                 }
                 case OP_NORM: {
@@ -834,36 +894,13 @@ struct Exec {
             // the op's own region (the shared scratch is the side stream's)
             const bool on_main = op.kind == OP_CONV && p.wgrad_on_main[i] && p.wz_off[i] != SIZE_MAX;
             const bool defer = gflat && p.wz_job_of_op[i] >= 0 && !on_main;   // slab only: summed by the batched reduce below
+            // the slab in the op's own region where the batched reduce sums it later, and for a conv's bf16 slab kernels whenever the plan
+            // laid one out; else in the shared scratch
+            const bool own = p.wz_off[i] != SIZE_MAX && (defer || (op.kind == OP_CONV && p.conv[i].wgrad == Wgrad::mfma));
             {   // the op's own bracket closes before flush_wz opens the batched reduce's (they would nest and count the reduce twice)
             ProfScope pw(i, UNET_PROF_WGRAD, sb);
-            switch (p.conv[i].wgrad) {
-                case Wgrad::first_mfma:
-                    launch_conv_first_wgrad_mfma(cg, sd, gptr(t), gparams[op.weight], gparams[op.bias],
-                                                 ws + (defer ? p.wz_off[i] : p.wgrad_off), sb, defer);
-                    break;
-                case Wgrad::mfma:
-                    if (op.kind == OP_CONVT)
-                        launch_mfma_convt_wgrad(cg, sd, gptr(t), gparams[op.weight], ws + (defer ? p.wz_off[i] : p.wgrad_off), sb, defer, gparams[op.bias],
-                                                p.side_polite[i]);
-                    else if (on_main)
-                        launch_mfma_conv_wgrad(cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wz_off[i], s, false, 0);
-                    else
-                        launch_mfma_conv_wgrad(cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias],
-                                               ws + (p.wz_off[i] != SIZE_MAX ? p.wz_off[i] : p.wgrad_off), sb, defer, p.side_polite[i]);
-                    break;
-                case Wgrad::f32_mfma:
-                    launch_wgrad_f32_mfma(cg, sd, op.nsrc, (const float*)gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-                    break;
-                case Wgrad::small:
-                    launch_conv_wgrad_small(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-                    break;
-                case Wgrad::direct:
-                    if (op.kind == OP_CONVT)
-                        launch_convt_wgrad_direct(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-                    else
-                        launch_conv_wgrad_direct(p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wgrad_off, sb);
-                    break;
-            }
+            conv_wgrad(p.conv[i].wgrad, op.kind == OP_CONVT, p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias],
+                       ws + (own ? p.wz_off[i] : p.wgrad_off), on_main ? s : sb, defer, on_main ? 0 : p.side_polite[i], nullptr);
             }
             if (defer) { wz_ran[p.wz_job_of_op[i]] = 1; ++wz_pending; }
             if (wz_pending >= 3) flush_wz(sb);      // (every layer and one flush at the end both measured slower: profiles/r06 A/Bs)
@@ -951,8 +988,8 @@ struct Exec {
                         ProfScope pw(i, UNET_PROF_WGRAD, s);
                         const Tensor& To = g.tensors[t];
                         NormBwdFuse nf = {tptr(t), first_fused ? stat(To.norm) : nullptr, first_fused ? coef(To.norm) : nullptr, To.act};
-                        launch_conv_first_wgrad_mfma(cg, sd, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wz_off[i], s, false,
-                                                     first_fused ? &nf : nullptr);
+                        conv_wgrad(p.conv[i].wgrad, false, p.dtype, cg, sd, op.nsrc, gptr(t), gparams[op.weight], gparams[op.bias], ws + p.wz_off[i],
+                                   s, false, 0, first_fused ? &nf : nullptr);
                     } else
                     if (!dry) {
                         const int64_t vox = (int64_t)cg.Do * cg.Ho * cg.Wo;
@@ -972,41 +1009,31 @@ struct Exec {
                         }
                     }
                     ProfScope pd(i, UNET_PROF_DGRAD, s);
-                    if (any) switch (p.conv[i].dgrad) {
-                        case Dgrad::mfma: {
-                            // The source is a norm layer's view read by this conv alone: its gradient is complete when this dgrad
-                            // has written it, so the statistics pass of that norm's backward (a second read of the gradient and of the
-                            // raw tensor) moves into the dgrad's epilogue where the kernel has one (k_mfma_conv_z16).  The rows wait in
-                            // partial(): the next thing the caller's stream runs is that tensor's view_backward.
-                            // With several consumers the one with the lowest op index writes last -- accumulating -- and sees the complete
-                            // gradient: for the skip tensors that is the stride-2 conv, whose dgrad (k_s2_scatter) fetches the old gradient
-                            // and the raw tensor by LDS-DMA and has the epilogue too.  (Stride-1 kernels only take it when they WRITE.)
-                            // The deep levels' split-K kernels, as the last writer of a norm layer's view, run that norm's whole backward.
-                            const int ts = op.src[0];
-                            const Tensor& Ts = g.tensors[ts];
-                            const bool can = op.nsrc == 1 && Ts.norm >= 0 && p.first_consumer[ts] == i && p.dtype == UNET_DTYPE_BF16;
-                            DeepNormBwd nb;
-                            if (can) {
-                                const Norm& n = g.norms[Ts.norm];
-                                nb = {tptr(ts), stat(Ts.norm), params[n.gamma], coef(Ts.norm), gparams[n.gamma], gparams[n.beta], Ts.act};
-                            }
-                            // (dry: the outcome alone, which the launch of an earlier part reported then)
-                            const DgradOutcome o = mfma_dgrad(cg, op.kind == OP_CONVT, gptr(t), ws + p.wm_dgrad[i], dg, op.nsrc, can ? &nb : nullptr,
-                                                              partial(), deep(), s, !dry);
-                            if (o.norm_done) norm_done[ts] = 1;
-                            if (o.rows > 0) { bn_tensor = ts; bn_rows = o.rows; }
-                            break;
+                    if (any) {
+                        // The source is a norm layer's view read by this conv alone: its gradient is complete when this dgrad
+                        // has written it, so the statistics pass of that norm's backward (a second read of the gradient and of the
+                        // raw tensor) moves into the dgrad's epilogue where the kernel has one (k_mfma_conv_z16).  The rows wait in
+                        // partial(): the next thing the caller's stream runs is that tensor's view_backward.
+                        // With several consumers the one with the lowest op index writes last -- accumulating -- and sees the complete
+                        // gradient: for the skip tensors that is the stride-2 conv, whose dgrad (k_s2_scatter) fetches the old gradient
+                        // and the raw tensor by LDS-DMA and has the epilogue too.  (Stride-1 kernels only take it when they WRITE.)
+                        // The deep levels' split-K kernels, as the last writer of a norm layer's view, run that norm's whole backward.
+                        // (Only the bf16 matrix-core family has such epilogues: conv_dgrad.)
+                        const int ts = op.src[0];
+                        const Tensor& Ts = g.tensors[ts];
+                        const bool can = op.nsrc == 1 && Ts.norm >= 0 && p.first_consumer[ts] == i && p.dtype == UNET_DTYPE_BF16;
+                        DeepNormBwd nb;
+                        if (can) {
+                            const Norm& n = g.norms[Ts.norm];
+                            nb = {tptr(ts), stat(Ts.norm), params[n.gamma], coef(Ts.norm), gparams[n.gamma], gparams[n.beta], Ts.act};
                         }
-                        case Dgrad::f32_mfma:
-                            if (!dry) launch_conv_f32_mfma_dgrad(cg, (const float*)gptr(t), wd, dg, op.nsrc, s);
-                            break;
-                        case Dgrad::direct:
-                            if (dry) break;
-                            if (op.kind == OP_CONVT) launch_convt_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
-                            else launch_conv_dgrad_direct(p.dtype, cg, gptr(t), wd, dg, op.nsrc, s);
-                            break;
+                        // (dry: the outcome alone, which the launch of an earlier part reported then)
+                        const DgradOutcome o = conv_dgrad(p.conv[i].dgrad, op.kind == OP_CONVT, p.dtype, cg, gptr(t), at(p.wm_dgrad[i]), wd, dg, op.nsrc,
+                                                          can ? &nb : nullptr, partial(), deep(), s, !dry);
+                        if (o.norm_done) norm_done[ts] = 1;
+                        if (o.rows > 0) { bn_tensor = ts; bn_rows = o.rows; }
+                        mark(op);
                     }
-                    if (any) mark(op);
                     break;
                 }
                 case OP_MATERIALIZE: {
@@ -1662,6 +1689,34 @@ static DeepScratch op_deep() {
     per_dev[dev] = d;
     return d;
 }
+// The conv / conv_trans entries below: geometry, sources and destinations, choose_conv, the filter form the choice reads packed into
+// the scratch, then the executor's own launch of that direction (conv_fwd, conv_dgrad, conv_wgrad above).
+// one bf16 MFMA filter pack of a call, forward or dgrad
+static void* op_pack_mfma(const float* w, const ConvGeom& g, bool transposed, bool dgrad, void* scratch, hipStream_t s) {
+    void* wm = (char*)scratch + OpScratch(g.Cin, g.Cout).pack;
+    if (transposed) launch_mfma_pack_convt_w(w, dgrad ? nullptr : wm, dgrad ? wm : nullptr, g, s);
+    else launch_mfma_pack_conv_w(w, dgrad ? nullptr : wm, dgrad ? wm : nullptr, g, s);
+    return wm;
+}
+// the forward of an entry; use_deep == false: no deep scratch is passed, the split-K kernels stay out
+static FwdRan op_conv_fwd(const ConvChoice& c, bool transposed, int dtype, const ConvGeom& g, const SrcDesc* sd, int nsrc, const float* w,
+                          const float* b, void* y, float* part, const DeepNormFwd* nf, bool use_deep, void* scratch, hipStream_t s) {
+    float *wf = nullptr, *wd;
+    const void* wm = nullptr;
+    if (c.mfma_fwd()) wm = op_pack_mfma(w, g, transposed, false, scratch, s);
+    else if (!c.param_fwd()) op_pack(w, g.Cin, g.Cout, g.ks * g.ks * g.ks, transposed, scratch, &wf, &wd, s);
+    return conv_fwd(c.fwd, transposed, dtype, g, sd, nsrc, w, wf, wm, b, y, nullptr, part, nf,
+                    use_deep && c.mfma_fwd() ? op_deep() : DeepScratch(), s);
+}
+// the input gradient of an entry, into one destination
+static DgradOutcome op_conv_dgrad(Dgrad c, bool transposed, int dtype, const ConvGeom& g, const void* dy, const float* w, const DstGrad& d,
+                                  const DeepNormBwd* nb, float* part, void* scratch, hipStream_t s) {
+    float *wf, *wd = nullptr;
+    const void* wm = nullptr;
+    if (c == Dgrad::mfma) wm = op_pack_mfma(w, g, transposed, true, scratch, s);
+    else op_pack(w, g.Cin, g.Cout, g.ks * g.ks * g.ks, transposed, scratch, &wf, &wd, s);
+    return conv_dgrad(c, transposed, dtype, g, dy, wm, wd, &d, 1, nb, part, c == Dgrad::mfma ? op_deep() : DeepScratch(), s);
+}
 
 // what the entry points below ask choose_conv for one plain source of cin channels, as integers; launches nothing
 int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]) {
@@ -1679,24 +1734,10 @@ int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, in
 int unet_op_conv3d_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D, int H,
                        int W, int ks, int stride, void* scratch, void* stream) {
     OP_TRY({
-        hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
-        float *wf, *wd;
         SrcDesc sd; sd.ptr = x; sd.C = cin;
         const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
-        if (c.mfma_fwd()) {
-            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
-            launch_mfma_pack_conv_w(w, wm, nullptr, g, s);
-            if (!launch_deep_conv_fwd(g, &sd, 1, wm, b, y, nullptr, op_deep(), s)) launch_mfma_conv_fwd(g, &sd, 1, wm, b, y, nullptr, s);
-        } else if (c.fwd == Fwd::first_mfma) {
-            launch_conv_first_mfma(g, &sd, w, b, y, nullptr, s);
-        } else if (c.fwd == Fwd::first_f32_mfma) {
-            (void)launch_conv_first_f32_mfma(g, &sd, w, b, (float*)y, nullptr, s);
-        } else {
-            op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
-            if (c.fwd == Fwd::f32_mfma) (void)launch_conv_f32_mfma(g, &sd, 1, wf, b, (float*)y, s);
-            else launch_conv_fwd_direct(dtype, g, &sd, 1, wf, b, y, nullptr, s);
-        }
+        op_conv_fwd(c, false, dtype, g, &sd, 1, w, b, y, nullptr, nullptr, true, scratch, (hipStream_t)stream);
     })
 }
 int unet_op_conv3d_fwd_fused(int dtype, int impl, const void* x, const float* scale, const float* shift, int act, const float* w,
@@ -1705,33 +1746,17 @@ int unet_op_conv3d_fwd_fused(int dtype, int impl, const void* x, const float* sc
     OP_TRY({
         hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
-        float *wf, *wd;
         SrcDesc sd; sd.ptr = x; sd.C = cin; sd.scale = scale; sd.shift = shift; sd.act = act;
         int64_t So = (int64_t)g.Do * g.Ho * g.Wo;
-        const OpScratch L(cin, cout);
-        float* part = (float*)((char*)scratch + L.partials);
-        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
-        if (c.mfma_fwd()) {
-            void* wm = (char*)scratch + L.pack;
-            launch_mfma_pack_conv_w(w, wm, nullptr, g, s);
-            int rows = launch_mfma_conv_fwd(g, &sd, 1, wm, b, y, stats ? part : nullptr, s);
-            if (stats) launch_stats_sum(part, rows, cout, stats, s);
-        } else if (c.fwd == Fwd::first_mfma) {
-            int rows = launch_conv_first_mfma(g, &sd, w, b, y, stats ? part : nullptr, s);
-            if (stats) launch_stats_sum(part, rows, cout, stats, s);
-        } else {   // (the fp32 first conv too: this entry runs it on the direct kernel + a statistics pass)
-            op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
-            if (c.fwd == Fwd::f32_mfma) {
-                // the fp32 matrix-core conv leaves its own fp64 statistics rows (one per tile)
-                const int rows = launch_conv_f32_mfma(g, &sd, 1, wf, b, (float*)y, s, stats ? (double*)part : nullptr);
-                if (stats) launch_stats_sum(part, rows, cout, stats, s, true);
-            } else {
-                launch_conv_fwd_direct(dtype, g, &sd, 1, wf, b, y, nullptr, s);
-                if (stats) {
-                    launch_stats_partial(dtype, y, cout, So, part, s);
-                    launch_stats_sum(part, stats_blocks(So), cout, stats, s, dtype == UNET_DTYPE_F32);
-                }
-            }
+        float* part = (float*)((char*)scratch + OpScratch(cin, cout).partials);
+        ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
+        if (c.fwd == Fwd::first_f32_mfma) c.fwd = Fwd::direct;   // (the fp32 first conv too: this entry runs it on the direct kernel + a statistics pass)
+        // (this entry passes no deep scratch: it keeps to the kernels that leave statistics rows)
+        const FwdRan r = op_conv_fwd(c, false, dtype, g, &sd, 1, w, b, y, stats ? part : nullptr, nullptr, false, scratch, s);
+        if (stats && r.rows) launch_stats_sum(part, r.rows, cout, stats, s, r.dbl);
+        else if (stats) {
+            launch_stats_partial(dtype, y, cout, So, part, s);
+            launch_stats_sum(part, stats_blocks(So), cout, stats, s, dtype == UNET_DTYPE_F32);
         }
     })
 }
@@ -1758,25 +1783,15 @@ int unet_op_conv3d_fwd_packed(int dtype, const void* x, const void* wpacked, con
 int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w, void* dx, int cin, int cout, int D, int H, int W,
                             int ks, int stride, void* scratch, void* stream) {
     OP_TRY({
-        hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
-        float *wf, *wd;
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = 0;
         SrcDesc sd; sd.C = cin;
-        const Dgrad c = choose_conv(dtype, impl, g, &sd, 1, false, false).dgrad;
-        if (c == Dgrad::mfma) {
-            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
-            launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
-            mfma_dgrad(g, false, dy, wm, &d, 1, nullptr, nullptr, op_deep(), s);
-        } else {
-            op_pack(w, cin, cout, ks * ks * ks, false, scratch, &wf, &wd, s);
-            if (c == Dgrad::f32_mfma) launch_conv_f32_mfma_dgrad(g, (const float*)dy, wd, &d, 1, s);
-            else launch_conv_dgrad_direct(dtype, g, dy, wd, &d, 1, s);
-        }
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
+        op_conv_dgrad(c.dgrad, false, dtype, g, dy, w, d, nullptr, nullptr, scratch, (hipStream_t)stream);
     })
 }
-// A conv k3 and the norm + activation behind it, bf16, as the executor runs that layer: on the deep levels the split-K kernel with
-// the norm in its epilogue (DEEP_FWD_NORM), else the MFMA conv with its statistics rows and the norm's separate launches.
+// A conv k3 and the norm + activation behind it, bf16, as the executor runs that layer (conv_fwd): on the deep levels the split-K kernel
+// with the norm in its epilogue (DEEP_FWD_NORM), else the MFMA conv with its statistics rows and the norm's separate launches.
 int unet_op_conv3d_fwd_norm(const void* x0, const void* x1, int cin0, int cin1, const float* w, const float* b, const float* gamma,
                             const float* beta, double eps, float* rm, float* rv, double momentum, int use_running, int act, void* y,
                             void* y_act, float* stat, int cout, int D, int H, int W, int stride, void* scratch, void* stream) {
@@ -1790,21 +1805,17 @@ int unet_op_conv3d_fwd_norm(const void* x0, const void* x1, int cin0, int cin1, 
         const ConvChoice c = choose_conv(UNET_DTYPE_BF16, UNET_IMPL_AUTO, g, sd, nsrc, false, false);
         if (!c.mfma_fwd() || (use_running && (!rm || !rv)))
             throw std::runtime_error("unet_op_conv3d_fwd_norm: shape not covered by the MFMA kernels, or eval mode without running statistics");
-        const OpScratch L(cin, cout);
-        void* wm = (char*)scratch + L.pack;
-        float* part = (float*)((char*)scratch + L.partials);
-        launch_mfma_pack_conv_w(w, wm, nullptr, g, s);
+        float* part = (float*)((char*)scratch + OpScratch(cin, cout).partials);
         const DeepNormFwd nf = {gamma, beta, eps, stat, rm, rv, momentum, use_running ? 1 : 0, act, y_act};
-        if (!(c.fwd == Fwd::deep && launch_deep_conv_fwd(g, sd, nsrc, wm, b, y, &nf, op_deep(), s))) {
-            const int rows = launch_mfma_conv_fwd(g, sd, nsrc, wm, b, y, use_running ? nullptr : part, s);
-            norm_fwd_passes(UNET_DTYPE_BF16, y, cout, (int64_t)g.Do * g.Ho * g.Wo, part, rows, false, use_running != 0, gamma, beta, eps,
+        const FwdRan r = op_conv_fwd(c, false, UNET_DTYPE_BF16, g, sd, nsrc, w, b, y, use_running ? nullptr : part, &nf, true, scratch, s);
+        if (!r.norm_done)
+            norm_fwd_passes(UNET_DTYPE_BF16, y, cout, (int64_t)g.Do * g.Ho * g.Wo, part, r.rows, r.dbl, use_running != 0, gamma, beta, eps,
                             stat, rm, rv, act, y_act, s);
-        }
     })
 }
 // The dgrad of a conv k3 s1 (or of a conv_trans k2 s2: transposed) into the view of a norm layer's tensor u, then that norm's backward
-// as the executor runs it: on the deep levels in the split-K kernel's epilogue (DEEP_BWD_NORM), else the dgrad (with the statistics
-// epilogue where the kernel has one) and the norm's separate backward launches.
+// as the executor runs it (conv_dgrad): on the deep levels in the split-K kernel's epilogue (DEEP_BWD_NORM), else the dgrad (with the
+// statistics epilogue where the kernel has one) and the norm's separate backward launches.
 int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w, void* dx, int accumulate, const void* u, const float* stat,
                                  const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin, int cout, int D, int H,
                                  int W, void* scratch, void* stream) {
@@ -1812,69 +1823,43 @@ int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w,
         hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, transposed ? 2 : 3, transposed ? 2 : 1, transposed != 0);
         SrcDesc sd; sd.C = cin;
-        if (choose_conv(UNET_DTYPE_BF16, UNET_IMPL_AUTO, g, &sd, 1, false, transposed != 0).dgrad != Dgrad::mfma)
-            throw std::runtime_error("unet_op_conv3d_bwd_data_norm: shape not covered by the MFMA kernels");
-        const OpScratch L(cin, cout);
-        void* wm = (char*)scratch + L.pack;
-        float* part = (float*)((char*)scratch + L.partials);
+        const ConvChoice c = choose_conv(UNET_DTYPE_BF16, UNET_IMPL_AUTO, g, &sd, 1, false, transposed != 0);
+        if (c.dgrad != Dgrad::mfma) throw std::runtime_error("unet_op_conv3d_bwd_data_norm: shape not covered by the MFMA kernels");
+        float* part = (float*)((char*)scratch + OpScratch(cin, cout).partials);
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = accumulate ? 1 : 0;
         const DeepNormBwd nb = {u, stat, gamma, coef, dgamma, dbeta, act};
-        if (transposed) launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
-        else launch_mfma_pack_conv_w(w, nullptr, wm, g, s);
-        const DgradOutcome o = mfma_dgrad(g, transposed != 0, dy, wm, &d, 1, &nb, part, op_deep(), s);
+        const DgradOutcome o = op_conv_dgrad(c.dgrad, transposed != 0, UNET_DTYPE_BF16, g, dy, w, d, &nb, part, scratch, s);
         if (!o.norm_done) norm_bwd_passes(UNET_DTYPE_BF16, dx, u, cin, (int64_t)D * H * W, stat, act, gamma, coef, dgamma, dbeta, part, o.rows, false, s);
     })
 }
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D,
                               int H, int W, int ks, int stride, void* scratch, void* stream) {
     OP_TRY({
-        hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        switch (choose_conv(dtype, impl, g, &sd, 1, false, false).wgrad) {
-            case Wgrad::first_mfma: launch_conv_first_wgrad_mfma(g, &sd, dy, dw, db, scratch, s); break;
-            case Wgrad::mfma: launch_mfma_conv_wgrad(g, &sd, 1, dy, dw, db, scratch, s, false, env().op_polite ? 1 : 0); break;
-            case Wgrad::f32_mfma: launch_wgrad_f32_mfma(g, &sd, 1, (const float*)dy, dw, db, scratch, s); break;
-            case Wgrad::small: launch_conv_wgrad_small(dtype, g, &sd, 1, dy, dw, db, scratch, s); break;
-            case Wgrad::direct: launch_conv_wgrad_direct(dtype, g, &sd, 1, dy, dw, db, nullptr, s);
-        }
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
+        // (the direct kernel gets no scratch from this surface: one block range, no slab; polite: UNET_OP_POLITE)
+        conv_wgrad(c.wgrad, false, dtype, g, &sd, 1, dy, dw, db, c.wgrad == Wgrad::direct ? nullptr : scratch, (hipStream_t)stream, false,
+                   env().op_polite ? 1 : 0, nullptr);
     })
 }
 int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D, int H,
                       int W, void* scratch, void* stream) {
     OP_TRY({
-        hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, 2, 2, true);
-        float *wf, *wd;
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        const Fwd f = choose_conv(dtype, impl, g, &sd, 1, false, true).fwd;
-        if (f == Fwd::mfma) {
-            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
-            launch_mfma_pack_convt_w(w, wm, nullptr, g, s);
-            if (!launch_deep_convt_fwd(g, &sd, 1, wm, b, y, op_deep(), s)) launch_mfma_convt_fwd(g, &sd, 1, wm, b, y, s);
-        } else {
-            op_pack(w, cin, cout, 8, true, scratch, &wf, &wd, s);
-            if (f == Fwd::f32_mfma) launch_convt_f32_mfma(g, &sd, wf, b, (float*)y, s);
-            else launch_convt_fwd_direct(dtype, g, &sd, 1, wf, b, y, s);
-        }
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, true);
+        op_conv_fwd(c, true, dtype, g, &sd, 1, w, b, y, nullptr, nullptr, true, scratch, (hipStream_t)stream);
     })
 }
 int unet_op_convt_bwd_data(int dtype, int impl, const void* dy, const float* w, void* dx, int cin, int cout, int D, int H, int W,
                            void* scratch, void* stream) {
     OP_TRY({
-        hipStream_t s = (hipStream_t)stream;
         ConvGeom g = op_geom(cin, cout, D, H, W, 2, 2, true);
-        float *wf, *wd;
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = 0;
         SrcDesc sd; sd.C = cin;
-        if (choose_conv(dtype, impl, g, &sd, 1, false, true).dgrad == Dgrad::mfma) {
-            void* wm = (char*)scratch + OpScratch(cin, cout).pack;
-            launch_mfma_pack_convt_w(w, nullptr, wm, g, s);
-            mfma_dgrad(g, true, dy, wm, &d, 1, nullptr, nullptr, op_deep(), s);
-        } else {
-            op_pack(w, cin, cout, 8, true, scratch, &wf, &wd, s);
-            launch_convt_dgrad_direct(dtype, g, dy, wd, &d, 1, s);
-        }
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, true);
+        op_conv_dgrad(c.dgrad, true, dtype, g, dy, w, d, nullptr, nullptr, scratch, (hipStream_t)stream);
     })
 }
 int unet_op_convt_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D, int H,
@@ -1882,10 +1867,8 @@ int unet_op_convt_bwd_weight(int dtype, int impl, const void* x, const void* dy,
     OP_TRY({
         ConvGeom g = op_geom(cin, cout, D, H, W, 2, 2, true);
         SrcDesc sd; sd.ptr = x; sd.C = cin;
-        if (choose_conv(dtype, impl, g, &sd, 1, false, true).wgrad == Wgrad::mfma)
-            launch_mfma_convt_wgrad(g, &sd, dy, dw, scratch, (hipStream_t)stream, false, db);
-        else
-            launch_convt_wgrad_direct(dtype, g, &sd, 1, dy, dw, db, nullptr, (hipStream_t)stream);
+        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, true);
+        conv_wgrad(c.wgrad, true, dtype, g, &sd, 1, dy, dw, db, c.wgrad == Wgrad::direct ? nullptr : scratch, (hipStream_t)stream, false, 0, nullptr);
     })
 }
 int unet_op_pack_ndhwc(int dtype, const float* x, void* y, int C, int64_t S, void* stream) {
