@@ -35,6 +35,7 @@ from . import instances  # noqa: F401  (the module: instances.EXPORTS the symbol
 from . import morph  # noqa: F401  (the module: morph.EXPORTS the symbols of include/unet_morph.h)
 from . import connectivity  # noqa: F401  (the module: connectivity.EXPORTS the symbols of include/unet_connectivity.h)
 from . import stats  # noqa: F401  (the module: stats.EXPORTS the symbols of include/unet_stats.h)
+from . import calib  # noqa: F401  (the module: calib.EXPORTS the symbols of include/unet_calib.h)
 
 
 def save_to_file(model, file_name):

@@ -2659,6 +2659,44 @@ int unet_stats_quantiles(const void* labels, int label_bytes, const float* image
     });
 }
 
+// ---- the calibration tables (include/unet_calib.h) ----
+static std::string calib_size_error(const std::string& w, int out_c, int64_t voxels) {
+    if (out_c < 2 || out_c > UNET_CALIB_MAX_CLASSES)
+        return w + "out_c must be in [2, " + std::to_string(UNET_CALIB_MAX_CLASSES) + "], got " + std::to_string(out_c);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
+    return std::string();
+}
+int unet_calib_table_len(int out_c, size_t* count) {
+    const std::string who = "unet_calib_table_len: ";
+    if (std::string e = calib_size_error(who, out_c, 1); !e.empty()) return fail(e);
+    if (!count) return fail(who + "null count");
+    *count = calib_table_len(out_c);
+    return 0;
+}
+int unet_calib_scratch_bytes(int out_c, int64_t voxels, size_t* bytes) {
+    const std::string who = "unet_calib_scratch_bytes: ";
+    if (std::string e = calib_size_error(who, out_c, voxels); !e.empty()) return fail(e);
+    if (!bytes) return fail(who + "null bytes");
+    *bytes = calib_scratch_bytes(out_c);   // the running table: nothing per voxel
+    return 0;
+}
+int unet_calib_tables(const float* src, int src_kind, int out_c, int64_t voxels, const float* label, const uint8_t* mask, int accumulate,
+                      int64_t* tables, uint8_t* wrong, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_calib_tables: ";
+    std::string e = ptr_error(who, src, "src", 4);
+    if (e.empty() && src_kind != UNET_CALIB_SRC_LOGITS && src_kind != UNET_CALIB_SRC_PROBS) e = who + "unknown src_kind " + std::to_string(src_kind);
+    if (e.empty()) e = calib_size_error(who, out_c, voxels);
+    if (e.empty()) e = ptr_error(who, label, "label", 4);
+    if (e.empty()) e = ptr_error(who, tables, "tables", 8);
+    if (e.empty() && (impl < UNET_CALIB_IMPL_DEFAULT || impl > UNET_CALIB_IMPL_GLOBAL)) e = who + "unknown impl " + std::to_string(impl);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < calib_scratch_bytes(out_c)) e = who + "scratch too small (see unet_calib_scratch_bytes)";
+    if (!e.empty()) return fail(e);
+    return run_on_device_of(src, stream, [&](hipStream_t s) {
+        launch_calib_tables(src, src_kind, out_c, voxels, label, mask, accumulate, tables, wrong, impl, scratch, s);
+    });
+}
+
 // ---- the boundary distances of label maps (include/unet_distance.h) ----
 static std::string dist_grid_error(const std::string& w_, const void* map, const char* name, int bytes, int w, int h, int d) {
     if (!map) return w_ + "null " + name;

@@ -7,6 +7,7 @@
 
 #include "../../include/unet_atlas.h"
 #include "../../include/unet_augment.h"
+#include "../../include/unet_calib.h"
 #include "../../include/unet_components.h"
 #include "../../include/unet_connectivity.h"
 #include "../../include/unet_distance.h"
@@ -498,6 +499,12 @@ void launch_stats_hist(const void* labels, int label_bytes, const float* image, 
                        int64_t* rows, int impl, void* scratch, hipStream_t s);
 void launch_stats_quantiles(const void* labels, int label_bytes, const float* image, int64_t voxels, int n_labels, float lo, float hi,
                             float scale, const int* permille, int n_quantiles, int32_t* out, int impl, void* scratch, hipStream_t s);
+
+// kernels_calib.hip: the calibration tables (include/unet_calib.h); mask and wrong may be null; the running table lives in the scratch
+size_t calib_table_len(int C);
+size_t calib_scratch_bytes(int C);
+void launch_calib_tables(const float* src, int src_kind, int C, int64_t S, const float* label, const uint8_t* mask, int accumulate,
+                         int64_t* tables, uint8_t* wrong, int impl, void* scratch, hipStream_t s);
 
 // kernels_distance.hip: the exact squared distance transform and the surface lists (include/unet_distance.h); the volume between
 // the passes lives in the scratch

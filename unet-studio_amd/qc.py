@@ -404,6 +404,150 @@ def lesion_qc(model, model_path, cases, labels=None, rule="any", threshold=0.0, 
     return 0, report
 
 
+# ---- calibration of the probabilities (this project's: the only family that judges the probabilities, not the label map) --------------
+CALIBRATION_COLUMNS = ("voxels", "accuracy", "ece", "mce", "brier", "nll")
+CALIBRATION_MASKS = ("all", "foreground")
+
+
+def calibration_report_path(model_path):
+    d, f = os.path.split(model_path)
+    return os.path.join(d, os.path.splitext(f)[0] + ".calibration_report.tsv")
+
+
+def calibration_scores(table, out_count, bins=10, hists=None):
+    """The scores of one calibration table (calib.py) as a dict: voxels (the valid ones), accuracy, ece, mce, brier (summed over the
+    classes), nll (the estimate of calib.nll_bounds), cw_ece and brier_c (arrays of out_count entries), and with hists = (h_correct,
+    h_wrong) of calib.uncertainty_hists also auroc_entropy and aurc_entropy."""
+    from . import calib as CB
+    head, top, cls, logh = CB.split(table, out_count)
+    per, total = CB.brier(cls)
+    s = {"voxels": int(head[CB.VALID]), "accuracy": CB.accuracy(top), "ece": CB.ece(top, bins), "mce": CB.mce(top, bins), "brier": total,
+         "nll": CB.nll_bounds(logh)[1], "cw_ece": CB.classwise_ece(cls, bins), "brier_c": per}
+    if hists is not None:
+        s["auroc_entropy"] = CB.auroc(*hists)
+        s["aurc_entropy"] = CB.risk_coverage(*hists)[2]
+    return s
+
+
+def format_calibration_report(out_count, rows, with_entropy=False):
+    """the report text; rows: (image, label, scores) with scores the dict of calibration_scores, or None for a case whose classes are
+    not the model's (a shifted label): N/A in every column.  The last row, named total, has an empty ground_truth."""
+    extra = ("auroc_entropy", "aurc_entropy") if with_entropy else ()
+    lines = ["image\tground_truth\t" + "\t".join(CALIBRATION_COLUMNS) + "".join("\tcw_ece%d" % c for c in range(out_count))
+             + "".join("\tbrier%d" % c for c in range(out_count)) + "".join("\t" + k for k in extra)]
+    width = len(CALIBRATION_COLUMNS) + 2 * out_count + len(extra)
+    for image, label, s in rows:
+        cols = [os.path.basename(image), os.path.basename(label)]
+        if s is None:
+            cols += ["N/A"] * width
+        else:
+            cols += ["%d" % s["voxels"]] + ["%.9g" % s[k] for k in CALIBRATION_COLUMNS[1:]]
+            cols += ["%.9g" % v for v in s["cw_ece"]] + ["%.9g" % v for v in s["brier_c"]] + ["%.9g" % s[k] for k in extra]
+        lines.append("\t".join(cols))
+    return "\n".join(lines) + "\n"
+
+
+def calibration_qc(model, model_path, cases, bins=10, ensemble=None, ensemble_weights=None, mask="all"):
+    """Per case, whether the model's probabilities mean anything (calib.py, include/unet_calib.h): the valid voxels, the accuracy, the
+    expected and the maximum calibration error over `bins` confidence bins (a divisor of 20), the Brier score, the negative
+    log-likelihood, and per class the class-wise ECE and the Brier score, written to `<model stem>.calibration_report.tsv` beside
+    the model with a last row `total` over all cases -> (0, report path) or (1, message).  ensemble: a list of further models
+    (`model` is member 0; ensemble_weights as in ensemble.normalize_weights): the mean probabilities are judged, and
+    auroc_entropy / aurc_entropy say whether the wrong voxels are the high-entropy ones.  mask: "all", or "foreground" for the
+    voxels whose truth or whose prediction is not the background.  A case that label_plan marks as shifted gets N/A in every column."""
+    from . import calib as CB
+    from . import ensemble as EN
+    cases = list(cases)
+    if not cases:
+        return 1, "no image/label pairs found"
+    if model.out_count < 2:
+        return 1, "QC requires a categorical model"
+    if mask not in CALIBRATION_MASKS:
+        return 1, "calibration_qc: mask must be one of %s, got %r" % (", ".join(CALIBRATION_MASKS), mask)
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 1 or CB.BINS % bins:
+        return 1, "calibration_qc: bins must divide %d, got %r" % (CB.BINS, bins)
+    if ensemble is None and ensemble_weights is not None:
+        return 1, "ensemble_weights needs ensemble"
+    if ensemble is not None and not isinstance(ensemble, (list, tuple)):
+        return 1, "ensemble must be a list of further models, got %r" % (ensemble,)
+    members = [model] + list(ensemble or [])
+    out_c = model.out_count
+    for k, other in enumerate(members[1:], 1):
+        for what in ("in_count", "out_count", "dim"):
+            if not hasattr(other, what):
+                return 1, "ensemble: member %d is not a model (it has no %s)" % (k, what)
+            a, b = getattr(other, what), getattr(model, what)
+            a, b = (tuple(a), tuple(b)) if what == "dim" else (a, b)
+            if a != b:
+                return 1, "ensemble: member %d has %s %s, member 0 has %s" % (k, what, a, b)
+    W, H, D = (int(v) for v in model.dim)
+    S = D * H * W
+    dev = model.device()
+    rows = []
+    try:
+        weights = EN.normalize_weights(ensemble_weights, len(members)) if ensemble is not None else None
+        _, shift = label_plan(cases, out_c)
+        n = CB.table_len(out_c)
+        total, table = torch.zeros(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+        scratch = torch.empty(CB.scratch_bytes(out_c, S), dtype=torch.uint8, device=dev)
+        wrong = torch.empty(S, dtype=torch.uint8, device=dev) if ensemble is not None else None
+        state = EN.new_state(out_c, S, dev) if ensemble is not None else None
+        hist_total = torch.zeros(2, 256, dtype=torch.int64, device=dev)
+        ln_c = float(np.log(out_c))
+        for case, shifted in zip(cases, shift):
+            scores = None
+            if not shifted:
+                image, label = case[2], case[3]
+                if int(np.prod(image.shape)) != S * model.in_count or int(np.prod(label.shape)) != S:
+                    raise UNetError("%s: training data dimension mismatch" % case[0])
+                x = _to_device(image, dev).view(1, model.in_count, D, H, W)
+                t = _to_device(label, dev).view(-1)
+                with torch.no_grad():
+                    for k, member in enumerate(members):
+                        logits = member._forward_level0(x)
+                        if logits is None or tuple(logits.shape) != (1, out_c, D, H, W):
+                            raise UNetError("%s: model output dimension mismatch" % case[0])
+                        if state is not None:
+                            EN.accumulate(logits, state, weights[k], k == 0)
+                planes = logits[0].view(out_c, S) if state is None else state[:out_c * S * 4].view(torch.float32).view(out_c, S)
+                region = None
+                if mask == "foreground":
+                    region = ((torch.trunc(t) != 0) | (torch.argmax(planes, dim=0) != 0)).to(torch.uint8).contiguous()
+                hists = None
+                if state is None:
+                    CB.tables(logits[0], t, mask=region, out=table, scratch=scratch)
+                else:
+                    CB.tables_from_probs(state, out_c, S, t, mask=region, out=table, wrong=wrong, scratch=scratch)
+                    entropy = EN.finalize(state, out_c, (D, H, W), outputs=("entropy",))["entropy"]
+                    hc, hw = CB.uncertainty_hists(wrong, entropy, 0.0, ln_c)
+                    hist_total[0] += hc
+                    hist_total[1] += hw
+                    hists = (hc.cpu(), hw.cpu())
+                total += table
+                scores = calibration_scores(table, out_c, bins, hists)
+            rows.append((case[0], case[1], scores))
+        if not all(shift):
+            rows.append(("total", "", calibration_scores(total, out_c, bins, tuple(hist_total.cpu()) if state is not None else None)))
+        else:
+            rows.append(("total", "", None))
+    except UNetError as e:
+        return 1, str(e)
+    report = calibration_report_path(model_path)
+    tmp = report + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(format_calibration_report(out_c, rows, ensemble is not None).encode())
+    except OSError as e:
+        return 1, "failed writing %s: %s" % (tmp, e)
+    try:
+        if os.path.lexists(report):
+            os.remove(report)
+        os.rename(tmp, report)
+    except OSError as e:
+        return 1, "cannot create %s: %s" % (report, e)
+    return 0, report
+
+
 def qc(model_path, cases, device="cuda:0", dtype="bf16", thread_count=4):
     """int qc(void) (qc.cpp:164-376) for cases already read -> (0, report path) or (1, message)"""
     from .unet3d import UNet3d
