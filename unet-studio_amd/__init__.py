@@ -36,6 +36,7 @@ from . import morph  # noqa: F401  (the module: morph.EXPORTS the symbols of inc
 from . import connectivity  # noqa: F401  (the module: connectivity.EXPORTS the symbols of include/unet_connectivity.h)
 from . import stats  # noqa: F401  (the module: stats.EXPORTS the symbols of include/unet_stats.h)
 from . import calib  # noqa: F401  (the module: calib.EXPORTS the symbols of include/unet_calib.h)
+from . import recal  # noqa: F401  (the module: recal.EXPORTS the symbols of include/unet_recal.h)
 
 
 def save_to_file(model, file_name):

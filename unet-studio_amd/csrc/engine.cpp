@@ -2697,6 +2697,41 @@ int unet_calib_tables(const float* src, int src_kind, int out_c, int64_t voxels,
     });
 }
 
+// ---- the recalibration pass (include/unet_recal.h) ----
+static std::string recal_size_error(const std::string& w, int out_c, int64_t voxels) {
+    if (out_c < 2 || out_c > UNET_RECAL_MAX_CLASSES)
+        return w + "out_c must be in [2, " + std::to_string(UNET_RECAL_MAX_CLASSES) + "], got " + std::to_string(out_c);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return w + "voxels must be in [1, 2^31), got " + std::to_string(voxels);
+    return std::string();
+}
+int unet_recal_scratch_bytes(int out_c, int64_t voxels, size_t* bytes) {
+    const std::string who = "unet_recal_scratch_bytes: ";
+    if (std::string e = recal_size_error(who, out_c, voxels); !e.empty()) return fail(e);
+    if (!bytes) return fail(who + "null bytes");
+    *bytes = recal_scratch_bytes();   // the running table: nothing per voxel or class
+    return 0;
+}
+int unet_recal_eval(const float* logits, int out_c, int64_t voxels, const float* label, const uint8_t* mask, const float* betas, int n_betas,
+                    int accumulate, int64_t* tables, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string who = "unet_recal_eval: ";
+    std::string e = ptr_error(who, logits, "logits", 4);
+    if (e.empty()) e = recal_size_error(who, out_c, voxels);
+    if (e.empty()) e = ptr_error(who, label, "label", 4);
+    if (e.empty() && !betas) e = who + "null betas";
+    if (e.empty() && (n_betas < 1 || n_betas > UNET_RECAL_MAX_BETAS))
+        e = who + "n_betas must be in [1, " + std::to_string(UNET_RECAL_MAX_BETAS) + "], got " + std::to_string(n_betas);
+    for (int k = 0; e.empty() && k < n_betas; ++k)
+        if (!std::isfinite(betas[k]) || !(betas[k] > 0.f))
+            e = who + "betas[" + std::to_string(k) + "] must be finite and positive, got " + std::to_string(betas[k]);
+    if (e.empty()) e = ptr_error(who, tables, "tables", 8);
+    if (e.empty() && !scratch) e = who + "null scratch";
+    if (e.empty() && scratch_bytes < recal_scratch_bytes()) e = who + "scratch too small (see unet_recal_scratch_bytes)";
+    if (!e.empty()) return fail(e);
+    return run_on_device_of(logits, stream, [&](hipStream_t s) {   // betas is consumed inside the launcher
+        launch_recal_eval(logits, out_c, voxels, label, mask, betas, n_betas, accumulate, tables, scratch, s);
+    });
+}
+
 // ---- the boundary distances of label maps (include/unet_distance.h) ----
 static std::string dist_grid_error(const std::string& w_, const void* map, const char* name, int bytes, int w, int h, int d) {
     if (!map) return w_ + "null " + name;

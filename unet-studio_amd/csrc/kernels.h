@@ -8,6 +8,7 @@
 #include "../../include/unet_atlas.h"
 #include "../../include/unet_augment.h"
 #include "../../include/unet_calib.h"
+#include "../../include/unet_recal.h"
 #include "../../include/unet_components.h"
 #include "../../include/unet_connectivity.h"
 #include "../../include/unet_distance.h"
@@ -505,6 +506,12 @@ size_t calib_table_len(int C);
 size_t calib_scratch_bytes(int C);
 void launch_calib_tables(const float* src, int src_kind, int C, int64_t S, const float* label, const uint8_t* mask, int accumulate,
                          int64_t* tables, uint8_t* wrong, int impl, void* scratch, hipStream_t s);
+
+// kernels_recal.hip: the recalibration pass (include/unet_recal.h); mask may be null; betas: n_betas host floats, read before the
+// return; the running table lives in the scratch
+size_t recal_scratch_bytes();
+void launch_recal_eval(const float* logits, int C, int64_t S, const float* label, const uint8_t* mask, const float* betas, int n_betas,
+                       int accumulate, int64_t* tables, void* scratch, hipStream_t s);
 
 // kernels_distance.hip: the exact squared distance transform and the surface lists (include/unet_distance.h); the volume between
 // the passes lives in the scratch

@@ -548,6 +548,94 @@ def calibration_qc(model, model_path, cases, bins=10, ensemble=None, ensemble_we
     return 0, report
 
 
+def recalibration_qc(model, model_path, cases, mask="all", u_range=(-4.0, 4.0), rounds=3, apply=False):
+    """Fits one temperature to the model's level-0 logits over the cases (recal.py, include/unet_recal.h) and says what it buys: per
+    case the valid voxels and the mean negative log-likelihood before (beta = 1) and after (the fitted beta = 1 / T), written to
+    `<model stem>.recalibration_report.tsv` beside the model with a last row `total` that also carries beta, temperature, the
+    bracket, at_bound and the impossible and saturated voxels -> (0, report path) or (1, message).  u_range: the octaves of
+    log2 beta that are searched, rounds: of 8 candidates each (every round re-runs the forwards).  mask as in calibration_qc.  A case
+    that label_plan marks as shifted gets N/A and takes no part in the fit.  apply: fold beta into the model's level-0 head after
+    the closing pass (recal.fold: the head must be a bare conv); the caller saves the model."""
+    from . import recal as RC
+    cases = list(cases)
+    if not cases:
+        return 1, "no image/label pairs found"
+    if model.out_count < 2:
+        return 1, "QC requires a categorical model"
+    if mask not in CALIBRATION_MASKS:
+        return 1, "recalibration_qc: mask must be one of %s, got %r" % (", ".join(CALIBRATION_MASKS), mask)
+    try:
+        u_lo, u_hi = (float(v) for v in u_range)
+    except (TypeError, ValueError):
+        return 1, "recalibration_qc: u_range must be (u_lo, u_hi), got %r" % (u_range,)
+    try:
+        solver = RC.Solver(u_lo, u_hi, rounds)
+    except UNetError as e:
+        return 1, "recalibration_qc: %s" % e
+    if apply and not RC.head_is_bare_conv(model.architecture):
+        return 1, "recalibration_qc: the level-0 head %r is not a bare conv: beta cannot be folded in" % RC.head_token(model.architecture)
+    out_c = model.out_count
+    W, H, D = (int(v) for v in model.dim)
+    S = D * H * W
+    dev = model.device()
+    try:
+        _, shift = label_plan(cases, out_c)
+
+        def batches():
+            for case, shifted in zip(cases, shift):
+                if shifted:
+                    continue
+                image, label = case[2], case[3]
+                if int(np.prod(image.shape)) != S * model.in_count or int(np.prod(label.shape)) != S:
+                    raise UNetError("%s: training data dimension mismatch" % case[0])
+                x = _to_device(image, dev).view(1, model.in_count, D, H, W)
+                t = _to_device(label, dev).view(-1)
+                with torch.no_grad():
+                    logits = model._forward_level0(x)
+                if logits is None or tuple(logits.shape) != (1, out_c, D, H, W):
+                    raise UNetError("%s: model output dimension mismatch" % case[0])
+                region = None
+                if mask == "foreground":
+                    region = ((torch.trunc(t) != 0) | (torch.argmax(logits[0].view(out_c, S), dim=0) != 0)).to(torch.uint8).contiguous()
+                yield logits[0], t, region
+
+        rows, fitted, total = [], None, None
+        if not all(shift):
+            fitted = RC.fit(batches, solver=solver)
+            total = torch.zeros(RC.TABLE_LEN, dtype=torch.int64, device=dev)
+            table = torch.empty(RC.TABLE_LEN, dtype=torch.int64, device=dev)
+            closing = iter(batches())
+        for case, shifted in zip(cases, shift):
+            if shifted:
+                rows.append((case[0], case[1], None))
+                continue
+            logits, t, region = next(closing)
+            RC.eval_betas(logits, t, (1.0, fitted["beta"]), mask=region, out=table)
+            total += table
+            rows.append((case[0], case[1], table.cpu()))
+        if fitted is not None:
+            fitted["table"] = total.cpu()
+        text = RC.format_report(rows, fitted)
+        if apply and fitted is not None:
+            RC.fold(model, fitted["beta"])
+    except UNetError as e:
+        return 1, str(e)
+    report = RC.report_path(model_path)
+    tmp = report + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(text.encode())
+    except OSError as e:
+        return 1, "failed writing %s: %s" % (tmp, e)
+    try:
+        if os.path.lexists(report):
+            os.remove(report)
+        os.rename(tmp, report)
+    except OSError as e:
+        return 1, "cannot create %s: %s" % (report, e)
+    return 0, report
+
+
 def qc(model_path, cases, device="cuda:0", dtype="bf16", thread_count=4):
     """int qc(void) (qc.cpp:164-376) for cases already read -> (0, report path) or (1, message)"""
     from .unet3d import UNet3d
