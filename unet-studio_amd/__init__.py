@@ -37,6 +37,8 @@ from . import connectivity  # noqa: F401  (the module: connectivity.EXPORTS the 
 from . import stats  # noqa: F401  (the module: stats.EXPORTS the symbols of include/unet_stats.h)
 from . import calib  # noqa: F401  (the module: calib.EXPORTS the symbols of include/unet_calib.h)
 from . import recal  # noqa: F401  (the module: recal.EXPORTS the symbols of include/unet_recal.h)
+from . import patches  # noqa: F401  (the module: patches.EXPORTS the symbols of include/unet_patches.h)
+from .patches import WindowFeed, to_canvas  # noqa: F401
 
 
 def save_to_file(model, file_name):

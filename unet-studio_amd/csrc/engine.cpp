@@ -2183,6 +2183,71 @@ int unet_tiles_postproc(const float* tiles, int out_c, int tw, int th, int td, c
     });
 }
 
+// ---- the patch feed: training windows cut out of a canvas larger than the field of view (include/unet_patches.h) ----
+static std::string patches_class_error(const std::string& w, int64_t voxels, int classes) {
+    if (voxels <= 0) return w + "voxels must be positive";
+    if (voxels >= ((int64_t)1 << 31)) return w + "the canvas must stay below 2^31 voxels";
+    if (classes < 0 || classes > UNET_PATCHES_MAX_CLASSES)
+        return w + "classes must be in [0, " + std::to_string(UNET_PATCHES_MAX_CLASSES) + "], got " + std::to_string(classes);
+    return std::string();
+}
+static std::string patches_window_error(const std::string& w, int W, int H, int D, int tw, int th, int td) {
+    if (W <= 0 || H <= 0 || D <= 0) return w + "canvas dimensions must be positive";
+    if (tw <= 0 || th <= 0 || td <= 0) return w + "window dimensions must be positive";
+    if ((int64_t)W * H * D >= ((int64_t)1 << 31)) return w + "the canvas must stay below 2^31 voxels";
+    if (tw > W || th > H || td > D) return w + "the window must fit the canvas (no padding)";
+    return std::string();
+}
+int unet_patches_index_bytes(int64_t voxels, int classes, size_t* bytes) {
+    const std::string e = patches_class_error("unet_patches_index_bytes: ", voxels, classes);
+    if (!e.empty()) return fail(e);
+    if (!bytes) return fail("unet_patches_index_bytes: null output");
+    *bytes = patches_index_bytes(voxels, classes ? classes : 2);
+    return 0;
+}
+int unet_patches_index(const float* label, int64_t voxels, int classes, int32_t* index, size_t index_bytes, void* stream) {
+    const std::string e = patches_class_error("unet_patches_index: ", voxels, classes);
+    if (!e.empty()) return fail(e);
+    if (!label || !index) return fail("unet_patches_index: null device pointer");
+    if (index_bytes < patches_index_bytes(voxels, classes ? classes : 2)) return fail("unet_patches_index: index too small (see unet_patches_index_bytes)");
+    return run_on_device_of(label, stream, [&](hipStream_t s) { launch_patches_index(label, voxels, classes, index, s); });
+}
+int unet_patches_pick(const float* label, const int32_t* index, int classes, int W, int H, int D, int tw, int th, int td,
+                      const UnetPatchPick* picks, int n, int32_t* origins, void* stream) {
+    const std::string w = "unet_patches_pick: ";
+    std::string e = patches_window_error(w, W, H, D, tw, th, td);
+    if (e.empty()) e = patches_class_error(w, (int64_t)W * H * D, classes);
+    if (!e.empty()) return fail(e);
+    if (!label || !index || !origins) return fail(w + "null device pointer");
+    if (n < 1 || n > UNET_PATCHES_MAX_PICKS) return fail(w + "n must be in [1, " + std::to_string(UNET_PATCHES_MAX_PICKS) + "], got " + std::to_string(n));
+    if (!picks) return fail(w + "null picks");
+    return run_on_device_of(label, stream, [&](hipStream_t s) { launch_patches_pick(label, index, classes, W, H, D, tw, th, td, picks, n, origins, s); });
+}
+int unet_patches_crop(const float* image, int channels, const float* label, int W, int H, int D, int tw, int th, int td,
+                      const int32_t* origin, float* x, float* lab, void* stream) {
+    const std::string w = "unet_patches_crop: ";
+    const std::string e = patches_window_error(w, W, H, D, tw, th, td);
+    if (!e.empty()) return fail(e);
+    if (channels < 1 || channels > 65534) return fail(w + "channels must be in [1, 65534], got " + std::to_string(channels));
+    if (td > 65535) return fail(w + "a window of more than 65535 slices");
+    if (!image || !x || !origin) return fail(w + "null device pointer");
+    if (lab && !label) return fail(w + "lab without a label to cut it from");
+    return run_on_device_of(image, stream, [&](hipStream_t s) { launch_patches_crop(image, channels, label, W, H, D, tw, th, td, origin, x, lab, s); });
+}
+int unet_patches_draws(uint64_t seed, uint64_t index, uint32_t first_k, int count, uint32_t* out) {
+    if (count < 0) return fail("unet_patches_draws: count must not be negative");
+    if (count && !out) return fail("unet_patches_draws: null output");
+    const uint64_t G = 0x9E3779B97F4A7C15ull;
+    auto mix = [](uint64_t z) {
+        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+        z ^= z >> 27; z *= 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    const uint64_t base = mix(mix(seed + G) ^ index);
+    for (int i = 0; i < count; ++i) out[i] = (uint32_t)(mix(base + ((uint64_t)first_k + (uint64_t)i + 1) * G) >> 32);
+    return 0;
+}
+
 // ---- test-time mirroring: the members' logits flipped back, swapped back and averaged (include/unet_mirror.h) ----
 static std::string mirror_args_error(const char* who, const void* stack, int out_c, int w, int h, int d, int n_members, const int* masks,
                                      int swap_axis, const int* pairs, int n_pairs) {

@@ -17,6 +17,7 @@
 #include "../../include/unet_hip.h"
 #include "../../include/unet_instances.h"
 #include "../../include/unet_morph.h"
+#include "../../include/unet_patches.h"
 #include "../../include/unet_postproc.h"
 #include "../../include/unet_preproc.h"
 #include "../../include/unet_qc.h"
@@ -375,6 +376,16 @@ void launch_feed_label_max(const float* label, int64_t S, int* out_max, void* sc
 void launch_feed_prepare(const float* image0, float* label, int64_t S, int normalize, int shift, int* label_max, void* scratch,
                          hipStream_t s);
 void launch_feed_target(const float* label, int64_t S, int normalize, int64_t* target, void* scratch, hipStream_t s);
+
+// kernels_patches.hip: the per-class index of a canvas label, the pick of a window and its crop (include/unet_patches.h); K = the
+// number of classes (2 for classes == 0); picks: n host entries, read before the return
+int64_t patches_segments(int64_t voxels);
+size_t patches_index_bytes(int64_t voxels, int K);
+void launch_patches_index(const float* label, int64_t voxels, int classes, int32_t* index, hipStream_t s);
+void launch_patches_pick(const float* label, const int32_t* index, int classes, int W, int H, int D, int tw, int th, int td,
+                         const UnetPatchPick* picks, int n, int32_t* origins, hipStream_t s);
+void launch_patches_crop(const float* image, int channels, const float* label, int W, int H, int D, int tw, int th, int td,
+                         const int32_t* origin, float* x, float* lab, hipStream_t s);
 
 // kernels_postproc.hip: the inference post-processing chain (include/unet_postproc.h)
 size_t postproc_scratch_bytes(int planes, int64_t S);

@@ -209,6 +209,14 @@ class TrainingFeed:
             shift = self.max_template_label if self.shifted[i] else 0
             if shift or not self.is_label:
                 prepare(lab, t1w, normalize=not self.is_label, shift_by=shift, scratch=self._scratch("feed", feed_scratch_bytes(S)))
+        return self._finish(index, is_template, x, lab)
+
+    def _finish(self, index, is_template, x, lab):
+        """the tail of a sample, in place on x {1,in,D,H,W} / lab {D,H,W} at model.dim (also patches.WindowFeed's): simulate_modality,
+        augmentation, target"""
+        D, H, W = self.size
+        S = self.voxels
+        t1w = x.view(-1)[:S]
         # simulate_modality (train.cpp:459-462), seed = seed_id as an unsigned int
         r = G.sim_to_struct(G.make_simulate_recipe((W, H, D), self.model.out_count if is_template else None, index))
         need = E.size_query(E.lib.unet_simulate_modality_scratch_bytes, C.byref(r))
