@@ -38,6 +38,7 @@ from . import stats  # noqa: F401  (the module: stats.EXPORTS the symbols of inc
 from . import calib  # noqa: F401  (the module: calib.EXPORTS the symbols of include/unet_calib.h)
 from . import recal  # noqa: F401  (the module: recal.EXPORTS the symbols of include/unet_recal.h)
 from . import patches  # noqa: F401  (the module: patches.EXPORTS the symbols of include/unet_patches.h)
+from . import coreg  # noqa: F401  (the module: coreg.EXPORTS the symbols of include/unet_coreg.h)
 from .patches import WindowFeed, to_canvas  # noqa: F401
 
 

@@ -2603,6 +2603,95 @@ int unet_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, cons
     });
 }
 
+// ---- the co-registration of two intensity images (include/unet_coreg.h) ----
+static bool coreg_bins_ok(int bins) { return bins == 8 || bins == 16 || bins == 32; }
+static std::string coreg_grids_error(const std::string& w, const void* fixed, int fw, int fh, int fd, const void* moving, int mw, int mh,
+                                     int md, int bins) {
+    if (!fixed) return w + "null fixed";
+    if (!moving) return w + "null moving";
+    if (fw <= 0 || fh <= 0 || fd <= 0) return w + "fixed dimensions must be positive";
+    if (mw <= 0 || mh <= 0 || md <= 0) return w + "moving dimensions must be positive";
+    if ((int64_t)fw * fh * fd >= ((int64_t)1 << 31)) return w + "the fixed grid must stay below 2^31 voxels";
+    if ((int64_t)mw * mh * md >= ((int64_t)1 << 31)) return w + "the moving grid must stay below 2^31 voxels";
+    if (!coreg_bins_ok(bins)) return w + "bins must be 8, 16 or 32, got " + std::to_string(bins);
+    return std::string();
+}
+int unet_coreg_scratch_bytes(int64_t fixed_voxels, int bins, int max_iterations, size_t* bytes) {
+    if (fixed_voxels <= 0 || fixed_voxels >= ((int64_t)1 << 31)) return fail("unet_coreg: fixed_voxels must be in [1, 2^31)");
+    if (!coreg_bins_ok(bins)) return fail("unet_coreg: bins must be 8, 16 or 32, got " + std::to_string(bins));
+    if (max_iterations < 1 || max_iterations > UNET_COREG_MAX_ITERATIONS) return fail("unet_coreg: max_iterations must be in [1, 1024]");
+    if (!bytes) return fail("unet_coreg_scratch_bytes: null output");
+    *bytes = coreg_scratch_bytes(bins);   // the state and the counters: nothing per voxel, nothing per iteration
+    return 0;
+}
+int unet_coreg_code(const float* image, int64_t voxels, float lo, float hi, int bins, uint8_t* codes, void* stream) {
+    const std::string w = "unet_coreg_code: ";
+    if (std::string e = ptr_error(w, image, "image", 4); !e.empty()) return fail(e);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail(w + "voxels must be in [1, 2^31)");
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(w + "lo and hi must be finite");
+    if (!(lo < hi)) return fail(w + "lo must be below hi");
+    if (!coreg_bins_ok(bins)) return fail(w + "bins must be 8, 16 or 32, got " + std::to_string(bins));
+    const float diff = hi - lo, scale = (float)bins / diff;   // fp32: one subtraction, one division
+    if (!std::isfinite(diff) || !std::isfinite(scale) || !(scale > 0.f)) return fail(w + "the scale bins / (hi - lo) must be finite");
+    if (!codes) return fail(w + "null codes");
+    return run_on_device_of(codes, stream, [&](hipStream_t s) { launch_coreg_code(image, voxels, lo, scale, bins, codes, s); });
+}
+int unet_coreg_hist(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                    const float* maps, int K, int stride, uint32_t* hist, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    (void)scratch; (void)scratch_bytes;   // reserved
+    const std::string w = "unet_coreg_hist: ";
+    if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
+    if (!maps) return fail(w + "null maps");
+    if (K < 1 || K > UNET_COREG_MAX_MAPS) return fail(w + "K must be in [1, 25], got " + std::to_string(K));
+    if (!reg_stride_ok(stride)) return fail(w + "stride must be 1, 2, 4 or 8, got " + std::to_string(stride));
+    if (std::string e = ptr_error(w, hist, "hist", 4); !e.empty()) return fail(e);
+    if (impl < UNET_COREG_IMPL_DEFAULT || impl > UNET_COREG_IMPL_GLOBAL) return fail(w + "unknown impl " + std::to_string(impl));
+    return run_on_device_of(hist, stream, [&](hipStream_t s) {   // maps is consumed inside the launcher, before this returns
+        launch_coreg_hist(fixed, fw, fh, fd, moving, mw, mh, md, bins, maps, K, stride, hist, impl, s);
+    });
+}
+int unet_coreg_score(const uint32_t* hist, int K, int bins, int64_t* scores, void* stream) {
+    const std::string w = "unet_coreg_score: ";
+    if (std::string e = ptr_error(w, hist, "hist", 4); !e.empty()) return fail(e);
+    if (K < 1 || K > UNET_COREG_MAX_MAPS) return fail(w + "K must be in [1, 25], got " + std::to_string(K));
+    if (!coreg_bins_ok(bins)) return fail(w + "bins must be 8, 16 or 32, got " + std::to_string(bins));
+    if (std::string e = ptr_error(w, scores, "scores", 8); !e.empty()) return fail(e);
+    return run_on_device_of(scores, stream, [&](hipStream_t s) { launch_coreg_score(hist, K, bins, scores, s); });
+}
+int unet_coreg_search(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                      const float* init, const float* step, const int* stages, int n_stages, int max_iterations, float* map_out,
+                      int64_t* trace, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string w = "unet_coreg_search: ";
+    if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
+    if (!init) return fail(w + "null init");
+    if (!step) return fail(w + "null step");
+    bool any = false;
+    for (int i = 0; i < 12; ++i) {
+        if (!std::isfinite(step[i]) || step[i] < 0.f) return fail(w + "step[" + std::to_string(i) + "] must be finite and >= 0");
+        any |= step[i] > 0.f;
+    }
+    if (!any) return fail(w + "at least one step must be > 0");
+    if (n_stages < 1 || n_stages > UNET_COREG_MAX_STAGES) return fail(w + "n_stages must be in [1, 4], got " + std::to_string(n_stages));
+    if (!stages) return fail(w + "null stages");
+    for (int g = 0; g < n_stages; ++g) {
+        const std::string st = w + "stage " + std::to_string(g) + ": ";
+        if (!reg_stride_ok(stages[3 * g])) return fail(st + "stride must be 1, 2, 4 or 8, got " + std::to_string(stages[3 * g]));
+        if (stages[3 * g + 1] < 0 || stages[3 * g + 1] > stages[3 * g + 2] || stages[3 * g + 2] > UNET_COREG_MAX_LEVEL)
+            return fail(st + "levels must satisfy 0 <= first_level <= last_level <= 20");
+    }
+    if (max_iterations < 1 || max_iterations > UNET_COREG_MAX_ITERATIONS) return fail(w + "max_iterations must be in [1, 1024]");
+    if (std::string e = ptr_error(w, map_out, "map_out", 4); !e.empty()) return fail(e);
+    if ((uintptr_t)trace & 7) return fail(w + "trace must be 8-byte aligned");
+    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return fail(e);
+    if (impl < UNET_COREG_IMPL_DEFAULT || impl > UNET_COREG_IMPL_GLOBAL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    if (scratch_bytes < coreg_scratch_bytes(bins)) return fail(w + "scratch too small (see unet_coreg_scratch_bytes)");
+    return run_on_device_of(map_out, stream, [&](hipStream_t s) {   // init, step and stages are consumed inside the launcher
+        launch_coreg_search(fixed, fw, fh, fd, moving, mw, mh, md, bins, init, step, stages, n_stages, max_iterations, map_out, trace, info,
+                            impl, scratch, s);
+    });
+}
+
 // ---- the tables of a label map (include/unet_table.h) ----
 static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
                                       size_t scratch_bytes) {

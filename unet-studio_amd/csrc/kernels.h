@@ -11,6 +11,7 @@
 #include "../../include/unet_recal.h"
 #include "../../include/unet_components.h"
 #include "../../include/unet_connectivity.h"
+#include "../../include/unet_coreg.h"
 #include "../../include/unet_distance.h"
 #include "../../include/unet_ensemble.h"
 #include "../../include/unet_feed.h"
@@ -493,6 +494,18 @@ void launch_reg_search(const void* subject, int sbytes, int sw, int sh, int sd, 
                        float* map_out, int64_t* trace, int64_t* info, int impl, void* scratch, hipStream_t s);
 void launch_reg_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
                       const uint16_t* atlas, int n_tissues, const float* map, uint16_t* out, uint32_t* counts, hipStream_t s);
+
+// kernels_coreg.hip: the co-registration of two intensity images (include/unet_coreg.h); fixed and moving are codes; scale =
+// (float)bins / (hi - lo), formed by the caller; maps, init, step, stages: host arrays, read before the return.  Only the search uses
+// scratch
+size_t coreg_scratch_bytes(int bins);
+void launch_coreg_code(const float* image, int64_t voxels, float lo, float scale, int bins, uint8_t* codes, hipStream_t s);
+void launch_coreg_hist(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                       const float* maps, int K, int stride, uint32_t* hist, int impl, hipStream_t s);
+void launch_coreg_score(const uint32_t* hist, int K, int bins, int64_t* scores, hipStream_t s);
+void launch_coreg_search(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                         const float* init, const float* step, const int* stages, int n_stages, int max_iterations, float* map_out,
+                         int64_t* trace, int64_t* info, int impl, void* scratch, hipStream_t s);
 
 // kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
 size_t table_scratch_bytes(int n_labels);

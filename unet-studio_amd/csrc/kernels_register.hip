@@ -20,6 +20,7 @@
 #include <string>
 
 #include "../../include/unet_register.h"
+#include "affine_search.h"
 #include "device_util.h"
 
 namespace unet {
@@ -75,40 +76,6 @@ __device__ __forceinline__ unsigned reg_tissue(const void* __restrict__ p, int b
     return v >= (unsigned)T ? 0u : v;
 }
 
-struct RegPos {
-    float qx, qy, qz;   // position + 0.5
-    bool in;
-};
-// map(x, y, z) + 0.5 in fp32, left to right, no fused multiply-add, and the inside test against float(dim); a NaN is outside
-__device__ __forceinline__ RegPos reg_locate(const float* m, int xi, int yi, int zi, int tw, int th, int td) {
-#pragma clang fp contract(off)
-    const float x = (float)xi, y = (float)yi, z = (float)zi;
-    RegPos p;
-    p.qx = (((m[0] * x + m[1] * y) + m[2] * z) + m[9]) + 0.5f;
-    p.qy = (((m[3] * x + m[4] * y) + m[5] * z) + m[10]) + 0.5f;
-    p.qz = (((m[6] * x + m[7] * y) + m[8] * z) + m[11]) + 0.5f;
-    p.in = p.qx >= 0.f && p.qy >= 0.f && p.qz >= 0.f && p.qx < (float)tw && p.qy < (float)th && p.qz < (float)td;
-    return p;
-}
-
-// A run of equal keys in registers (kernels_atlas.hip's): push() adds to the open run or hands the closed one to add(key, n)
-struct Run {
-    unsigned key, n;
-    template <typename Add> __device__ __forceinline__ void push(unsigned k, Add add) {
-        if (k == key) {
-            ++n;
-        } else {
-            if (n) add(key, n);
-            key = k;
-            n = 1u;
-        }
-    }
-    template <typename Add> __device__ __forceinline__ void close(Add add) {
-        if (n) add(key, n);
-        n = 0u;
-    }
-};
-
 // ---- joint histograms ------------------------------------------------------------------------------------------------------------
 template <bool LDS, bool DEV>
 __global__ void __launch_bounds__(REG_T) k_reg_hist(const void* __restrict__ subject, int sbytes, int sw, int sh, int sd,
@@ -136,7 +103,7 @@ __global__ void __launch_bounds__(REG_T) k_reg_hist(const void* __restrict__ sub
     // the counted voxels form an nx x ny x nz grid; a unit is REG_SEG of them along x
     const int nx = (sw + s - 1) / s, ny = (sh + s - 1) / s, nz = (sd + s - 1) / s, nseg = (nx + REG_SEG - 1) / REG_SEG;
     const int64_t units = (int64_t)nseg * ny * nz;
-    Run run = {0u, 0u};
+    AffRun run = {0u, 0u};
     for (int64_t u = (int64_t)blockIdx.x * REG_T + threadIdx.x; u < units; u += (int64_t)gridDim.x * REG_T) {
         const unsigned u32 = (unsigned)u;   // units <= voxels < 2^31: 32-bit division
         const int seg = (int)(u32 % (unsigned)nseg), r = (int)(u32 / (unsigned)nseg);
@@ -151,7 +118,7 @@ __global__ void __launch_bounds__(REG_T) k_reg_hist(const void* __restrict__ sub
 #pragma unroll
             for (int j = 0; j < REG_SEG; ++j) {
                 if (j < n) {
-                    const RegPos p = reg_locate(m, (x0 + j) * s, yi, zi, tw, th, td);
+                    const AffPos p = aff_locate(m, (x0 + j) * s, yi, zi, tw, th, td);
                     unsigned b = 0u;
                     if (p.in) b = reg_tissue(tmpl, tbytes, ((int64_t)(int)floorf(p.qz) * th + (int)floorf(p.qy)) * tw + (int)floorf(p.qx), T);
                     run.push(kbase + a[j] + b, add);
@@ -168,52 +135,6 @@ __global__ void __launch_bounds__(REG_T) k_reg_hist(const void* __restrict__ sub
 }
 
 // ---- the search ------------------------------------------------------------------------------------------------------------------
-// the index of the j-th parameter with step > 0 (12 when there is none)
-__device__ __forceinline__ int reg_param(const RegPlan& p, int j) {
-    int i = 0;
-    for (; i < 12; ++i)
-        if (p.step[i] > 0.f && j-- == 0) break;
-    return i;
-}
-
-// c[i] moved by one step of level l: sign > 0 adds ldexpf(step[i], -l), sign < 0 subtracts it (one fp32 operation)
-__device__ __forceinline__ float reg_move(float c, float step, int level, int sign) {
-    const float d = ldexpf(step, -level);
-    return sign > 0 ? c + d : c - d;
-}
-
-// the map of a state: the matrix unchanged, t_r = u_r - ((c[3r]*cx + c[3r+1]*cy) + c[3r+2]*cz)
-__device__ __forceinline__ void reg_state_map(const float (&c)[12], const RegPlan& p, float* map) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int e = 0; e < 9; ++e) map[e] = c[e];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) map[9 + r] = c[9 + r] - ((c[3 * r] * p.cx + c[3 * r + 1] * p.cy) + c[3 * r + 2] * p.cz);
-}
-
-// Every thread of the block: thread k < K writes the map of candidate k of (stage g, level l); thread 0 the K and the stride.
-// lc: the state's parameters in LDS
-__device__ __forceinline__ void reg_candidates(RegState* st, const float* lc, const RegPlan& p, int g, int l) {
-    int P = 0;
-    for (int i = 0; i < 12; ++i) P += p.step[i] > 0.f ? 1 : 0;
-    const int K = 1 + 2 * P, k = threadIdx.x;
-    if (k < K) {
-        const int i = k ? reg_param(p, (k - 1) >> 1) : 12, sign = (k & 1) ? 1 : -1;
-        const float step = i < 12 ? p.step[i] : 0.f;
-        float c[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) c[e] = e == i ? reg_move(lc[e], step, l, sign) : lc[e];
-        float map[12];
-        reg_state_map(c, p, map);
-#pragma unroll
-        for (int e = 0; e < 12; ++e) st->cand[k * 12 + e] = map[e];
-    }
-    if (k == 0) {
-        st->K = K;
-        st->stride = p.stages[g][0];
-    }
-}
-
 __global__ void __launch_bounds__(REG_T) k_reg_init(RegState* st, uint32_t* __restrict__ hist, RegMap init, RegPlan p,
                                                     int64_t* __restrict__ trace, int64_t* __restrict__ info) {
 #pragma clang fp contract(off)
@@ -232,7 +153,7 @@ __global__ void __launch_bounds__(REG_T) k_reg_init(RegState* st, uint32_t* __re
         st->converged = 0;
     }
     if (threadIdx.x < 4) info[threadIdx.x] = 0;   // k_reg_step of iteration 0 always runs and overwrites them
-    reg_candidates(st, lc, p, 0, p.stages[0][1]);
+    aff_candidates(st, lc, p, 0, p.stages[0][1]);
     for (int e = threadIdx.x; e < REG_MAXK * p.T * p.T; e += REG_T) hist[e] = 0u;
     if (trace)
         for (int e = threadIdx.x; e < 4 * p.max_iterations; e += REG_T) trace[e] = -1;
@@ -283,8 +204,8 @@ __global__ void __launch_bounds__(REG_T) k_reg_step(RegState* st, uint32_t* __re
                 else l = p.stages[g][1];
             }
         } else {
-            const int i = reg_param(p, (best - 1) >> 1);
-            lc[i] = reg_move(lc[i], p.step[i], l, (best & 1) ? 1 : -1);
+            const int i = aff_param(p, (best - 1) >> 1);
+            lc[i] = aff_move(lc[i], p.step[i], l, (best & 1) ? 1 : -1);
             st->c[i] = lc[i];
         }
         if (it + 1 == p.max_iterations) done = 1;
@@ -296,13 +217,13 @@ __global__ void __launch_bounds__(REG_T) k_reg_step(RegState* st, uint32_t* __re
         float c[12], map[12];
 #pragma unroll
         for (int e = 0; e < 12; ++e) c[e] = lc[e];
-        reg_state_map(c, p, map);
+        aff_state_map(c, p, map);
 #pragma unroll
         for (int e = 0; e < 12; ++e) map_out[e] = map[e];
     }
     __syncthreads();
     if (lg[0]) return;   // nothing reads the candidates or the counters after the last iteration
-    reg_candidates(st, lc, p, lg[1], lg[2]);
+    aff_candidates(st, lc, p, lg[1], lg[2]);
     for (int e = threadIdx.x; e < K * T * T; e += REG_T) hist[e] = 0u;
 }
 
@@ -331,7 +252,7 @@ __global__ void __launch_bounds__(REG_T) k_reg_carry(const void* __restrict__ su
             continue;
         }
         const int x = i % sw, y = (i / sw) % sh, z = i / (sw * sh);
-        const RegPos p = reg_locate(lm, x, y, z, tw, th, td);
+        const AffPos p = aff_locate(lm, x, y, z, tw, th, td);
         const int ix = reg_index(p.qx, tw), iy = reg_index(p.qy, th), iz = reg_index(p.qz, td);
         unsigned result = 0u, kind = 2u;   // left
         if (p.in) {
