@@ -39,6 +39,7 @@ from . import calib  # noqa: F401  (the module: calib.EXPORTS the symbols of inc
 from . import recal  # noqa: F401  (the module: recal.EXPORTS the symbols of include/unet_recal.h)
 from . import patches  # noqa: F401  (the module: patches.EXPORTS the symbols of include/unet_patches.h)
 from . import coreg  # noqa: F401  (the module: coreg.EXPORTS the symbols of include/unet_coreg.h)
+from . import start  # noqa: F401  (the module: start.EXPORTS the symbols of include/unet_start.h)
 from .patches import WindowFeed, to_canvas  # noqa: F401
 
 

@@ -22,6 +22,7 @@ import torch
 from . import engine as E
 from . import register as R
 from . import space as SP
+from . import start as STA
 from . import stats as ST
 from .engine import UNetError
 
@@ -174,11 +175,16 @@ def robust_range(image, permille=(10, 990)):
 
 
 def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES, max_iterations=400,
-          impl=IMPL_DEFAULT):
+          impl=IMPL_DEFAULT, starts=None):
     """The moving image on the fixed image's grid.  moving, fixed: (D, H, W) float32 device tensors of one subject, voxel sizes
     (x, y, z).  In order: robust_range and code of both images; the start, register.centre_init(fixed.shape, fixed_vs, moving.shape,
     moving_vs) unless `init` (a map, fixed voxel -> moving position) is given; search; the moving image resampled through the map
     found, linearly.
+
+    starts: a start.Plan(degrees, n, rank_stride).  The moments of the two code images (codes 1..bins-1) give start.candidates
+    (the start above is only their fallback); one coreg.joint_hist per 25 of them at rank_stride and coreg.scores rank them; the n
+    best (the unrotated one always among them) are read back once, n searches run one after another on the stream, and the best
+    final state by start.best_of's key is taken from one readback of the n infos.  None: the single search, unchanged.
 
     Returns (map float32 {12} on the device, info int64 {4} on the device = (iterations, converged, score, stage of the last
     iteration), moved float32 of fixed's shape).  The host reads the two ranges before the search and the 12 floats of the map
@@ -191,7 +197,22 @@ def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_S
     m0 = R._map12(init, "align")
     fc = code(fixed, *robust_range(fixed), b)
     mc = code(moving, *robust_range(moving), b)
-    map_dev, _, info = search(fc, mc, b, m0, step=step, stages=stages, max_iterations=max_iterations, impl=impl, trace=False)
+    if starts is None:
+        map_dev, _, info = search(fc, mc, b, m0, step=step, stages=stages, max_iterations=max_iterations, impl=impl, trace=False)
+    else:
+        degrees, n, rank_stride = STA._plan(starts, "coreg.align")
+        mom = torch.stack([STA.moments(fc, 1, b - 1), STA.moments(mc, 1, b - 1)]).cpu().numpy()
+        maps = STA.candidates(mom[0], mom[1], degrees, fallback=m0)
+        S = int(maps.shape[0])
+        ranked = torch.cat([scores(joint_hist(fc, mc, b, maps[k:k + MAX_MAPS], stride=rank_stride, impl=impl))
+                            for k in range(0, S, MAX_MAPS)]).cpu().numpy()
+        order = sorted(range(S), key=lambda k: (-int(ranked[k]), k))[:min(n, S)]
+        always = STA.ALWAYS if S > STA.ALWAYS else 0
+        if always not in order:
+            order[-1] = always
+        runs = [search(fc, mc, b, maps[k], step=step, stages=stages, max_iterations=max_iterations, impl=impl, trace=False) for k in order]
+        best = STA.best_of(torch.stack([r[2] for r in runs]).cpu().numpy())
+        map_dev, info = runs[best][0], runs[best][2]
     m = map_dev.cpu().numpy()
     moved = SP.resample(moving, tuple(fixed.shape), (m[:9], m[9:]), mode="linear")
     return map_dev, info, moved

@@ -3,7 +3,7 @@
 # Objects are compiled in parallel (one hipcc per source) and only when the source or a header is newer.
 set -e
 cd "$(dirname "$0")"
-SRCS="graph.cpp engine.cpp comm.cpp kernels_direct.hip kernels_elem.hip kernels_sgd_pack.hip kernels_mfma_conv.hip kernels_mfma_deep.hip kernels_mfma_conv_z16.hip kernels_mfma_s2.hip kernels_mfma_s2_wgrad.hip kernels_mfma_wgrad.hip kernels_mfma_wgrad_z.hip kernels_mfma_wgrad_zd.hip kernels_augment.hip kernels_mfma_f32.hip kernels_qc.hip kernels_feed.hip kernels_postproc.hip kernels_space.hip kernels_tiles.hip kernels_mirror.hip kernels_ensemble.hip kernels_preproc.hip kernels_components.hip kernels_atlas.hip kernels_register.hip kernels_table.hip kernels_distance.hip kernels_instances.hip kernels_morph.hip kernels_stats.hip kernels_calib.hip kernels_recal.hip kernels_patches.hip kernels_coreg.hip"
+SRCS="graph.cpp engine.cpp comm.cpp kernels_direct.hip kernels_elem.hip kernels_sgd_pack.hip kernels_mfma_conv.hip kernels_mfma_deep.hip kernels_mfma_conv_z16.hip kernels_mfma_s2.hip kernels_mfma_s2_wgrad.hip kernels_mfma_wgrad.hip kernels_mfma_wgrad_z.hip kernels_mfma_wgrad_zd.hip kernels_augment.hip kernels_mfma_f32.hip kernels_qc.hip kernels_feed.hip kernels_postproc.hip kernels_space.hip kernels_tiles.hip kernels_mirror.hip kernels_ensemble.hip kernels_preproc.hip kernels_components.hip kernels_atlas.hip kernels_register.hip kernels_table.hip kernels_distance.hip kernels_instances.hip kernels_morph.hip kernels_stats.hip kernels_calib.hip kernels_recal.hip kernels_patches.hip kernels_coreg.hip kernels_start.hip"
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wno-unused-result"
 mkdir -p build
 newest_hdr=$(ls -t *.h *.hpp ../../include/*.h | head -1)
@@ -34,19 +34,23 @@ for pair in conv_z:kernels_mfma_conv wgrad_z:kernels_mfma_wgrad_z conv_zdma:kern
         ;;
     esac
 done
-# the co-registration kernels (kernels_coreg.hip) must not spill: read every kernel's scratch size from the compiler's resource-usage
-# remarks whenever the file was rebuilt (the remarks stay in build/kernels_coreg.remarks: registers, LDS, occupancy)
-case " $todo " in *" kernels_coreg.hip "*)
-    hipcc $FLAGS --cuda-device-only -c -Rpass-analysis=kernel-resource-usage kernels_coreg.hip -o build/kernels_coreg.dev 2> build/kernels_coreg.remarks
-    n=$(grep -c 'ScratchSize \[bytes/lane\]: 0 ' build/kernels_coreg.remarks || true)
-    bad=$(grep -c 'ScratchSize \[bytes/lane\]: [1-9]' build/kernels_coreg.remarks || true)
-    if [ "$n" -lt 10 ] || [ "$bad" -ne 0 ]; then
-        echo "kernels_coreg.hip: expected 10 kernels without scratch, found $n without and $bad with (build/kernels_coreg.remarks)"
-        rm -f build/kernels_coreg.o; exit 1
-    fi
-    echo "kernels_coreg.hip: $n kernels, no scratch"
-    ;;
-esac
+# the co-registration kernels (kernels_coreg.hip) and the kernels of the starts (kernels_start.hip) must not spill: read every
+# kernel's scratch size from the compiler's resource-usage remarks whenever the file was rebuilt (the remarks stay in
+# build/<file>.remarks: registers, LDS, occupancy)
+for pair in kernels_coreg:10 kernels_start:6; do
+    f=${pair%%:*}; want=${pair##*:}
+    case " $todo " in *" $f.hip "*)
+        hipcc $FLAGS --cuda-device-only -c -Rpass-analysis=kernel-resource-usage $f.hip -o build/$f.dev 2> build/$f.remarks
+        n=$(grep -c 'ScratchSize \[bytes/lane\]: 0 ' build/$f.remarks || true)
+        bad=$(grep -c 'ScratchSize \[bytes/lane\]: [1-9]' build/$f.remarks || true)
+        if [ "$n" -lt "$want" ] || [ "$bad" -ne 0 ]; then
+            echo "$f.hip: expected $want kernels without scratch, found $n without and $bad with (build/$f.remarks)"
+            rm -f build/$f.o; exit 1
+        fi
+        echo "$f.hip: $n kernels, no scratch"
+        ;;
+    esac
+done
 OBJS=""
 for f in $SRCS; do OBJS="$OBJS build/${f%.*}.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o ../libunet_hip.so $OBJS -ldl

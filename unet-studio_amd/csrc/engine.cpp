@@ -2692,6 +2692,94 @@ int unet_coreg_search(const uint8_t* fixed, int fw, int fh, int fd, const uint8_
     });
 }
 
+// ---- the starts of a registration (include/unet_start.h) ----
+int unet_start_scratch_bytes(int n_tissues, int n, size_t* bytes) {
+    if (n_tissues < 2 || n_tissues > UNET_REG_MAX_TISSUES) return fail("unet_start: n_tissues must be in [2, 16], got " + std::to_string(n_tissues));
+    if (n < 1 || n > UNET_START_MAX_STATES) return fail("unet_start: n must be in [1, 4], got " + std::to_string(n));
+    if (!bytes) return fail("unet_start_scratch_bytes: null output");
+    *bytes = start_scratch_bytes(n_tissues, n);   // the states, their counters and the sequential searches' scratch: nothing per voxel
+    return 0;
+}
+int unet_start_moments(const void* volume, int vbytes, int w, int h, int d, int lo, int hi, uint64_t* sums, void* stream) {
+    const std::string wh = "unet_start_moments: ";
+    if (!volume) return fail(wh + "null volume");
+    if (vbytes != 1 && vbytes != 2) return fail(wh + "vbytes must be 1 or 2, got " + std::to_string(vbytes));
+    if (w <= 0 || h <= 0 || d <= 0) return fail(wh + "volume dimensions must be positive");
+    if (w > UNET_START_MAX_DIM || h > UNET_START_MAX_DIM || d > UNET_START_MAX_DIM) return fail(wh + "volume dimensions must stay below 65536");
+    if ((int64_t)w * h * d >= ((int64_t)1 << 31)) return fail(wh + "the volume must stay below 2^31 voxels");
+    if (lo < 0 || lo > 65535) return fail(wh + "lo must be in [0, 65535], got " + std::to_string(lo));
+    if (hi < 0 || hi > 65535) return fail(wh + "hi must be in [0, 65535], got " + std::to_string(hi));
+    if (std::string e = ptr_error(wh, sums, "sums", 8); !e.empty()) return fail(e);
+    return run_on_device_of(sums, stream, [&](hipStream_t s) { launch_start_moments(volume, vbytes, w, h, d, lo, hi, sums, s); });
+}
+int unet_start_pick(const uint32_t* hist, int S, int n_tissues, const float* maps, int n, int always, int64_t* scores, float* inits,
+                    int32_t* picked, void* stream) {
+    const std::string w = "unet_start_pick: ";
+    if (std::string e = ptr_error(w, hist, "hist", 4); !e.empty()) return fail(e);
+    if (S < 1 || S > UNET_START_MAX_STARTS) return fail(w + "S must be in [1, 125], got " + std::to_string(S));
+    if (n_tissues < 2 || n_tissues > UNET_REG_MAX_TISSUES) return fail(w + "n_tissues must be in [2, 16], got " + std::to_string(n_tissues));
+    if (std::string e = ptr_error(w, maps, "maps", 4); !e.empty()) return fail(e);
+    if (n < 1 || n > UNET_START_MAX_STATES || n > S) return fail(w + "n must be in [1, min(S, 4)], got " + std::to_string(n));
+    if (always < -1 || always >= S) return fail(w + "always must be -1 or in [0, S), got " + std::to_string(always));
+    if (std::string e = ptr_error(w, scores, "scores", 8); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, inits, "inits", 4); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, picked, "picked", 4); !e.empty()) return fail(e);
+    return run_on_device_of(picked, stream, [&](hipStream_t s) { launch_start_pick(hist, S, n_tissues, maps, n, always, scores, inits, picked, s); });
+}
+int unet_start_search(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                      int n_tissues, const float* inits, int n, const float* step, const int* stages, int n_stages, int max_iterations,
+                      float* maps_out, int64_t* trace, int64_t* info, int32_t* best, float* best_map, int impl, void* scratch,
+                      size_t scratch_bytes, void* stream) {
+    const std::string w = "unet_start_search: ";
+    const std::string e = reg_grids_error("unet_start_search", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (std::string pe = ptr_error(w, inits, "inits", 4); !pe.empty()) return fail(pe);
+    if (n < 1 || n > UNET_START_MAX_STATES) return fail(w + "n must be in [1, 4], got " + std::to_string(n));
+    if (!step) return fail(w + "null step");
+    bool any = false;
+    for (int i = 0; i < 12; ++i) {
+        if (!std::isfinite(step[i]) || step[i] < 0.f) return fail(w + "step[" + std::to_string(i) + "] must be finite and >= 0");
+        any |= step[i] > 0.f;
+    }
+    if (!any) return fail(w + "at least one step must be > 0");
+    if (n_stages < 1 || n_stages > UNET_REG_MAX_STAGES) return fail(w + "n_stages must be in [1, 4], got " + std::to_string(n_stages));
+    if (!stages) return fail(w + "null stages");
+    for (int g = 0; g < n_stages; ++g) {
+        const std::string st = w + "stage " + std::to_string(g) + ": ";
+        if (!reg_stride_ok(stages[3 * g])) return fail(st + "stride must be 1, 2, 4 or 8, got " + std::to_string(stages[3 * g]));
+        if (stages[3 * g + 1] < 0 || stages[3 * g + 1] > stages[3 * g + 2] || stages[3 * g + 2] > UNET_REG_MAX_LEVEL)
+            return fail(st + "levels must satisfy 0 <= first_level <= last_level <= 20");
+    }
+    if (max_iterations < 1 || max_iterations > UNET_REG_MAX_ITERATIONS) return fail(w + "max_iterations must be in [1, 1024]");
+    if (std::string pe = ptr_error(w, maps_out, "maps_out", 4); !pe.empty()) return fail(pe);
+    if ((uintptr_t)trace & 7) return fail(w + "trace must be 8-byte aligned");
+    if (std::string pe = ptr_error(w, info, "info", 8); !pe.empty()) return fail(pe);
+    if (std::string pe = ptr_error(w, best, "best", 4); !pe.empty()) return fail(pe);
+    if (std::string pe = ptr_error(w, best_map, "best_map", 4); !pe.empty()) return fail(pe);
+    if (impl < UNET_START_IMPL_DEFAULT || impl > UNET_START_IMPL_SEQUENTIAL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    if (scratch_bytes < start_scratch_bytes(n_tissues, n)) return fail(w + "scratch too small (see unet_start_scratch_bytes)");
+    if (impl != UNET_START_IMPL_SEQUENTIAL)   // DEFAULT: BATCHED
+        return run_on_device_of(maps_out, stream, [&](hipStream_t s) {   // step and stages are consumed inside the launcher
+            launch_start_search(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, inits, n, step, stages, n_stages,
+                                max_iterations, maps_out, trace, info, best, best_map, scratch, s);
+        });
+    // SEQUENTIAL: the register module's entry point takes its start from the host: one copy and one wait, then n searches in a row
+    float host_inits[UNET_START_MAX_STATES * 12];
+    if (int rc = run_on_device_of(maps_out, stream, [&](hipStream_t s) {
+            HIP_OK(hipMemcpyAsync(host_inits, inits, (size_t)n * 12 * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_OK(hipStreamSynchronize(s));
+        }))
+        return rc;
+    for (int s = 0; s < n; ++s)
+        if (int rc = unet_reg_search(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, host_inits + 12 * s, step, stages,
+                                     n_stages, max_iterations, maps_out + 12 * s, trace ? trace + (size_t)s * 4 * max_iterations : nullptr,
+                                     info + 4 * s, UNET_REG_IMPL_DEFAULT, start_seq_scratch(scratch, n_tissues, n, s),
+                                     start_seq_scratch_bytes(n_tissues), stream))
+            return rc;
+    return run_on_device_of(maps_out, stream, [&](hipStream_t s) { launch_start_close(info, maps_out, n, best, best_map, s); });
+}
+
 // ---- the tables of a label map (include/unet_table.h) ----
 static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
                                       size_t scratch_bytes) {

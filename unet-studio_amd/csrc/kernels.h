@@ -24,6 +24,7 @@
 #include "../../include/unet_qc.h"
 #include "../../include/unet_register.h"
 #include "../../include/unet_space.h"
+#include "../../include/unet_start.h"
 #include "../../include/unet_stats.h"
 #include "../../include/unet_table.h"
 #include "../../include/unet_mirror.h"
@@ -506,6 +507,19 @@ void launch_coreg_score(const uint32_t* hist, int K, int bins, int64_t* scores, 
 void launch_coreg_search(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
                          const float* init, const float* step, const int* stages, int n_stages, int max_iterations, float* map_out,
                          int64_t* trace, int64_t* info, int impl, void* scratch, hipStream_t s);
+
+// kernels_start.hip: the starts of a registration (include/unet_start.h); inits and maps: device arrays; step, stages: host arrays,
+// read before the return.  start_seq_scratch: the scratch of state s's own search under UNET_START_IMPL_SEQUENTIAL
+size_t start_scratch_bytes(int n_tissues, int n);
+void* start_seq_scratch(void* scratch, int n_tissues, int n, int s);
+size_t start_seq_scratch_bytes(int n_tissues);
+void launch_start_moments(const void* vol, int vbytes, int w, int h, int d, int lo, int hi, uint64_t* sums, hipStream_t s);
+void launch_start_pick(const uint32_t* hist, int S, int n_tissues, const float* maps, int n, int always, int64_t* scores, float* inits,
+                       int32_t* picked, hipStream_t s);
+void launch_start_search(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                         int n_tissues, const float* inits, int n, const float* step, const int* stages, int n_stages, int max_iterations,
+                         float* maps_out, int64_t* trace, int64_t* info, int32_t* best, float* best_map, void* scratch, hipStream_t s);
+void launch_start_close(const int64_t* info, const float* maps_out, int n, int32_t* best, float* best_map, hipStream_t s);
 
 // kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
 size_t table_scratch_bytes(int n_labels);

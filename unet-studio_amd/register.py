@@ -6,7 +6,8 @@ regions on the subject's own grid.
                up to 25 candidates from one pass, the host enqueues the launches and reads nothing back
   carry        the atlas brought onto the subject grid through a map: the nearest template voxel when its tissue agrees, else the
                mode of the agreeing voxels of the 3x3x3 cube around it
-  parcellate   search from centre_init, carry, then atlas.grow on the subject grid for what carry left
+  parcellate   search from centre_init (or, with `starts`, the best of several searches from ranked starts: start.find), carry,
+               then atlas.grow on the subject grid for what carry left
 
 In place of the reference's linear_cuda (evaluate.cpp:19-26, TIPL's affine registration; TIPL is not in the reference tree, so
 these are this project's definitions and parity is NOT pinned).  Every choice is made on integer counts: the results are pinned to
@@ -184,17 +185,32 @@ class Atlas:
             raise UNetError("register.Atlas: n_regions must be in [1, 65535], got %r" % (n_regions,))
         self.template, self.template_vs, self.regions = template, vs, regions
         self.n_tissues, self.n_regions = int(n_tissues), int(n_regions)
+        self._moments = None
+
+    def moments(self):
+        """The template's foreground moments (start.moments over tissues 1..n_tissues-1) as 10 host integers: a constant of the
+        atlas, read from the device once (a host synchronisation) and kept."""
+        if self._moments is None:
+            from . import start as ST
+            self._moments = ST.moments(self.template, 1, self.n_tissues - 1).cpu().numpy()
+        return self._moments
 
 
 def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissues=5, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES,
-               max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT):
+               max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT, starts=None, template_moments=None):
     """The atlas's regions on the subject's grid.  subject_tissue: the subject's tissue map (an evaluation's label output), template:
     the template's, atlas: the corrected atlas on the template grid (atlas.prepare_atlas); (D, H, W) device tensors, voxel sizes
     (x, y, z).  search from `init` (centre_init when None), carry, then atlas.grow on the subject grid with the subject tissue as
     the tissue map, tissues 1..n_tissues-1 flagged, CLAMP | PRESERVE: the regions grow into what carry left.
 
+    starts: a start.Plan(degrees, n, rank_stride) replaces the single search with start.find (the best of n searches from starts
+    ranked among the moments-and-rotations candidates; `init`, when given, is only the fallback for moments that say nothing);
+    template_moments: the template's start.moments when the caller has them (Atlas.moments()).  None: the single search, unchanged.
+
     Returns (regions uint16 on the subject grid, report) with report = dict(map (m[9], t[3]) float32, iterations, converged, score,
-    direct, rescued, left, filled (uint32 {n_tissues} each), rounds, grow_converged).
+    direct, rescued, left, filled (uint32 {n_tissues} each), rounds, grow_converged); with `starts` also starts = start.report's
+    dict, and iterations, converged and score are the best state's.  With `starts` the host also waits once for the subject's
+    moments before the searches.
 
     Two host synchronisations: the 12 floats of the map after the search (carry's map travels in its launch arguments), and the
     reports, read back once at the end."""
@@ -204,8 +220,15 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
         if not (torch.is_tensor(subject_tissue) and torch.is_tensor(template)):
             raise UNetError("register.parcellate: subject_tissue and template must be device tensors")
         init = centre_init(tuple(subject_tissue.shape), subject_vs, tuple(template.shape), template_vs)
-    map_dev, _, info = search(subject_tissue, template, T, init, step=step, stages=stages, max_iterations=max_iterations, impl=impl,
-                              trace=False)
+    pending = None
+    if starts is not None:
+        from . import start as ST
+        degrees, n, rank_stride = ST._plan(starts, "register.parcellate")
+        map_dev, pending = ST.find(subject_tissue, template, T, template_moments=template_moments, degrees=degrees, n=n,
+                                   rank_stride=rank_stride, step=step, stages=stages, max_iterations=max_iterations, fallback=init)
+    else:
+        map_dev, _, info = search(subject_tissue, template, T, init, step=step, stages=stages, max_iterations=max_iterations, impl=impl,
+                                  trace=False)
     m = map_dev.cpu().numpy()                                         # host synchronisation 1
     regions, counts = carry(subject_tissue, template, atlas, T, m)
     g = A.grow(subject_tissue, regions, T, list(range(1, T)), flags=A.CLAMP | A.PRESERVE, max_rounds=max_rounds, smooth_rounds=smooth_rounds)
@@ -213,8 +236,16 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
     def u32(t):
         return t.view(torch.int32).cpu().numpy().view(np.uint32)
 
-    info_h, counts_h, filled, ginfo = info.cpu().numpy(), u32(counts), u32(g["filled"]), u32(g["info"])      # 2
+    found = None
+    if pending is not None:
+        found = ST.report(pending)
+        info_h = found["info"][found["best"]]
+    else:
+        info_h = info.cpu().numpy()
+    counts_h, filled, ginfo = u32(counts), u32(g["filled"]), u32(g["info"])                                   # 2
     report = dict(map=(m[:9].copy(), m[9:].copy()), iterations=int(info_h[0]), converged=bool(info_h[1]), score=int(info_h[2]),
                   direct=counts_h[0], rescued=counts_h[1], left=counts_h[2], filled=filled, rounds=int(ginfo[0]),
                   grow_converged=bool(ginfo[1]))
+    if found is not None:
+        report["starts"] = found
     return regions, report
