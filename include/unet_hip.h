@@ -251,6 +251,60 @@ int unet_op_convt_bwd_weight(int dtype, int impl, const void* x, const void* dy,
 int unet_op_pack_ndhwc(int dtype, const float* x_ncdhw, void* y_ndhwc, int C, int64_t S, void* stream);
 int unet_op_unpack_ncdhw(int dtype, const void* x_ndhwc, float* y_ncdhw, int C, int64_t S, void* stream);
 
+/* ---- the layer kernels between the convs (csrc/kernels_elem.hip), each launched through the function a plan's executor launches it
+ * through.  Tensors are [S][C] (S = D*H*W voxels, channels last) in the element type of `dtype`.  A source given as (x, C, scale,
+ * shift, act) is a view: the consumer sees act(x * scale[c] + shift[c]) (scale = shift = NULL: no affine; act as above). ---- */
+/* A norm layer's own forward launches (norm_fwd_passes, no statistics rows from a conv): stat fp32 [4][C] = {mean, rstd, scale = gamma *
+ * rstd, shift = beta - mean * scale} from the statistics of raw (biased variance, eps), rm / rv (may be NULL) updated with momentum 0.1
+ * and the unbiased variance; use_running = 1 (eval BatchNorm): mean = rm, var = rv, both unchanged.  act_out (may be NULL) receives
+ * the activated copy act(raw * scale + shift).  scratch: unet_op_scratch_bytes(1, C, D, H, W) bytes for any D * H * W = S (the
+ * statistics rows are written at its start). */
+int unet_op_norm_fwd(int dtype, const void* raw, const float* gamma, const float* beta, double eps, float* rm, float* rv, int use_running,
+                     int act, void* act_out, float* stat, int C, int64_t S, void* scratch, void* stream);
+/* That layer's backward launches (norm_bwd_passes): g holds dL/d(view of u) and becomes dL/d(raw u); stat as unet_op_norm_fwd left it.
+ * Writes coef fp32 [3][C] = {gamma * rstd, mean(dv), mean(dv * xhat)} and adds dgamma += sum dv * xhat, dbeta += sum dv
+ * (dv = dL/d(view) * act').  scratch as for unet_op_norm_fwd. */
+int unet_op_norm_bwd(int dtype, void* g, const void* u, const float* stat, int act, const float* gamma, float* coef, float* dgamma,
+                     float* dbeta, int C, int64_t S, void* scratch, void* stream);
+/* Which form each step of the two entries above takes for a training-mode layer with an activated copy, from the predicates the launchers
+ * branch on.  Read-only, launches nothing.  out = {forward finalize, activated copy, backward statistics, backward finalize,
+ * backward apply}:
+ * forward finalize:    0 in the prologue of the activated copy (k_norm_finalize_apply8), 1 k_norm_finalize with 64 threads per channel,
+ *                      2 with 256
+ * activated copy:      0 in that fused launch, 1 k_apply_view8g, 2 k_apply_view8, 3 k_materialize
+ * backward statistics: 0 k_norm_bwd_stats8 with the shuffle reduction, 1 with the LDS reduction, 2 k_stats_partial
+ * backward finalize:   0 in the prologue of the apply (k_norm_bwd_finalize_apply8), 1 k_norm_bwd_finalize with 64 threads, 2 with 256
+ * backward apply:      0 in that fused launch, 1 k_norm_bwd_apply8, 2 k_norm_bwd_apply */
+int unet_op_norm_choice(int dtype, int C, int64_t S, int out[5]);
+/* The copy a plan makes of one view or of the channel concatenation of two (launch_materialize; x1 = NULL, c1 = 0: one source) into
+ * out [S][c0 + c1], and its backward (launch_materialize_bwd): gout [S][c0 + c1] split into d0 [S][c0] and d1 [S][c1], each written
+ * (acc = 0) or added to (acc = 1); either may be NULL (that source needs no gradient) and is then left alone. */
+int unet_op_view(int dtype, const void* x0, int c0, const float* scale0, const float* shift0, int act0, const void* x1, int c1,
+                 const float* scale1, const float* shift1, int act1, void* out, int64_t S, void* stream);
+int unet_op_view_bwd(int dtype, const void* gout, void* d0, int c0, int acc0, void* d1, int c1, int acc1, int64_t S, void* stream);
+/* The activated copy of one view that consumers read (launch_apply_view: vectorised for bf16 with C % 8 == 0). */
+int unet_op_apply_view(int dtype, const void* x, int C, const float* scale, const float* shift, int act, void* out, int64_t S,
+                       void* stream);
+/* The view backward without a norm (launch_act_bwd): g[i] *= act'(u[i]), n elements. */
+int unet_op_act_bwd(int dtype, void* g, const void* u, int act, int64_t n, void* stream);
+/* MaxPool3d(2, 2), floor mode, of a view [D][H][W][C] into out [D/2][H/2][W/2][C]; a NaN wins its window.  Backward: the first
+ * maximum of a window in (z, y, x) order (the last NaN, if it holds one) takes gout's value, every other voxel -- the trailing plane
+ * of an odd extent included -- takes 0; dx is written (accumulate = 0) or added to.  An extent of 1 leaves an empty output, which no
+ * plan contains (unet_plan_create refuses the network): both entries refuse it and launch nothing. */
+int unet_op_maxpool_fwd(int dtype, const void* x, int C, const float* scale, const float* shift, int act, void* out, int D, int H, int W,
+                        void* stream);
+int unet_op_maxpool_bwd(int dtype, const void* x, int C, const float* scale, const float* shift, int act, const void* gout, void* dx,
+                        int accumulate, int D, int H, int W, void* stream);
+/* Upsample(scale 2, nearest) of a view [D][H][W][C] into out [2D][2H][2W][C]; backward: dx (+)= the sum of the 8 fine voxels of gout. */
+int unet_op_upsample_fwd(int dtype, const void* x, int C, const float* scale, const float* shift, int act, void* out, int D, int H, int W,
+                         void* stream);
+int unet_op_upsample_bwd(int dtype, const void* gout, void* dx, int C, int accumulate, int D, int H, int W, void* stream);
+/* A network output and its gradient: a view -> fp32 NCDHW (launch_export); fp32 NCDHW -> [S][C] of the element type, written or
+ * added to (launch_import_grad). */
+int unet_op_export_view(int dtype, const void* x, int C, const float* scale, const float* shift, int act, float* y_ncdhw, int64_t S,
+                        void* stream);
+int unet_op_import_grad(int dtype, const float* g_ncdhw, void* g, int C, int64_t S, int accumulate, void* stream);
+
 /* ---- gradient collectives over RCCL / xGMI ----
  * Replaces the reference's replica synchronisation: UNet3dImpl::add_gradient_from (unet.cpp:224-244; call site train.cpp:756-757:
  * per parameter `grad.to(device0)` + `add_` on the root) becomes ONE sum all-reduce of the flat fp32 gradient buffer (or of its

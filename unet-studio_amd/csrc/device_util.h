@@ -37,7 +37,9 @@ __device__ __forceinline__ float act_d(float v, int act) {
 
 template <typename T> __device__ __forceinline__ float view_ld(const SrcDesc& s, int64_t voxel, int c) {
     float v = ld<T>((const T*)s.ptr, voxel * s.C + c);
-    if (s.scale) v = v * s.scale[c] + s.shift[c];
+    // one rounding, spelled out: the vectorised copies (k_apply_view8*) and every backward kernel evaluate the pre-activation with fmaf,
+    // and the forward must land on the same side of an activation's kink as they do whatever the contraction mode of the including file
+    if (s.scale) v = fmaf(v, s.scale[c], s.shift[c]);
     return act_f(v, s.act);
 }
 

@@ -464,6 +464,9 @@ namespace {
 // The separate launches of a norm layer, shared by the executor (OP_NORM, view_backward) and the single-op surface.  Forward: the
 // statistics from `rows` partial rows in `partial` (0: a statistics pass over `raw` first; dbl: fp64 rows) or, in eval mode, the
 // running ones; then the activated copy into act_out (may be nullptr), in one launch with the finalize where the rows are few.
+// unet_op_norm_choice (below) restates which launch each step of these two functions ends in, for rows = 0 in training mode with an
+// activated copy: whoever changes how the predicates are combined here (fused only when !dbl && act_out; the backward's vec8_ok) changes
+// it there as well.
 void norm_fwd_passes(int dtype, const void* raw, int C, int64_t S, float* partial, int rows, bool dbl, bool eval, const float* gamma,
                      const float* beta, double eps, float* stat, float* rm, float* rv, int act, void* act_out, hipStream_t s) {
     if (eval) launch_norm_eval(C, gamma, beta, rm, rv, eps, stat, s);
@@ -1876,6 +1879,145 @@ int unet_op_pack_ndhwc(int dtype, const float* x, void* y, int C, int64_t S, voi
 }
 int unet_op_unpack_ncdhw(int dtype, const void* x, float* y, int C, int64_t S, void* stream) {
     OP_TRY({ launch_unpack_ncdhw(dtype, x, y, C, S, (hipStream_t)stream); })
+}
+
+// ---- the layer kernels of kernels_elem.hip, through the launchers the executor uses ----
+static void op_layer_args(const char* who, int dtype, int C, int64_t S) {
+    if ((dtype != UNET_DTYPE_F32 && dtype != UNET_DTYPE_BF16) || C < 1 || S < 1)
+        throw std::runtime_error(std::string(who) + ": unknown element type, or a size that is not positive");
+}
+static SrcDesc op_view_src(const void* x, int C, const float* scale, const float* shift, int act) {
+    if (!x || (scale == nullptr) != (shift == nullptr) || act < 0 || act > 3)
+        throw std::runtime_error("single-op view: null source, scale without shift (or the reverse), or unknown activation");
+    SrcDesc d;
+    d.ptr = x; d.C = C; d.scale = scale; d.shift = shift; d.act = act;
+    return d;
+}
+static void op_pool_dims(const char* who, int D, int H, int W) {
+    // Graph::build refuses a network in which a tensor's extent becomes zero, so no plan pools an extent of 1
+    if (D < 2 || H < 2 || W < 2) throw std::runtime_error(std::string(who) + ": max_pool of an extent below 2 leaves an empty tensor");
+}
+int unet_op_norm_fwd(int dtype, const void* raw, const float* gamma, const float* beta, double eps, float* rm, float* rv, int use_running,
+                     int act, void* act_out, float* stat, int C, int64_t S, void* scratch, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_norm_fwd", dtype, C, S);
+        if (!raw || !gamma || !beta || !stat || !scratch || (rm == nullptr) != (rv == nullptr) || (use_running && !rm))
+            throw std::runtime_error("unet_op_norm_fwd: null argument, or eval mode without running statistics");
+        norm_fwd_passes(dtype, raw, C, S, (float*)scratch, 0, false, use_running != 0, gamma, beta, eps, stat, rm, rv, act, act_out,
+                        (hipStream_t)stream);
+    })
+}
+int unet_op_norm_bwd(int dtype, void* g, const void* u, const float* stat, int act, const float* gamma, float* coef, float* dgamma,
+                     float* dbeta, int C, int64_t S, void* scratch, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_norm_bwd", dtype, C, S);
+        if (!g || !u || !stat || !gamma || !coef || !dgamma || !dbeta || !scratch) throw std::runtime_error("unet_op_norm_bwd: null argument");
+        norm_bwd_passes(dtype, g, u, C, S, stat, act, gamma, coef, dgamma, dbeta, (float*)scratch, 0, false, (hipStream_t)stream);
+    })
+}
+// the branches of norm_fwd_passes / norm_bwd_passes and of the launchers they call, from the launchers' own predicates (kernels.h).  How
+// the two pass functions combine them is restated here (see the note above norm_fwd_passes) and must follow them.
+int unet_op_norm_choice(int dtype, int C, int64_t S, int out[5]) {
+    try {
+        if (!out) throw std::runtime_error("unet_op_norm_choice: null output");
+        op_layer_args("unet_op_norm_choice", dtype, C, S);
+        const int rows = stats_blocks(S);
+        const bool fused = fused_norm_ok(dtype, C, rows);
+        const int separate = finalize_threads(rows) == 64 ? 1 : 2;
+        const ViewCopy copy = apply_view_form(dtype, C, S);
+        out[0] = fused ? 0 : separate;
+        out[1] = fused ? 0 : copy == ViewCopy::vec8g ? 1 : copy == ViewCopy::vec8 ? 2 : 3;
+        out[2] = !vec8_ok(dtype, C) ? 2 : C / 8 <= STATS8_SHUFFLE_MAX_G8 ? 0 : 1;
+        out[3] = fused ? 0 : separate;
+        out[4] = fused ? 0 : vec8_ok(dtype, C) ? 1 : 2;
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+int unet_op_view(int dtype, const void* x0, int c0, const float* scale0, const float* shift0, int act0, const void* x1, int c1,
+                 const float* scale1, const float* shift1, int act1, void* out, int64_t S, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_view", dtype, c0, S);
+        if (!out || c1 < 0 || (x1 == nullptr) != (c1 == 0)) throw std::runtime_error("unet_op_view: null output, or a second source without channels");
+        SrcDesc sd[2];
+        sd[0] = op_view_src(x0, c0, scale0, shift0, act0);
+        if (x1) sd[1] = op_view_src(x1, c1, scale1, shift1, act1);
+        launch_materialize(dtype, sd, x1 ? 2 : 1, out, S, (hipStream_t)stream);
+    })
+}
+int unet_op_view_bwd(int dtype, const void* gout, void* d0, int c0, int acc0, void* d1, int c1, int acc1, int64_t S, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_view_bwd", dtype, c0, S);
+        if (!gout || c1 < 0 || (d1 && !c1)) throw std::runtime_error("unet_op_view_bwd: null gradient, or a second destination without channels");
+        DstGrad dg[2];
+        dg[0].ptr = d0; dg[0].C = c0; dg[0].accumulate = acc0 ? 1 : 0;
+        dg[1].ptr = d1; dg[1].C = c1; dg[1].accumulate = acc1 ? 1 : 0;
+        launch_materialize_bwd(dtype, gout, dg, c1 ? 2 : 1, S, (hipStream_t)stream);
+    })
+}
+int unet_op_apply_view(int dtype, const void* x, int C, const float* scale, const float* shift, int act, void* out, int64_t S,
+                       void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_apply_view", dtype, C, S);
+        if (!out) throw std::runtime_error("unet_op_apply_view: null output");
+        launch_apply_view(dtype, op_view_src(x, C, scale, shift, act), out, S, (hipStream_t)stream);
+    })
+}
+int unet_op_act_bwd(int dtype, void* g, const void* u, int act, int64_t n, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_act_bwd", dtype, 1, n);
+        if (!g || !u || act < 0 || act > 3) throw std::runtime_error("unet_op_act_bwd: null argument or unknown activation");
+        launch_act_bwd(dtype, g, u, act, n, (hipStream_t)stream);
+    })
+}
+int unet_op_maxpool_fwd(int dtype, const void* x, int C, const float* scale, const float* shift, int act, void* out, int D, int H, int W,
+                        void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_maxpool_fwd", dtype, C, 1);
+        op_pool_dims("unet_op_maxpool_fwd", D, H, W);
+        if (!out) throw std::runtime_error("unet_op_maxpool_fwd: null output");
+        launch_maxpool_fwd(dtype, op_view_src(x, C, scale, shift, act), out, D, H, W, (hipStream_t)stream);
+    })
+}
+int unet_op_maxpool_bwd(int dtype, const void* x, int C, const float* scale, const float* shift, int act, const void* gout, void* dx,
+                        int accumulate, int D, int H, int W, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_maxpool_bwd", dtype, C, 1);
+        op_pool_dims("unet_op_maxpool_bwd", D, H, W);
+        if (!gout || !dx) throw std::runtime_error("unet_op_maxpool_bwd: null gradient");
+        DstGrad d; d.ptr = dx; d.C = C; d.accumulate = accumulate ? 1 : 0;
+        launch_maxpool_bwd(dtype, op_view_src(x, C, scale, shift, act), gout, d, D, H, W, (hipStream_t)stream);
+    })
+}
+int unet_op_upsample_fwd(int dtype, const void* x, int C, const float* scale, const float* shift, int act, void* out, int D, int H, int W,
+                         void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_upsample_fwd", dtype, C, (int64_t)D * H * W);
+        if (D < 1 || H < 1 || W < 1 || !out) throw std::runtime_error("unet_op_upsample_fwd: null output, or a size that is not positive");
+        launch_upsample_fwd(dtype, op_view_src(x, C, scale, shift, act), out, D, H, W, (hipStream_t)stream);
+    })
+}
+int unet_op_upsample_bwd(int dtype, const void* gout, void* dx, int C, int accumulate, int D, int H, int W, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_upsample_bwd", dtype, C, (int64_t)D * H * W);
+        if (D < 1 || H < 1 || W < 1 || !gout || !dx) throw std::runtime_error("unet_op_upsample_bwd: null gradient, or a size that is not positive");
+        DstGrad d; d.ptr = dx; d.C = C; d.accumulate = accumulate ? 1 : 0;
+        launch_upsample_bwd(dtype, gout, d, D, H, W, (hipStream_t)stream);
+    })
+}
+int unet_op_export_view(int dtype, const void* x, int C, const float* scale, const float* shift, int act, float* y, int64_t S,
+                        void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_export_view", dtype, C, S);
+        if (!y) throw std::runtime_error("unet_op_export_view: null output");
+        launch_export(dtype, op_view_src(x, C, scale, shift, act), y, S, (hipStream_t)stream);
+    })
+}
+int unet_op_import_grad(int dtype, const float* g, void* o, int C, int64_t S, int accumulate, void* stream) {
+    OP_TRY({
+        op_layer_args("unet_op_import_grad", dtype, C, S);
+        if (!g || !o) throw std::runtime_error("unet_op_import_grad: null argument");
+        launch_import_grad(dtype, g, o, C, S, accumulate ? 1 : 0, (hipStream_t)stream);
+    })
 }
 
 

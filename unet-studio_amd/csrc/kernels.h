@@ -100,6 +100,28 @@ void launch_stats_sum(const float* partial, int nblk, int C, float* out, hipStre
 // eval-mode bnorm: scale = gamma/sqrt(rv+eps), shift = beta - rm*scale (mean := rm, rstd := 1/sqrt(rv+eps))
 void launch_norm_eval(int C, const float* gamma, const float* beta, const float* rm, const float* rv, double eps, float* stat,
                       hipStream_t s);
+// The predicates the norm launchers and the copy launcher of kernels_elem.hip branch on.  unet_op_norm_choice (engine.cpp) reports
+// from the same functions, so the query and the launches cannot disagree.
+// bf16 with C/8 a power of two <= 256: the 16-B (8-channel) statistics / apply kernels of the backward (and k_colsum8)
+static inline bool vec8_ok(int dtype, int C) {
+    if (dtype != 1 || C % 8) return false;
+    int g8 = C / 8;
+    return g8 <= 256 && (g8 & (g8 - 1)) == 0;
+}
+constexpr int STATS8_SHUFFLE_MAX_G8 = 32;   // k_norm_bwd_stats8 / k_colsum8: shuffle reduction up to this many 8-channel groups, LDS above
+// few partial rows: the finalize runs in the prologue of the element-wise pass (k_norm_finalize_apply8, k_norm_bwd_finalize_apply8)
+constexpr int FUSED_MAX_ROWS = 128, FUSED_MAX_C = 512;
+static inline bool fused_norm_ok(int dtype, int C, int nblk) {
+    return dtype == 1 && C % 8 == 0 && C <= FUSED_MAX_C && 256 % (C / 8) == 0 && nblk <= FUSED_MAX_ROWS;
+}
+// threads per channel of the separate finalize kernels (k_norm_finalize, k_norm_bwd_finalize, k_stats_sum)
+static inline int finalize_threads(int nblk) { return nblk > 128 ? 256 : 64; }
+// the copy launch_apply_view makes: k_apply_view8g (voxel-walking, four loads in flight), k_apply_view8, or k_materialize
+enum class ViewCopy { vec8g, vec8, generic };
+static inline ViewCopy apply_view_form(int dtype, int C, int64_t S) {
+    if (dtype == 1 && C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0 && S * C >= (1 << 18)) return ViewCopy::vec8g;
+    return dtype == 1 && C % 8 == 0 ? ViewCopy::vec8 : ViewCopy::generic;
+}
 
 // ---- view backward: g holds dL/d(act(norm(u))) on entry ----
 // no norm: g *= act'(u)

@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(256) k_norm_bwd_stats8(const uint4* __restrict
     // wave totals through LDS (the serial loop over NV = 256 / G8 LDS rows per output -- 128 at 16 channels -- was as long as the
     // block's whole voxel loop).  G8 = 64..256: a wave holds each group at most once, the (<= 4) rows are summed from LDS as before.
     const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (G8 <= 32) {
+    if (G8 <= STATS8_SHUFFLE_MAX_G8) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float a = s1[e], b = s2[e];
@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(256) k_colsum8(const uint4* __restrict__ x8, i
         for (int e = 0; e < 8; ++e) s1[e] += f[e];
     }
     const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (G8 <= 32) {      // as in k_norm_bwd_stats8: shuffle tree over the lanes G8 apart, then the four wave totals
+    if (G8 <= STATS8_SHUFFLE_MAX_G8) {      // as in k_norm_bwd_stats8: shuffle tree over the lanes G8 apart, then the four wave totals
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float a = s1[e];
@@ -265,7 +265,6 @@ __global__ void __launch_bounds__(256) k_colsum8(const uint4* __restrict__ x8, i
         partial[(int64_t)blockIdx.x * C + gg * 8 + e] = a;
     }
 }
-static inline bool vec8_ok(int dtype, int C);
 // partial[blk][C]; returns the number of blocks, 0 when the vectorised form does not apply
 int launch_colsum_partial8(int dtype, const void* x, int C, int64_t S, float* partial, hipStream_t s) {
     if (!vec8_ok(dtype, C)) return 0;
@@ -274,11 +273,6 @@ int launch_colsum_partial8(int dtype, const void* x, int C, int64_t S, float* pa
     return nb;
 }
 
-static inline bool vec8_ok(int dtype, int C) {
-    if (dtype != 1 || C % 8) return false;
-    int g8 = C / 8;
-    return g8 <= 256 && (g8 & (g8 - 1)) == 0;
-}
 void launch_norm_bwd_partial(int dtype, void* g, const void* u, int C, int64_t S, const float* stat, int act, float* partial,
                              hipStream_t s) {
     int nb = stats_blocks(S);
@@ -334,7 +328,7 @@ __global__ void __launch_bounds__(256) k_norm_finalize(const float* __restrict__
 }
 void launch_norm_finalize(const float* partial, int nblk, int C, int64_t S, const float* gamma, const float* beta, double eps,
                           float* stat, float* rm, float* rv, double momentum, hipStream_t s, bool dbl) {
-    k_norm_finalize<<<C, nblk > 128 ? 256 : 64, 0, s>>>(partial, nblk, C, S, gamma, beta, eps, stat, rm, rv, momentum, dbl ? 1 : 0);
+    k_norm_finalize<<<C, finalize_threads(nblk), 0, s>>>(partial, nblk, C, S, gamma, beta, eps, stat, rm, rv, momentum, dbl ? 1 : 0);
 }
 
 // out[c][j] = sum over blocks of partial[blk][c][j]   (one wave per channel, fp64, fixed order)
@@ -346,7 +340,7 @@ __global__ void __launch_bounds__(256) k_stats_sum(const float* __restrict__ par
     if (threadIdx.x == 0) { out[c * 2] = (float)a; out[c * 2 + 1] = (float)b; }
 }
 void launch_stats_sum(const float* partial, int nblk, int C, float* out, hipStream_t s, bool dbl) {
-    k_stats_sum<<<C, nblk > 128 ? 256 : 64, 0, s>>>(partial, nblk, C, out, dbl ? 1 : 0);
+    k_stats_sum<<<C, finalize_threads(nblk), 0, s>>>(partial, nblk, C, out, dbl ? 1 : 0);
 }
 
 __global__ void k_norm_eval(int C, const float* gamma, const float* beta, const float* rm, const float* rv, double eps, float* stat) {
@@ -377,7 +371,7 @@ __global__ void __launch_bounds__(256) k_norm_bwd_finalize(const float* __restri
 }
 void launch_norm_bwd_finalize(const float* partial, int nblk, int C, int64_t S, const float* gamma, const float* stat, float* coef,
                               float* dgamma, float* dbeta, hipStream_t s, bool dbl) {
-    k_norm_bwd_finalize<<<C, nblk > 128 ? 256 : 64, 0, s>>>(partial, nblk, C, S, gamma, stat, coef, dgamma, dbeta, dbl ? 1 : 0);
+    k_norm_bwd_finalize<<<C, finalize_threads(nblk), 0, s>>>(partial, nblk, C, S, gamma, stat, coef, dgamma, dbeta, dbl ? 1 : 0);
 }
 
 // norm backward with few partial rows: k_norm_bwd_finalize in the prologue of k_norm_bwd_apply8 (see k_norm_finalize_apply8)
@@ -447,7 +441,6 @@ void launch_norm_bwd_apply(int dtype, void* g, const void* u, int C, int64_t S, 
     UNET_DISPATCH(dtype, (k_norm_bwd_apply<T><<<cdiv64(S * C, 256), 256, 0, s>>>((T*)g, (const T*)u, C, S * C, stat, coef, act)));
 }
 
-static inline bool fused_norm_ok(int dtype, int C, int nblk);
 static inline int64_t fused_vpb(int C, int64_t S);
 bool launch_norm_bwd_finalize_apply(int dtype, const float* partial, int nblk, int C, int64_t S, const float* gamma, const float* stat,
                                     float* coef, float* dgamma, float* dbeta, void* g, const void* u, int act, hipStream_t s) {
@@ -611,7 +604,8 @@ __global__ void __launch_bounds__(256) k_apply_view8g(SrcDesc src, uint4* __rest
     for (; v < v1; v += NV) out[v * G8 + grp] = one(in[v * G8 + grp]);
 }
 void launch_apply_view(int dtype, SrcDesc src, void* out, int64_t S, hipStream_t s) {
-    if (dtype == 1 && src.C % 8 == 0 && src.C <= 2048 && 256 % (src.C / 8) == 0 && S * src.C >= (1 << 18)) {
+    const ViewCopy form = apply_view_form(dtype, src.C, S);
+    if (form == ViewCopy::vec8g) {
         int64_t vpb = (S + 4095) / 4096;
         const int64_t nv4 = 4 * (256 / (src.C / 8));
         if (vpb < nv4) vpb = nv4;
@@ -619,7 +613,7 @@ void launch_apply_view(int dtype, SrcDesc src, void* out, int64_t S, hipStream_t
         k_apply_view8g<<<cdiv64(S, vpb), 256, 0, s>>>(src, (uint4*)out, S, vpb);
         return;
     }
-    if (dtype == 1 && src.C % 8 == 0) {
+    if (form == ViewCopy::vec8) {
         int64_t n8 = S * src.C / 8;
         k_apply_view8<<<cdiv64(n8, 256), 256, 0, s>>>(src, (uint4*)out, n8);
     } else {
@@ -633,7 +627,6 @@ void launch_apply_view(int dtype, SrcDesc src, void* out, int64_t S, hipStream_t
 // from L2 (<= 64 KB), one thread per (channel, row quarter), fp64, fixed order; block 0 also leaves the values the later passes read
 // (stat / coef, running statistics, dgamma / dbeta).  (For the 64^3 and 128^3 levels -- 512..1024 rows -- that re-read is as much L2
 // traffic as the tensor itself, measured slower: they keep the separate finalize.)
-constexpr int FUSED_MAX_ROWS = 128, FUSED_MAX_C = 512;
 __device__ __forceinline__ void prologue_sums(const float* __restrict__ partial, int nblk, int C, double* sa, double* sb) {
     // sa / sb: LDS, 512 doubles each.  A thread owns a channel PAIR (one 16-B load per row: {a, b} of two channels) and every RG-th row;
     // its loads are issued sixteen at a time before the first add (one load per trip of a rolled loop is one exposed L2 latency per
@@ -702,9 +695,6 @@ __global__ void __launch_bounds__(256) k_norm_finalize_apply8(const float* __res
         }
         out[v * G8 + grp] = make_uint4(w[0], w[1], w[2], w[3]);
     }
-}
-static inline bool fused_norm_ok(int dtype, int C, int nblk) {
-    return dtype == 1 && C % 8 == 0 && C <= FUSED_MAX_C && 256 % (C / 8) == 0 && nblk <= FUSED_MAX_ROWS;
 }
 static inline int64_t fused_vpb(int C, int64_t S) {
     const int64_t nv = 256 / (C / 8);

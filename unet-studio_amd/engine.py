@@ -102,6 +102,21 @@ _sig("unet_op_convt_bwd_data", _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _v
 _sig("unet_op_convt_bwd_weight", _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp)
 _sig("unet_op_pack_ndhwc", _i, _i, _vp, _vp, _i, C.c_int64, _vp)
 _sig("unet_op_unpack_ncdhw", _i, _i, _vp, _vp, _i, C.c_int64, _vp)
+_i64, _d = C.c_int64, C.c_double
+_view = (_vp, _i, _vp, _vp, _i)   # a source as a view: x, C, scale, shift, act
+_sig("unet_op_norm_fwd", _i, _i, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _vp, _vp, _i, _i64, _vp, _vp)
+_sig("unet_op_norm_bwd", _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp)
+_sig("unet_op_norm_choice", _i, _i, _i, _i64, C.POINTER(_i))
+_sig("unet_op_view", _i, _i, *_view, *_view, _vp, _i64, _vp)
+_sig("unet_op_view_bwd", _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _vp)
+_sig("unet_op_apply_view", _i, _i, *_view, _vp, _i64, _vp)
+_sig("unet_op_act_bwd", _i, _i, _vp, _vp, _i, _i64, _vp)
+_sig("unet_op_maxpool_fwd", _i, _i, *_view, _vp, _i, _i, _i, _vp)
+_sig("unet_op_maxpool_bwd", _i, _i, *_view, _vp, _vp, _i, _i, _i, _i, _vp)
+_sig("unet_op_upsample_fwd", _i, _i, *_view, _vp, _i, _i, _i, _vp)
+_sig("unet_op_upsample_bwd", _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp)
+_sig("unet_op_export_view", _i, _i, *_view, _vp, _i64, _vp)
+_sig("unet_op_import_grad", _i, _i, _vp, _vp, _i, _i64, _i, _vp)
 
 # every symbol include/unet_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
@@ -112,6 +127,8 @@ EXPORTS = [
     "unet_sgd_step", "unet_sgd_step_packed", "unet_pack_filters", "unet_stream_create_cu_range", "unet_stream_destroy", "unet_plan_side_cu_range", "unet_set_error", "unet_comm_unique_id", "unet_comm_create", "unet_comm_create_all", "unet_comm_destroy", "unet_comm_rank",
     "unet_allreduce_grads", "unet_allreduce_grads_all", "unet_comm_broadcast", "unet_comm_join", "unet_op_scratch_bytes", "unet_op_conv_choice", "unet_op_conv3d_fwd", "unet_op_conv3d_fwd_fused", "unet_op_conv3d_pack", "unet_op_conv3d_fwd_packed", "unet_op_conv3d_bwd_data", "unet_op_conv3d_fwd_norm", "unet_op_conv3d_bwd_data_norm", "unet_op_conv3d_bwd_weight",
     "unet_op_convt_fwd", "unet_op_convt_bwd_data", "unet_op_convt_bwd_weight", "unet_op_pack_ndhwc", "unet_op_unpack_ncdhw",
+    "unet_op_norm_fwd", "unet_op_norm_bwd", "unet_op_norm_choice", "unet_op_view", "unet_op_view_bwd", "unet_op_apply_view", "unet_op_act_bwd",
+    "unet_op_maxpool_fwd", "unet_op_maxpool_bwd", "unet_op_upsample_fwd", "unet_op_upsample_bwd", "unet_op_export_view", "unet_op_import_grad",
 ]
 
 
