@@ -40,6 +40,7 @@ from . import recal  # noqa: F401  (the module: recal.EXPORTS the symbols of inc
 from . import patches  # noqa: F401  (the module: patches.EXPORTS the symbols of include/unet_patches.h)
 from . import coreg  # noqa: F401  (the module: coreg.EXPORTS the symbols of include/unet_coreg.h)
 from . import start  # noqa: F401  (the module: start.EXPORTS the symbols of include/unet_start.h)
+from . import warp  # noqa: F401  (the module: warp.EXPORTS the symbols of include/unet_warp.h)
 from .patches import WindowFeed, to_canvas  # noqa: F401
 
 

@@ -2922,6 +2922,132 @@ int unet_start_search(const void* subject, int sbytes, int sw, int sh, int sd, c
     return run_on_device_of(maps_out, stream, [&](hipStream_t s) { launch_start_close(info, maps_out, n, best, best_map, s); });
 }
 
+// ---- the non-linear refinement of a parcellation (include/unet_warp.h) ----
+static bool warp_g_ok(int g) { return g == 4 || g == 8 || g == 16 || g == 32; }
+static std::string warp_g_error(const std::string& w, int g) {
+    return warp_g_ok(g) ? std::string() : w + "g must be 4, 8, 16 or 32, got " + std::to_string(g);
+}
+// the levels of a fit: n_levels x {g, first_step, last_step, max_sweeps, limit}
+static std::string warp_levels_error(const std::string& w, const int* levels, int n_levels) {
+    if (n_levels < 1 || n_levels > UNET_WARP_MAX_LEVELS) return w + "n_levels must be in [1, 4], got " + std::to_string(n_levels);
+    if (!levels) return w + "null levels";
+    int rows = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const int* v = levels + 5 * l;
+        const std::string lv = w + "level " + std::to_string(l) + ": ";
+        if (!warp_g_ok(v[0])) return lv + "g must be 4, 8, 16 or 32, got " + std::to_string(v[0]);
+        if (l && 2 * v[0] != levels[5 * (l - 1)]) return lv + "g must be half the level before's, got " + std::to_string(v[0]);
+        for (int e = 1; e <= 2; ++e)
+            if (v[e] < 1 || v[e] > UNET_WARP_MAX_STEP || (v[e] & (v[e] - 1)))
+                return lv + (e == 1 ? "first_step" : "last_step") + " must be a power of two in [1, 16384], got " + std::to_string(v[e]);
+        if (v[1] < v[2]) return lv + "first_step must not be below last_step";
+        if (v[3] < 1 || v[3] > UNET_WARP_MAX_SWEEPS) return lv + "max_sweeps must be in [1, 16], got " + std::to_string(v[3]);
+        if (v[4] < 0) return lv + "limit must not be negative, got " + std::to_string(v[4]);
+        for (int s = v[1]; s >= v[2]; s >>= 1) ++rows;
+    }
+    if (rows > UNET_WARP_MAX_ROWS) return w + "levels hold " + std::to_string(rows) + " (level, step) pairs, more than 32";
+    return std::string();
+}
+static std::string warp_dims_error(const std::string& w, int sw, int sh, int sd) {
+    if (sw <= 0 || sh <= 0 || sd <= 0) return w + "subject dimensions must be positive";
+    if ((int64_t)sw * sh * sd >= ((int64_t)1 << 31)) return w + "the subject grid must stay below 2^31 voxels";
+    return std::string();
+}
+int unet_warp_lattice(int sw, int sh, int sd, int g, int* nx, int* ny, int* nz) {
+    const std::string w = "unet_warp_lattice: ";
+    if (std::string e = warp_dims_error(w, sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (!nx || !ny || !nz) return fail(w + "null output");
+    *nx = (sw + g - 1) / g + 1;
+    *ny = (sh + g - 1) / g + 1;
+    *nz = (sd + g - 1) / g + 1;
+    return 0;
+}
+int unet_warp_scratch_bytes(int sw, int sh, int sd, int n_tissues, const int* levels, int n_levels, size_t* bytes) {
+    const std::string w = "unet_warp_scratch_bytes: ";
+    if (std::string e = warp_dims_error(w, sw, sh, sd); !e.empty()) return fail(e);
+    if (n_tissues < 2 || n_tissues > UNET_WARP_MAX_TISSUES) return fail(w + "n_tissues must be in [2, 16], got " + std::to_string(n_tissues));
+    if (std::string e = warp_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
+    if (!bytes) return fail(w + "null output");
+    *bytes = warp_scratch_bytes(sw, sh, sd, levels, n_levels);
+    return 0;
+}
+int unet_warp_hist(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                   int n_tissues, const float* map, const int32_t* D, int g, uint32_t* hist, void* stream) {
+    const std::string w = "unet_warp_hist: ";
+    const std::string e = reg_grids_error("unet_warp_hist", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string pe = ptr_error(w, D, "D", 4); !pe.empty()) return fail(pe);
+    if (std::string ge = warp_g_error(w, g); !ge.empty()) return fail(ge);
+    if (std::string pe = ptr_error(w, hist, "hist", 4); !pe.empty()) return fail(pe);
+    return run_on_device_of(hist, stream, [&](hipStream_t s) {   // map is consumed inside the launcher, before this returns
+        launch_warp_hist(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, map, D, g, hist, s);
+    });
+}
+int unet_warp_sweep(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                    int n_tissues, const float* map, int32_t* D, int g, int step, int limit, int64_t* info, int impl, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+    const std::string w = "unet_warp_sweep: ";
+    const std::string e = reg_grids_error("unet_warp_sweep", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string pe = ptr_error(w, D, "D", 4); !pe.empty()) return fail(pe);
+    if (std::string ge = warp_g_error(w, g); !ge.empty()) return fail(ge);
+    if (step < 1 || step > UNET_WARP_MAX_DISP) return fail(w + "step must be in [1, 32767], got " + std::to_string(step));
+    if (limit < 0) return fail(w + "limit must not be negative, got " + std::to_string(limit));
+    if (std::string pe = ptr_error(w, info, "info", 8); !pe.empty()) return fail(pe);
+    if (impl < UNET_WARP_IMPL_DEFAULT || impl > UNET_WARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    const int level[5] = {g, 1, 1, 1, 0};
+    if (scratch_bytes < warp_scratch_bytes(sw, sh, sd, level, 1)) return fail(w + "scratch too small (see unet_warp_scratch_bytes)");
+    return run_on_device_of(D, stream, [&](hipStream_t s) {
+        launch_warp_sweep(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, map, D, g, step, limit, info, impl, scratch, s);
+    });
+}
+int unet_warp_refine(const int32_t* D_coarse, int sw, int sh, int sd, int g, int32_t* D_fine, void* stream) {
+    const std::string w = "unet_warp_refine: ";
+    if (std::string pe = ptr_error(w, D_coarse, "D_coarse", 4); !pe.empty()) return fail(pe);
+    if (std::string e = warp_dims_error(w, sw, sh, sd); !e.empty()) return fail(e);
+    if (g != 8 && g != 16 && g != 32) return fail(w + "g must be 8, 16 or 32, got " + std::to_string(g));
+    if (std::string pe = ptr_error(w, D_fine, "D_fine", 4); !pe.empty()) return fail(pe);
+    return run_on_device_of(D_fine, stream, [&](hipStream_t s) { launch_warp_refine(D_coarse, sw, sh, sd, g, D_fine, s); });
+}
+int unet_warp_fit(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                  int n_tissues, const float* map, const int* levels, int n_levels, int32_t* D_out, int64_t* report, int impl, void* scratch,
+                  size_t scratch_bytes, void* stream) {
+    const std::string w = "unet_warp_fit: ";
+    const std::string e = reg_grids_error("unet_warp_fit", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string le = warp_levels_error(w, levels, n_levels); !le.empty()) return fail(le);
+    if (std::string pe = ptr_error(w, D_out, "D_out", 4); !pe.empty()) return fail(pe);
+    if (std::string pe = ptr_error(w, report, "report", 8); !pe.empty()) return fail(pe);
+    if (impl < UNET_WARP_IMPL_DEFAULT || impl > UNET_WARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    if (scratch_bytes < warp_scratch_bytes(sw, sh, sd, levels, n_levels)) return fail(w + "scratch too small (see unet_warp_scratch_bytes)");
+    return run_on_device_of(D_out, stream, [&](hipStream_t s) {   // map and levels are consumed inside the launcher
+        launch_warp_fit(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, map, levels, n_levels, D_out, report, impl,
+                        scratch, s);
+    });
+}
+int unet_warp_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* template_, int tbytes, int tw, int th, int td,
+                    const uint16_t* atlas, int n_tissues, const float* map, const int32_t* D, int g, uint16_t* out, uint32_t* counts,
+                    void* stream) {
+    const std::string w = "unet_warp_carry: ";
+    const std::string e = reg_grids_error("unet_warp_carry", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
+    if (!e.empty()) return fail(e);
+    if (std::string pe = ptr_error(w, atlas, "atlas", 2); !pe.empty()) return fail(pe);
+    if (!map) return fail(w + "null map");
+    if (std::string pe = ptr_error(w, D, "D", 4); !pe.empty()) return fail(pe);
+    if (std::string ge = warp_g_error(w, g); !ge.empty()) return fail(ge);
+    if (std::string pe = ptr_error(w, out, "out", 2); !pe.empty()) return fail(pe);
+    if ((uintptr_t)counts & 3) return fail(w + "counts must be 4-byte aligned");
+    return run_on_device_of(out, stream, [&](hipStream_t s) {   // map is consumed inside the launcher
+        launch_warp_carry(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, atlas, n_tissues, map, D, g, out, counts, s);
+    });
+}
+
 // ---- the tables of a label map (include/unet_table.h) ----
 static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
                                       size_t scratch_bytes) {

@@ -29,6 +29,7 @@
 #include "../../include/unet_table.h"
 #include "../../include/unet_mirror.h"
 #include "../../include/unet_tiles.h"
+#include "../../include/unet_warp.h"
 
 namespace unet {
 
@@ -542,6 +543,22 @@ void launch_start_search(const void* subject, int sbytes, int sw, int sh, int sd
                          int n_tissues, const float* inits, int n, const float* step, const int* stages, int n_stages, int max_iterations,
                          float* maps_out, int64_t* trace, int64_t* info, int32_t* best, float* best_map, void* scratch, hipStream_t s);
 void launch_start_close(const int64_t* info, const float* maps_out, int n, int32_t* best, float* best_map, hipStream_t s);
+
+// kernels_warp.hip: the non-linear refinement of a parcellation (include/unet_warp.h); map and levels (n_levels x 5): host arrays,
+// read before the return.  warp_scratch_bytes: the scratch of a fit of these levels; a sweep at g uses that of the one-level list {g}
+size_t warp_scratch_bytes(int sw, int sh, int sd, const int* levels, int n_levels);
+void launch_warp_hist(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                      int n_tissues, const float* map, const int32_t* D, int g, uint32_t* hist, hipStream_t s);
+void launch_warp_sweep(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                       int n_tissues, const float* map, int32_t* D, int g, int step, int limit, int64_t* info, int impl, void* scratch,
+                       hipStream_t s);
+void launch_warp_refine(const int32_t* coarse, int sw, int sh, int sd, int g, int32_t* fine, hipStream_t s);
+void launch_warp_fit(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                     int n_tissues, const float* map, const int* levels, int n_levels, int32_t* D_out, int64_t* report, int impl,
+                     void* scratch, hipStream_t s);
+void launch_warp_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
+                       const uint16_t* atlas, int n_tissues, const float* map, const int32_t* D, int g, uint16_t* out, uint32_t* counts,
+                       hipStream_t s);
 
 // kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
 size_t table_scratch_bytes(int n_labels);

@@ -22,6 +22,7 @@
 #include "../../include/unet_register.h"
 #include "affine_search.h"
 #include "device_util.h"
+#include "tissue_carry.h"
 
 namespace unet {
 
@@ -67,13 +68,6 @@ Scratch reg_scratch(void* scratch, int T) {
     s.hist = (uint32_t*)(b + o);  o += reg_align((size_t)REG_MAXK * T * T * 4);
     s.bytes = o;
     return s;
-}
-
-// a tissue as read: uint8 or uint16 at any alignment; a value >= T reads as 0
-__device__ __forceinline__ unsigned reg_tissue(const void* __restrict__ p, int bytes, int64_t i, int T) {
-    const unsigned v = bytes == 1 ? (unsigned)((const uint8_t*)p)[i]
-                                  : (unsigned)((const uint8_t*)p)[2 * i] | ((unsigned)((const uint8_t*)p)[2 * i + 1] << 8);
-    return v >= (unsigned)T ? 0u : v;
 }
 
 // ---- joint histograms ------------------------------------------------------------------------------------------------------------
@@ -228,12 +222,6 @@ __global__ void __launch_bounds__(REG_T) k_reg_step(RegState* st, uint32_t* __re
 }
 
 // ---- carry -----------------------------------------------------------------------------------------------------------------------
-// floorf(q) as an index along an axis of `dim` voxels; below -2, above dim + 1 or NaN reads as -2: no cube voxel is inside there
-__device__ __forceinline__ int reg_index(float q, int dim) {
-    const float f = floorf(q);
-    return f >= -2.f && f <= (float)(dim + 1) ? (int)f : -2;
-}
-
 __global__ void __launch_bounds__(REG_T) k_reg_carry(const void* __restrict__ subject, int sbytes, int sw, int sh, int sd,
                                                      const void* __restrict__ tmpl, int tbytes, int tw, int th, int td,
                                                      const uint16_t* __restrict__ atlas, int T, RegMap map, uint16_t* __restrict__ out,
@@ -253,34 +241,8 @@ __global__ void __launch_bounds__(REG_T) k_reg_carry(const void* __restrict__ su
         }
         const int x = i % sw, y = (i / sw) % sh, z = i / (sw * sh);
         const AffPos p = aff_locate(lm, x, y, z, tw, th, td);
-        const int ix = reg_index(p.qx, tw), iy = reg_index(p.qy, th), iz = reg_index(p.qz, td);
-        unsigned result = 0u, kind = 2u;   // left
-        if (p.in) {
-            const int o = (iz * th + iy) * tw + ix;
-            const unsigned v = atlas[o];
-            if (v && reg_tissue(tmpl, tbytes, o, T) == a) { result = v; kind = 0u; }   // direct
-        }
-        if (kind) {
-            unsigned lab[27];
-#pragma unroll
-            for (int n = 0; n < 27; ++n) {
-                const int xx = ix + n % 3 - 1, yy = iy + (n / 3) % 3 - 1, zz = iz + n / 9 - 1;
-                const bool ok = xx >= 0 && xx < tw && yy >= 0 && yy < th && zz >= 0 && zz < td;
-                const int o = ok ? (zz * th + yy) * tw + xx : 0;
-                const unsigned v = atlas[o];
-                lab[n] = ok && v && reg_tissue(tmpl, tbytes, o, T) == a ? v : 0u;
-            }
-            // the most frequent non-zero entry, the smallest among equal counts
-            unsigned best = 0u, best_n = 0u;
-#pragma unroll
-            for (int j = 0; j < 27; ++j) {
-                unsigned n = 0u;
-#pragma unroll
-                for (int k = 0; k < 27; ++k) n += lab[k] == lab[j] ? 1u : 0u;
-                if (lab[j] && (n > best_n || (n == best_n && lab[j] < best))) { best_n = n; best = lab[j]; }
-            }
-            if (best) { result = best; kind = 1u; }   // rescued
-        }
+        unsigned result;
+        const unsigned kind = reg_carry_at(p, a, tmpl, tbytes, tw, th, td, atlas, T, result);
         out[i] = (uint16_t)result;
         if (counts) atomicAdd(&lc[kind * (unsigned)T + a], 1u);
     }

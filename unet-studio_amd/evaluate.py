@@ -56,6 +56,8 @@ when it is.  parcellate synchronises with the host twice per buffer (the map, th
 buffer's results still runs under the forward, but the host does not run ahead of this stage.  Without `atlas` nothing changes.
 `atlas_starts` (a start.Plan; None: the search from centre_init, unchanged) lets parcellate begin from image moments and ranked
 rotated starts: one more host wait per buffer, for the label's moments; the template's come from atlas.moments().
+`atlas_warp` (a warp.Plan; None: the affine map alone, unchanged) lets parcellate refine its map by a lattice field before the carry
+(DESIGN.md §34): no further host wait.
 
 With `mirror_axes` (a string of the letters x, y, z; None and "" are the paths above with no extra launch) every window is run
 under each combination of flips of those axes, K = 2^|axes| forwards on inputs flipped on the device, and the members' logits are
@@ -145,7 +147,7 @@ class EvaluateUNet:
     def __init__(self, model, device=None, postproc=None, outputs=("label",), params=None, preproc=None, orientation=None,
                  single_component=None, fov_strategy=None, tile_overlap=0.25, atlas=None, atlas_options=None, morphology=None,
                  single_component_connectivity=6, mirror_axes=None, mirror_swap=None, ensemble=None, ensemble_weights=None,
-                 atlas_starts=None):
+                 atlas_starts=None, atlas_warp=None):
         self.model = model
         self.ensemble = ensemble               # a list of further models (self.model is member 0), None: one model
         self.ensemble_weights = ensemble_weights   # one positive weight per member, member 0 first; None: equal
@@ -159,6 +161,7 @@ class EvaluateUNet:
         self.atlas = atlas                     # a register.Atlas: the outputs "atlas" and "regions" become available
         self.atlas_options = atlas_options     # register.parcellate's keywords (init, step, stages, max_iterations, ...)
         self.atlas_starts = atlas_starts       # a start.Plan: parcellate searches from ranked starts; None: centre_init
+        self.atlas_warp = atlas_warp           # a warp.Plan: parcellate refines the map by a lattice field; None: affine
         self.morphology = morphology           # a list of morph.run's ops on the label output, None / []: none
         self.mirror_axes = mirror_axes         # letters of the model grid's axes to mirror over, None / "": no mirroring
         self.mirror_swap = mirror_swap         # (axis letter, [(a, b), ...]): channel pairs exchanged under a flip of that axis
@@ -470,6 +473,8 @@ class EvaluateUNet:
         opts = dict(self.atlas_options or {})
         if self.atlas_starts is not None:
             opts.update(starts=self.atlas_starts, template_moments=atl.moments())
+        if self.atlas_warp is not None:
+            opts.update(warp=self.atlas_warp)
         parc, report = REG.parcellate(label, vs, atl.template, atl.template_vs, atl.regions, atl.n_tissues, **opts)
         if "atlas" in cfg.staged:
             results["atlas"] = parc

@@ -6,8 +6,9 @@ regions on the subject's own grid.
                up to 25 candidates from one pass, the host enqueues the launches and reads nothing back
   carry        the atlas brought onto the subject grid through a map: the nearest template voxel when its tissue agrees, else the
                mode of the agreeing voxels of the 3x3x3 cube around it
-  parcellate   search from centre_init (or, with `starts`, the best of several searches from ranked starts: start.find), carry,
-               then atlas.grow on the subject grid for what carry left
+  parcellate   search from centre_init (or, with `starts`, the best of several searches from ranked starts: start.find), carry
+               (with `warp`, through the lattice field warp.fit finds after the search), then atlas.grow on the subject grid for
+               what carry left
 
 In place of the reference's linear_cuda (evaluate.cpp:19-26, TIPL's affine registration; TIPL is not in the reference tree, so
 these are this project's definitions and parity is NOT pinned).  Every choice is made on integer counts: the results are pinned to
@@ -197,7 +198,7 @@ class Atlas:
 
 
 def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissues=5, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES,
-               max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT, starts=None, template_moments=None):
+               max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT, starts=None, template_moments=None, warp=None):
     """The atlas's regions on the subject's grid.  subject_tissue: the subject's tissue map (an evaluation's label output), template:
     the template's, atlas: the corrected atlas on the template grid (atlas.prepare_atlas); (D, H, W) device tensors, voxel sizes
     (x, y, z).  search from `init` (centre_init when None), carry, then atlas.grow on the subject grid with the subject tissue as
@@ -206,6 +207,10 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
     starts: a start.Plan(degrees, n, rank_stride) replaces the single search with start.find (the best of n searches from starts
     ranked among the moments-and-rotations candidates; `init`, when given, is only the fallback for moments that say nothing);
     template_moments: the template's start.moments when the caller has them (Atlas.moments()).  None: the single search, unchanged.
+
+    warp: a warp.Plan(levels, limit) refines the map non-linearly: warp.fit runs after the search on the map read
+    back at synchronisation 1, and warp.carry takes carry's place.  The report gains warp = dict(levels int32 {n, 5}, report (the
+    rows of the schedule), score_affine, score_warped, max_disp_q8).  None: today's calls, unchanged.
 
     Returns (regions uint16 on the subject grid, report) with report = dict(map (m[9], t[3]) float32, iterations, converged, score,
     direct, rescued, left, filled (uint32 {n_tissues} each), rounds, grow_converged); with `starts` also starts = start.report's
@@ -216,6 +221,9 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
     reports, read back once at the end."""
     from . import atlas as A
     T = int(n_tissues)
+    if warp is not None:
+        from . import warp as W
+        warp_levels, warp_limit = W._plan(warp, "register.parcellate")
     if init is None:
         if not (torch.is_tensor(subject_tissue) and torch.is_tensor(template)):
             raise UNetError("register.parcellate: subject_tissue and template must be device tensors")
@@ -230,7 +238,13 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
         map_dev, _, info = search(subject_tissue, template, T, init, step=step, stages=stages, max_iterations=max_iterations, impl=impl,
                                   trace=False)
     m = map_dev.cpu().numpy()                                         # host synchronisation 1
-    regions, counts = carry(subject_tissue, template, atlas, T, m)
+    if warp is None:
+        regions, counts = carry(subject_tissue, template, atlas, T, m)
+    else:
+        levels = W.levels_of(warp_levels, warp_limit, m, "register.parcellate")
+        field, rows = W.fit(subject_tissue, template, T, m, levels=levels)
+        regions, counts = W.carry(subject_tissue, template, atlas, T, m, field, int(levels[-1, 0]))
+        affine_hist, max_disp = joint_hist(subject_tissue, template, T, [m]), field.abs().amax()
     g = A.grow(subject_tissue, regions, T, list(range(1, T)), flags=A.CLAMP | A.PRESERVE, max_rounds=max_rounds, smooth_rounds=smooth_rounds)
 
     def u32(t):
@@ -248,4 +262,9 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
                   grow_converged=bool(ginfo[1]))
     if found is not None:
         report["starts"] = found
+    if warp is not None:
+        rows_h = rows.cpu().numpy()
+        rows_h = rows_h[rows_h[:, 0] >= 0]
+        report["warp"] = dict(levels=levels, report=rows_h, score_affine=W.score(u32(affine_hist)[0]), score_warped=int(rows_h[-1, 4]),
+                              max_disp_q8=int(max_disp.cpu()))
     return regions, report
