@@ -41,6 +41,7 @@ from . import patches  # noqa: F401  (the module: patches.EXPORTS the symbols of
 from . import coreg  # noqa: F401  (the module: coreg.EXPORTS the symbols of include/unet_coreg.h)
 from . import start  # noqa: F401  (the module: start.EXPORTS the symbols of include/unet_start.h)
 from . import warp  # noqa: F401  (the module: warp.EXPORTS the symbols of include/unet_warp.h)
+from . import cowarp  # noqa: F401  (the module: cowarp.EXPORTS the symbols of include/unet_cowarp.h)
 from .patches import WindowFeed, to_canvas  # noqa: F401
 
 

@@ -8,7 +8,8 @@ T2 / FLAIR beside a T1, an FA or SUV map beside the scan) on the scan's grid, fo
   search        the centred pattern search of `register` over the 12 parameters of an affine map, entirely on the device: every
                 iteration scores its up to 25 candidates from one pass, the host enqueues the launches and reads nothing back
   robust_range  the (lo, hi) two quantiles of an image span (the only host read of an alignment)
-  align         range, codes, search from register.centre_init, and the moving image resampled onto the fixed grid
+  align         range, codes, search from register.centre_init, and the moving image resampled onto the fixed grid; with `warp`, a
+                lattice field fitted after the search (cowarp.fit) and the image resampled through map + field
 
 In place of the reference's linear_cuda (evaluate.cpp:19-26, TIPL's affine registration; TIPL is not in the reference tree, so
 these are this project's definitions and parity is NOT pinned).  Every choice is made on integers, the score included: the results
@@ -175,7 +176,7 @@ def robust_range(image, permille=(10, 990)):
 
 
 def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES, max_iterations=400,
-          impl=IMPL_DEFAULT, starts=None):
+          impl=IMPL_DEFAULT, starts=None, warp=None):
     """The moving image on the fixed image's grid.  moving, fixed: (D, H, W) float32 device tensors of one subject, voxel sizes
     (x, y, z).  In order: robust_range and code of both images; the start, register.centre_init(fixed.shape, fixed_vs, moving.shape,
     moving_vs) unless `init` (a map, fixed voxel -> moving position) is given; search; the moving image resampled through the map
@@ -186,9 +187,19 @@ def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_S
     best (the unrotated one always among them) are read back once, n searches run one after another on the stream, and the best
     final state by start.best_of's key is taken from one readback of the n infos.  None: the single search, unchanged.
 
+    warp: a cowarp.Plan(levels, limit, impl) refines the map non-linearly: after the search and the readback of the
+    map, cowarp.fit runs on the two code images and cowarp.resample takes space.resample's place.  A fourth element is returned,
+    dict(field int32 {nz, ny, nx, 3} on the last level's lattice, g its spacing, report int64 {cowarp.MAX_ROWS, 5}, score_affine
+    and score_warped int64 {1} (N * MI before and after), max_disp_q8 int32 {}), all device tensors, not read here.  None: the
+    3-tuple, from the same calls as before the keyword existed.
+
     Returns (map float32 {12} on the device, info int64 {4} on the device = (iterations, converged, score, stage of the last
     iteration), moved float32 of fixed's shape).  The host reads the two ranges before the search and the 12 floats of the map
     after it (the resampling takes its map in the launch arguments)."""
+    if warp is not None:
+        from . import cowarp as CW
+        from . import warp as W
+        warp_levels, warp_limit, warp_impl = CW._plan(warp, "coreg.align")
     _image(fixed, "fixed", "align")
     _image(moving, "moving", "align", fixed.device)
     b = _bins(bins, "align")
@@ -214,5 +225,15 @@ def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_S
         best = STA.best_of(torch.stack([r[2] for r in runs]).cpu().numpy())
         map_dev, info = runs[best][0], runs[best][2]
     m = map_dev.cpu().numpy()
-    moved = SP.resample(moving, tuple(fixed.shape), (m[:9], m[9:]), mode="linear")
-    return map_dev, info, moved
+    if warp is None:
+        moved = SP.resample(moving, tuple(fixed.shape), (m[:9], m[9:]), mode="linear")
+        return map_dev, info, moved
+    levels = W.levels_of(warp_levels, warp_limit, m, "coreg.align")
+    g0, g = int(levels[0, 0]), int(levels[-1, 0])
+    zero = torch.zeros(W.lattice(tuple(fixed.shape), g0) + (3,), dtype=torch.int32, device=fixed.device)
+    score_affine = scores(CW.hist(fc, mc, b, m, zero, g0).view(1, b, b + 1))
+    field, report = CW.fit(fc, mc, b, m, levels=levels, impl=warp_impl)
+    score_warped = scores(CW.hist(fc, mc, b, m, field, g).view(1, b, b + 1))
+    moved = CW.resample(moving, tuple(fixed.shape), m, field, g)
+    return map_dev, info, moved, dict(field=field, g=g, report=report, score_affine=score_affine, score_warped=score_warped,
+                                      max_disp_q8=field.abs().max())

@@ -3048,6 +3048,98 @@ int unet_warp_carry(const void* subject, int sbytes, int sw, int sh, int sd, con
     });
 }
 
+// ---- the non-linear refinement of a co-registration (include/unet_cowarp.h) ----
+static std::string cowarp_g_error(const std::string& w, int g) {
+    return g == 4 || g == 8 || g == 16 ? std::string() : w + "g must be 4, 8 or 16, got " + std::to_string(g);
+}
+// the levels of a fit: unet_warp.h's rows, without g = 32
+static std::string cowarp_levels_error(const std::string& w, const int* levels, int n_levels) {
+    if (n_levels < 1 || n_levels > UNET_COWARP_MAX_LEVELS) return w + "n_levels must be in [1, 3], got " + std::to_string(n_levels);
+    if (!levels) return w + "null levels";
+    for (int l = 0; l < n_levels; ++l)
+        if (std::string e = cowarp_g_error(w + "level " + std::to_string(l) + ": ", levels[5 * l]); !e.empty()) return e;
+    return warp_levels_error(w, levels, n_levels);
+}
+static_assert(UNET_COWARP_MAX_STEP == UNET_WARP_MAX_STEP && UNET_COWARP_MAX_SWEEPS == UNET_WARP_MAX_SWEEPS &&
+              UNET_COWARP_MAX_ROWS == UNET_WARP_MAX_ROWS && UNET_COWARP_MAX_DISP == UNET_WARP_MAX_DISP, "one schedule for both warps");
+int unet_cowarp_scratch_bytes(int fw, int fh, int fd, int bins, const int* levels, int n_levels, size_t* bytes) {
+    const std::string w = "unet_cowarp_scratch_bytes: ";
+    if (fw <= 0 || fh <= 0 || fd <= 0) return fail(w + "fixed dimensions must be positive");
+    if ((int64_t)fw * fh * fd >= ((int64_t)1 << 31)) return fail(w + "the fixed grid must stay below 2^31 voxels");
+    if (!coreg_bins_ok(bins)) return fail(w + "bins must be 8, 16 or 32, got " + std::to_string(bins));
+    if (std::string e = cowarp_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
+    if (!bytes) return fail(w + "null output");
+    *bytes = cowarp_scratch_bytes(fw, fh, fd, levels, n_levels);
+    return 0;
+}
+int unet_cowarp_hist(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins, const float* map,
+                     const int32_t* D, int g, uint32_t* hist, void* stream) {
+    const std::string w = "unet_cowarp_hist: ";
+    if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
+    if (std::string e = cowarp_g_error(w, g); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, hist, "hist", 4); !e.empty()) return fail(e);
+    return run_on_device_of(hist, stream, [&](hipStream_t s) {   // map is consumed inside the launcher, before this returns
+        launch_cowarp_hist(fixed, fw, fh, fd, moving, mw, mh, md, bins, map, D, g, hist, s);
+    });
+}
+int unet_cowarp_weights(const uint32_t* hist, int bins, int16_t* weights, void* stream) {
+    const std::string w = "unet_cowarp_weights: ";
+    if (std::string e = ptr_error(w, hist, "hist", 4); !e.empty()) return fail(e);
+    if (!coreg_bins_ok(bins)) return fail(w + "bins must be 8, 16 or 32, got " + std::to_string(bins));
+    if (std::string e = ptr_error(w, weights, "weights", 2); !e.empty()) return fail(e);
+    return run_on_device_of(weights, stream, [&](hipStream_t s) { launch_cowarp_weights(hist, bins, weights, s); });
+}
+int unet_cowarp_sweep(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins, const float* map,
+                      int32_t* D, int g, int step, int limit, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
+    const std::string w = "unet_cowarp_sweep: ";
+    if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
+    if (std::string e = cowarp_g_error(w, g); !e.empty()) return fail(e);
+    if (step < 1 || step > UNET_COWARP_MAX_DISP) return fail(w + "step must be in [1, 32767], got " + std::to_string(step));
+    if (limit < 0) return fail(w + "limit must not be negative, got " + std::to_string(limit));
+    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return fail(e);
+    if (impl < UNET_COWARP_IMPL_DEFAULT || impl > UNET_COWARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    const int level[5] = {g, 1, 1, 1, 0};
+    if (scratch_bytes < cowarp_scratch_bytes(fw, fh, fd, level, 1)) return fail(w + "scratch too small (see unet_cowarp_scratch_bytes)");
+    return run_on_device_of(D, stream, [&](hipStream_t s) {
+        launch_cowarp_sweep(fixed, fw, fh, fd, moving, mw, mh, md, bins, map, D, g, step, limit, info, impl, scratch, s);
+    });
+}
+int unet_cowarp_fit(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins, const float* map,
+                    const int* levels, int n_levels, int32_t* D_out, int64_t* report, int impl, void* scratch, size_t scratch_bytes,
+                    void* stream) {
+    const std::string w = "unet_cowarp_fit: ";
+    if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string e = cowarp_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, D_out, "D_out", 4); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, report, "report", 8); !e.empty()) return fail(e);
+    if (impl < UNET_COWARP_IMPL_DEFAULT || impl > UNET_COWARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    if (scratch_bytes < cowarp_scratch_bytes(fw, fh, fd, levels, n_levels)) return fail(w + "scratch too small (see unet_cowarp_scratch_bytes)");
+    return run_on_device_of(D_out, stream, [&](hipStream_t s) {   // map and levels are consumed inside the launcher
+        launch_cowarp_fit(fixed, fw, fh, fd, moving, mw, mh, md, bins, map, levels, n_levels, D_out, report, impl, scratch, s);
+    });
+}
+int unet_cowarp_resample(const float* moving, int mw, int mh, int md, int fw, int fh, int fd, const float* map, const int32_t* D, int g,
+                         float* out, void* stream) {
+    const std::string w = "unet_cowarp_resample: ";
+    if (std::string e = ptr_error(w, moving, "moving", 4); !e.empty()) return fail(e);
+    if (mw <= 0 || mh <= 0 || md <= 0) return fail(w + "moving dimensions must be positive");
+    if (fw <= 0 || fh <= 0 || fd <= 0) return fail(w + "fixed dimensions must be positive");
+    if ((int64_t)mw * mh * md >= ((int64_t)1 << 31)) return fail(w + "the moving grid must stay below 2^31 voxels");
+    if ((int64_t)fw * fh * fd >= ((int64_t)1 << 31)) return fail(w + "the fixed grid must stay below 2^31 voxels");
+    if (!map) return fail(w + "null map");
+    if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
+    if (std::string e = cowarp_g_error(w, g); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, out, "out", 4); !e.empty()) return fail(e);
+    return run_on_device_of(out, stream, [&](hipStream_t s) { launch_cowarp_resample(moving, mw, mh, md, fw, fh, fd, map, D, g, out, s); });
+}
+
 // ---- the tables of a label map (include/unet_table.h) ----
 static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
                                       size_t scratch_bytes) {

@@ -12,6 +12,7 @@
 #include "../../include/unet_components.h"
 #include "../../include/unet_connectivity.h"
 #include "../../include/unet_coreg.h"
+#include "../../include/unet_cowarp.h"
 #include "../../include/unet_distance.h"
 #include "../../include/unet_ensemble.h"
 #include "../../include/unet_feed.h"
@@ -559,6 +560,21 @@ void launch_warp_fit(const void* subject, int sbytes, int sw, int sh, int sd, co
 void launch_warp_carry(const void* subject, int sbytes, int sw, int sh, int sd, const void* tmpl, int tbytes, int tw, int th, int td,
                        const uint16_t* atlas, int n_tissues, const float* map, const int32_t* D, int g, uint16_t* out, uint32_t* counts,
                        hipStream_t s);
+
+// kernels_cowarp.hip: the non-linear refinement of a co-registration (include/unet_cowarp.h); fixed and moving are codes; map and
+// levels (n_levels x 5): host arrays, read before the return.  cowarp_scratch_bytes: the scratch of a fit of these levels; a sweep at
+// g uses that of the one-level list {g}.  A fit refines with launch_warp_refine
+size_t cowarp_scratch_bytes(int fw, int fh, int fd, const int* levels, int n_levels);
+void launch_cowarp_hist(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                        const float* map, const int32_t* D, int g, uint32_t* hist, hipStream_t s);
+void launch_cowarp_weights(const uint32_t* hist, int bins, int16_t* weights, hipStream_t s);
+void launch_cowarp_sweep(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                         const float* map, int32_t* D, int g, int step, int limit, int64_t* info, int impl, void* scratch, hipStream_t s);
+void launch_cowarp_fit(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t* moving, int mw, int mh, int md, int bins,
+                       const float* map, const int* levels, int n_levels, int32_t* D_out, int64_t* report, int impl, void* scratch,
+                       hipStream_t s);
+void launch_cowarp_resample(const float* moving, int mw, int mh, int md, int fw, int fh, int fd, const float* map, const int32_t* D, int g,
+                            float* out, hipStream_t s);
 
 // kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
 size_t table_scratch_bytes(int n_labels);

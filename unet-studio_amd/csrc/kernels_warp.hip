@@ -17,7 +17,8 @@
 //   k_warp_carry   one thread per subject voxel: kernels_register.hip's carry at the warped position (tissue_carry.h)
 // Every atomic is an integer add: the results do not depend on the schedule.  Positions are computed per voxel from its integer
 // coordinates with contraction off.  In a fit every sweep's kernels return at once when `prev`, the count of nodes the preceding
-// sweep of the same (level, step) changed, is zero (stream order makes it final): the host reads nothing back.
+// sweep of the same (level, step) changed, is zero (stream order makes it final): the host reads nothing back.  The lattice, the
+// positions, a node's support, admissibility and choice are the one copy of lattice_field.h, shared with kernels_cowarp.hip.
 //
 // Scratch, each part 256-B aligned: the sweeps' {changed, visited} slots, a histogram, the counters of IMPL_VOXEL (7 per node of the
 // finest lattice), the fields of all levels but the last.
@@ -27,6 +28,7 @@
 #include "../../include/unet_warp.h"
 #include "affine_search.h"
 #include "device_util.h"
+#include "lattice_field.h"
 #include "tissue_carry.h"
 
 namespace unet {
@@ -38,28 +40,7 @@ constexpr int WARP_MAXB = 8192;              // their grid cap; they stride over
 constexpr int WARP_MAXT = UNET_WARP_MAX_TISSUES;
 constexpr int WARP_SLOTS = UNET_WARP_MAX_ROWS * UNET_WARP_MAX_SWEEPS;
 typedef unsigned long long u64;
-
-struct WarpMap {
-    float v[12];
-};
-struct WarpLat {   // a lattice over the subject grid
-    int nx, ny, nz, g, lg;
-    float scale;   // 2^-(8 + 3 lg)
-};
-
-int warp_log2(int g) { return g == 4 ? 2 : g == 8 ? 3 : g == 16 ? 4 : 5; }
-WarpLat warp_lattice(int sw, int sh, int sd, int g) {
-    WarpLat L;
-    L.g = g;
-    L.lg = warp_log2(g);
-    L.nx = (sw + g - 1) / g + 1;
-    L.ny = (sh + g - 1) / g + 1;
-    L.nz = (sd + g - 1) / g + 1;
-    L.scale = ldexpf(1.f, -(8 + 3 * L.lg));
-    return L;
-}
-size_t warp_nodes(const WarpLat& L) { return (size_t)L.nx * L.ny * L.nz; }
-size_t warp_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static_assert(WARP_MAX_DISP == UNET_WARP_MAX_DISP, "lattice_field.h's range is this header's");
 
 struct Scratch {
     u64* slots;        // WARP_SLOTS x {changed, visited}
@@ -83,111 +64,14 @@ Scratch warp_scratch(void* scratch, int sw, int sh, int sd, const int* levels, i
     return s;
 }
 
-// n_r of voxel (x, y, z): the cell's 8 corners weighted; a corner of weight 0 is not read
-__device__ __forceinline__ void warp_corners(const int32_t* __restrict__ D, const WarpLat& L, int x, int y, int z, int& n0, int& n1, int& n2) {
-    const int g = L.g, m = g - 1, cx = x >> L.lg, cy = y >> L.lg, cz = z >> L.lg, fx = x & m, fy = y & m, fz = z & m;
-    n0 = n1 = n2 = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int w = ((c & 1) ? fx : g - fx) * ((c & 2) ? fy : g - fy) * ((c & 4) ? fz : g - fz);
-        if (w) {
-            const int32_t* d = D + (((size_t)(cz + (c >> 2)) * L.ny + (cy + ((c >> 1) & 1))) * L.nx + (cx + (c & 1))) * 3;
-            n0 += w * d[0];
-            n1 += w * d[1];
-            n2 += w * d[2];
-        }
-    }
-}
-
-// the affine position of a voxel, before the displacement and the half: fp32, left to right, no fused multiply-add
-__device__ __forceinline__ void warp_affine(const float* m, int xi, int yi, int zi, float& px, float& py, float& pz) {
-#pragma clang fp contract(off)
-    const float x = (float)xi, y = (float)yi, z = (float)zi;
-    px = ((m[0] * x + m[1] * y) + m[2] * z) + m[9];
-    py = ((m[3] * x + m[4] * y) + m[5] * z) + m[10];
-    pz = ((m[6] * x + m[7] * y) + m[8] * z) + m[11];
-}
-// q = (p + n * 2^-(8 + 3 lg)) + 0.5 along one axis; the scaling by a power of two is exact
-__device__ __forceinline__ float warp_q(float p, int n, float scale) {
-#pragma clang fp contract(off)
-    const float d = (float)n * scale;
-    const float w = p + d;
-    return w + 0.5f;
-}
-__device__ __forceinline__ AffPos warp_pos(float qx, float qy, float qz, int tw, int th, int td) {
-    AffPos p;
-    p.qx = qx; p.qy = qy; p.qz = qz;
-    p.in = qx >= 0.f && qy >= 0.f && qz >= 0.f && qx < (float)tw && qy < (float)th && qz < (float)td;
-    return p;
-}
-__device__ __forceinline__ AffPos warp_locate(const float* m, const int32_t* __restrict__ D, const WarpLat& L, int x, int y, int z, int tw, int th,
-                                              int td) {
-    float px, py, pz;
-    int n0, n1, n2;
-    warp_affine(m, x, y, z, px, py, pz);
-    warp_corners(D, L, x, y, z, n0, n1, n2);
-    return warp_pos(warp_q(px, n0, L.scale), warp_q(py, n1, L.scale), warp_q(pz, n2, L.scale), tw, th, td);
-}
-// the template index of a position, -1 outside
-__device__ __forceinline__ int warp_offset(float qx, float qy, float qz, int tw, int th, int td) {
-    const AffPos p = warp_pos(qx, qy, qz, tw, th, td);
-    return p.in ? ((int)floorf(qz) * th + (int)floorf(qy)) * tw + (int)floorf(qx) : -1;
-}
 // what a voxel of subject tissue a adds to agree - disagree when its template sample reads b
 __device__ __forceinline__ int warp_vote(unsigned a, unsigned b) { return a == b ? (a ? 1 : 0) : -1; }
 
-// The seven votes of one voxel: p its affine position, n its corner sums with the node unmoved, wc * step what one step of the node
-// adds to a sum.  mask: bit c set = candidate c wanted (bit 0 always); the others give 0
-struct WarpVotes {
-    int v[7];
-};
+// The seven votes of one voxel of subject tissue a (lattice_field.h's warp_seven): an outside sample reads tissue 0
 __device__ __forceinline__ WarpVotes warp_votes(unsigned a, float px, float py, float pz, int n0, int n1, int n2, int ws, float scale,
                                                 const void* __restrict__ tmpl, int tbytes, int tw, int th, int td, int T, unsigned mask) {
-    const float q0 = warp_q(px, n0, scale), q1 = warp_q(py, n1, scale), q2 = warp_q(pz, n2, scale);
-    const int ob = warp_offset(q0, q1, q2, tw, th, td);
-    const unsigned bb = ob < 0 ? 0u : reg_tissue(tmpl, tbytes, ob, T);
-    WarpVotes r;
-    r.v[0] = warp_vote(a, bb);
-    auto moved = [&](int c, float qx, float qy, float qz) {
-        if (!((mask >> c) & 1u)) return 0;
-        const int o = warp_offset(qx, qy, qz, tw, th, td);
-        return warp_vote(a, o == ob ? bb : o < 0 ? 0u : reg_tissue(tmpl, tbytes, o, T));
-    };
-    r.v[1] = moved(1, warp_q(px, n0 + ws, scale), q1, q2);
-    r.v[2] = moved(2, warp_q(px, n0 - ws, scale), q1, q2);
-    r.v[3] = moved(3, q0, warp_q(py, n1 + ws, scale), q2);
-    r.v[4] = moved(4, q0, warp_q(py, n1 - ws, scale), q2);
-    r.v[5] = moved(5, q0, q1, warp_q(pz, n2 + ws, scale));
-    r.v[6] = moved(6, q0, q1, warp_q(pz, n2 - ws, scale));
-    return r;
-}
-
-// Is moved candidate c (1..6) of a node at (d0, d1, d2) admissible?  nb(n, v0, v1, v2) -> whether lattice neighbour n (-x, +x, -y,
-// +y, -z, +z) exists, and its field
-template <typename Nb> __device__ __forceinline__ bool warp_admissible(int d0, int d1, int d2, int c, int step, int limit, Nb nb) {
-    const int axis = (c - 1) >> 1, delta = (c & 1) ? step : -step;
-    const int c0 = d0 + (axis == 0 ? delta : 0), c1 = d1 + (axis == 1 ? delta : 0), c2 = d2 + (axis == 2 ? delta : 0);
-    const int moved = axis == 0 ? c0 : axis == 1 ? c1 : c2;
-    bool ok = moved <= UNET_WARP_MAX_DISP && moved >= -UNET_WARP_MAX_DISP;
-#pragma unroll
-    for (int n = 0; n < 6; ++n) {
-        int v0, v1, v2;
-        if (nb(n, v0, v1, v2)) ok = ok && abs(c0 - v0) <= limit && abs(c1 - v1) <= limit && abs(c2 - v2) <= limit;
-    }
-    return ok;
-}
-// the winner of seven local scores under a mask of admissible candidates: the best, the lowest index among equals
-__device__ __forceinline__ int warp_best(const int* score, unsigned mask) {
-    int best = 0, top = score[0];
-#pragma unroll
-    for (int c = 1; c < 7; ++c)
-        if (((mask >> c) & 1u) && score[c] > top) { best = c; top = score[c]; }
-    return best;
-}
-// the support of a node along one axis of `dim` voxels: [lo, hi], empty when lo > hi
-__device__ __forceinline__ void warp_support(int i, int g, int dim, int& lo, int& hi) {
-    lo = max(0, (i - 1) * g + 1);
-    hi = min(dim - 1, (i + 1) * g - 1);
+    return warp_seven(px, py, pz, n0, n1, n2, ws, scale, tw, th, td, mask,
+                      [&](int o) { return o < 0 ? 0u : reg_tissue(tmpl, tbytes, o, T); }, [&](unsigned b) { return warp_vote(a, b); });
 }
 
 // ---- the joint histogram ---------------------------------------------------------------------------------------------------------
@@ -232,43 +116,19 @@ __global__ void __launch_bounds__(NT) k_warp_node(const void* __restrict__ subje
     warp_support(k, L.g, sd, z0, z1);
     if (x0 > x1 || y0 > y1 || z0 > z1) return;   // uniform: an empty support, the node stays
     const int tid = threadIdx.x;
-    for (int e = tid; e < 81; e += NT) {
-        const int nb = e / 3, ii = i + nb % 3 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb / 9 - 1;
-        const bool ok = ii >= 0 && ii < L.nx && jj >= 0 && jj < L.ny && kk >= 0 && kk < L.nz;
-        ld[e] = ok ? D[(((size_t)kk * L.ny + jj) * L.nx + ii) * 3 + e % 3] : 0;
-    }
+    warp_stage<NT>(D, L, i, j, k, ld);
     if (tid < 12) lm[tid] = map.v[tid];
     if (tid == 0) ladm = 1u;
     __syncthreads();
-    if (tid < 6) {
-        auto nb = [&](int n, int& v0, int& v1, int& v2) {
-            const int a = n >> 1, s = (n & 1) ? 1 : -1, ii = i + (a == 0 ? s : 0), jj = j + (a == 1 ? s : 0), kk = k + (a == 2 ? s : 0);
-            const int* v = ld + (((kk - k + 1) * 3 + (jj - j + 1)) * 3 + (ii - i + 1)) * 3;
-            v0 = v[0]; v1 = v[1]; v2 = v[2];
-            return ii >= 0 && ii < L.nx && jj >= 0 && jj < L.ny && kk >= 0 && kk < L.nz;
-        };
-        if (warp_admissible(ld[39], ld[40], ld[41], tid + 1, step, limit, nb)) atomicOr(&ladm, 2u << tid);
-    }
+    if (tid < 6 && warp_staged_admissible(ld, L, i, j, k, tid + 1, step, limit)) atomicOr(&ladm, 2u << tid);
     __syncthreads();
     const unsigned mask = ladm;
     const int g = L.g, ex = x1 - x0 + 1, ey = y1 - y0 + 1, n = ex * ey * (z1 - z0 + 1);
     int acc[7] = {0, 0, 0, 0, 0, 0, 0};
     for (int v = tid; v < n; v += NT) {
         const int x = x0 + v % ex, y = y0 + (v / ex) % ey, z = z0 + v / (ex * ey);
-        const int dx = x - i * g, dy = y - j * g, dz = z - k * g;
-        // the voxel's cell inside the neighbourhood: its lower corner is the node itself (1) or the one before it (0)
-        const int bx = dx >= 0 ? 1 : 0, by = dy >= 0 ? 1 : 0, bz = dz >= 0 ? 1 : 0;
-        const int fx = dx >= 0 ? dx : g + dx, fy = dy >= 0 ? dy : g + dy, fz = dz >= 0 ? dz : g + dz;
-        int n0 = 0, n1 = 0, n2 = 0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int w = ((c & 1) ? fx : g - fx) * ((c & 2) ? fy : g - fy) * ((c & 4) ? fz : g - fz);
-            const int* d = ld + (((bz + (c >> 2)) * 3 + (by + ((c >> 1) & 1))) * 3 + (bx + (c & 1))) * 3;
-            n0 += w * d[0];
-            n1 += w * d[1];
-            n2 += w * d[2];
-        }
-        const int ws = (g - abs(dx)) * (g - abs(dy)) * (g - abs(dz)) * step;   // <= g^3 * 32767
+        int n0, n1, n2;
+        const int ws = warp_staged_corners(ld, g, x, y, z, i, j, k, n0, n1, n2) * step;   // <= g^3 * 32767
         const unsigned a = reg_tissue(subject, sbytes, ((int64_t)z * sh + y) * sw + x, T);
         float px, py, pz;
         warp_affine(lm, x, y, z, px, py, pz);
@@ -302,13 +162,6 @@ __global__ void __launch_bounds__(NT) k_warp_node(const void* __restrict__ subje
 }
 
 // ---- a colour pass, a thread per voxel -------------------------------------------------------------------------------------------
-// the node of parity `par` whose support holds coordinate x, -1 for none
-__device__ __forceinline__ int warp_owner(int x, int lg, int g, int par) {
-    const int cell = x >> lg;
-    if ((x & (g - 1)) == 0) return (cell & 1) == par ? cell : -1;
-    return (cell & 1) == par ? cell : cell + 1;
-}
-
 __global__ void __launch_bounds__(WARP_T) k_warp_vox(const void* __restrict__ subject, int sbytes, int sw, int sh, int sd,
                                                      const void* __restrict__ tmpl, int tbytes, int tw, int th, int td, int T, WarpMap map,
                                                      const int32_t* __restrict__ D, WarpLat L, int colour, int step, int* __restrict__ cnt,
@@ -353,23 +206,12 @@ __global__ void __launch_bounds__(WARP_T) k_warp_pick(int sw, int sh, int sd, in
         const size_t node = ((size_t)k * L.ny + j) * L.nx + i;
         int32_t* d = D + node * 3;
         const int d0 = d[0], d1 = d[1], d2 = d[2];
-        auto nb = [&](int n, int& v0, int& v1, int& v2) {
-            const int a = n >> 1, s = (n & 1) ? 1 : -1, ii = i + (a == 0 ? s : 0), jj = j + (a == 1 ? s : 0), kk = k + (a == 2 ? s : 0);
-            const bool ok = ii >= 0 && ii < L.nx && jj >= 0 && jj < L.ny && kk >= 0 && kk < L.nz;
-            v0 = v1 = v2 = 0;
-            if (ok) {
-                const int32_t* v = D + (((size_t)kk * L.ny + jj) * L.nx + ii) * 3;   // another colour: not written in this pass
-                v0 = v[0]; v1 = v[1]; v2 = v[2];
-            }
-            return ok;
-        };
-        unsigned mask = 1u;
+        const unsigned mask = warp_pick_mask(D, L, i, j, k, d0, d1, d2, step, limit);
         int score[7];
 #pragma unroll
         for (int c = 0; c < 7; ++c) {
             score[c] = cnt[node * 7 + c];
             cnt[node * 7 + c] = 0;
-            if (c && warp_admissible(d0, d1, d2, c, step, limit, nb)) mask |= 1u << c;
         }
         const int best = warp_best(score, mask);
         if (best) {
@@ -459,12 +301,6 @@ int warp_blocks(int64_t items) {
     const int64_t nb = (items + WARP_T - 1) / WARP_T;
     return (int)(nb > WARP_MAXB ? WARP_MAXB : nb < 1 ? 1 : nb);
 }
-WarpMap warp_map(const float* map) {
-    WarpMap m;
-    for (int e = 0; e < 12; ++e) m.v[e] = map[e];
-    return m;
-}
-
 struct Grids {   // what every kernel over the two tissue maps takes
     const void* subject; int sbytes, sw, sh, sd;
     const void* tmpl;    int tbytes, tw, th, td;
