@@ -42,6 +42,7 @@ from . import coreg  # noqa: F401  (the module: coreg.EXPORTS the symbols of inc
 from . import start  # noqa: F401  (the module: start.EXPORTS the symbols of include/unet_start.h)
 from . import warp  # noqa: F401  (the module: warp.EXPORTS the symbols of include/unet_warp.h)
 from . import cowarp  # noqa: F401  (the module: cowarp.EXPORTS the symbols of include/unet_cowarp.h)
+from . import deform  # noqa: F401  (the module: deform.EXPORTS the symbols of include/unet_deform.h)
 from .patches import WindowFeed, to_canvas  # noqa: F401
 
 

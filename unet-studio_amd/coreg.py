@@ -176,7 +176,7 @@ def robust_range(image, permille=(10, 990)):
 
 
 def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES, max_iterations=400,
-          impl=IMPL_DEFAULT, starts=None, warp=None):
+          impl=IMPL_DEFAULT, starts=None, warp=None, geometry=None):
     """The moving image on the fixed image's grid.  moving, fixed: (D, H, W) float32 device tensors of one subject, voxel sizes
     (x, y, z).  In order: robust_range and code of both images; the start, register.centre_init(fixed.shape, fixed_vs, moving.shape,
     moving_vs) unless `init` (a map, fixed voxel -> moving position) is given; search; the moving image resampled through the map
@@ -193,6 +193,10 @@ def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_S
     and score_warped int64 {1} (N * MI before and after), max_disp_q8 int32 {}), all device tensors, not read here.  None: the
     3-tuple, from the same calls as before the keyword existed.
 
+    geometry: a deform.Plan(jacobian, iters, impl), only with `warp`: deform.jacobian runs on the fitted field and
+    the fourth element gains det (float32 on the fixed grid, None when the plan's jacobian is False), folded, det_min, det_max (int64
+    {1} each, the extremes as deform.summary's keys), device tensors, not read here.  None: nothing of this runs.
+
     Returns (map float32 {12} on the device, info int64 {4} on the device = (iterations, converged, score, stage of the last
     iteration), moved float32 of fixed's shape).  The host reads the two ranges before the search and the 12 floats of the map
     after it (the resampling takes its map in the launch arguments)."""
@@ -200,6 +204,11 @@ def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_S
         from . import cowarp as CW
         from . import warp as W
         warp_levels, warp_limit, warp_impl = CW._plan(warp, "coreg.align")
+    if geometry is not None:
+        from . import deform as DF
+        if warp is None:
+            raise UNetError("coreg.align: geometry needs warp: there is no field without a fit")
+        geo_det = DF._plan(geometry, "coreg.align")[0]
     _image(fixed, "fixed", "align")
     _image(moving, "moving", "align", fixed.device)
     b = _bins(bins, "align")
@@ -235,5 +244,8 @@ def align(moving, moving_vs, fixed, fixed_vs, bins=16, init=None, step=DEFAULT_S
     field, report = CW.fit(fc, mc, b, m, levels=levels, impl=warp_impl)
     score_warped = scores(CW.hist(fc, mc, b, m, field, g).view(1, b, b + 1))
     moved = CW.resample(moving, tuple(fixed.shape), m, field, g)
-    return map_dev, info, moved, dict(field=field, g=g, report=report, score_affine=score_affine, score_warped=score_warped,
-                                      max_disp_q8=field.abs().max())
+    extra = dict(field=field, g=g, report=report, score_affine=score_affine, score_warped=score_warped, max_disp_q8=field.abs().max())
+    if geometry is not None:
+        det, det_info = DF.jacobian(tuple(fixed.shape), m, field, g, det=geo_det)
+        extra.update(det=det, folded=det_info[1:2], det_min=det_info[2:3], det_max=det_info[3:4])
+    return map_dev, info, moved, extra

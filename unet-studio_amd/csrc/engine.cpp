@@ -3140,6 +3140,50 @@ int unet_cowarp_resample(const float* moving, int mw, int mh, int md, int fw, in
     return run_on_device_of(out, stream, [&](hipStream_t s) { launch_cowarp_resample(moving, mw, mh, md, fw, fh, fd, map, D, g, out, s); });
 }
 
+// ---- the geometry of a fitted lattice warp (include/unet_deform.h) ----
+static std::string deform_grid_error(const std::string& w, const char* name, int a, int b, int c) {
+    if (a <= 0 || b <= 0 || c <= 0) return w + name + " dimensions must be positive";
+    if ((int64_t)a * b * c >= ((int64_t)1 << 31)) return w + "the " + name + " grid must stay below 2^31 voxels";
+    return std::string();
+}
+static std::string opt_ptr_error(const std::string& w, const void* p, const char* name, int align) {
+    return p ? ptr_error(w, p, name, align) : std::string();
+}
+static_assert(UNET_DEFORM_MAX_DISP == UNET_WARP_MAX_DISP, "a field of either warp");
+int unet_deform_jacobian(int sw, int sh, int sd, const float* map, const int32_t* D, int g, float* det, int64_t* info, void* stream) {
+    const std::string w = "unet_deform_jacobian: ";
+    if (std::string e = deform_grid_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (std::string e = opt_ptr_error(w, det, "det", 4); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return fail(e);
+    return run_on_device_of(info, stream, [&](hipStream_t s) {   // map is consumed inside the launcher, before this returns
+        launch_deform_jacobian(sw, sh, sd, map, D, g, det, info, s);
+    });
+}
+int unet_deform_pull(const void* volume, int kind, int sw, int sh, int sd, int tw, int th, int td, const float* map, const float* inv,
+                     const int32_t* D, int g, int iters, void* out, float* pos, int64_t* info, int impl, void* stream) {
+    const std::string w = "unet_deform_pull: ";
+    if (kind < UNET_DEFORM_KIND_F32 || kind > UNET_DEFORM_KIND_U16) return fail(w + "unknown kind " + std::to_string(kind));
+    const int bytes = kind == UNET_DEFORM_KIND_F32 ? 4 : kind == UNET_DEFORM_KIND_U16 ? 2 : 1;
+    if (std::string e = ptr_error(w, volume, "volume", bytes); !e.empty()) return fail(e);
+    if (std::string e = deform_grid_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = deform_grid_error(w, "template", tw, th, td); !e.empty()) return fail(e);
+    if (!map) return fail(w + "null map");
+    if (!inv) return fail(w + "null inv");
+    if (std::string e = opt_ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (iters < 0 || iters > UNET_DEFORM_MAX_ITERS) return fail(w + "iters must be in [0, 32], got " + std::to_string(iters));
+    if (std::string e = ptr_error(w, out, "out", bytes); !e.empty()) return fail(e);
+    if (std::string e = opt_ptr_error(w, pos, "pos", 4); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return fail(e);
+    if (impl < UNET_DEFORM_IMPL_DEFAULT || impl > UNET_DEFORM_IMPL_TILE) return fail(w + "unknown impl " + std::to_string(impl));
+    return run_on_device_of(info, stream, [&](hipStream_t s) {   // map and inv are consumed inside the launcher
+        launch_deform_pull(volume, kind, sw, sh, sd, tw, th, td, map, inv, D, g, iters, out, pos, info, impl, s);
+    });
+}
+
 // ---- the tables of a label map (include/unet_table.h) ----
 static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
                                       size_t scratch_bytes) {

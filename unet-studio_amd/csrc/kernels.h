@@ -13,6 +13,7 @@
 #include "../../include/unet_connectivity.h"
 #include "../../include/unet_coreg.h"
 #include "../../include/unet_cowarp.h"
+#include "../../include/unet_deform.h"
 #include "../../include/unet_distance.h"
 #include "../../include/unet_ensemble.h"
 #include "../../include/unet_feed.h"
@@ -575,6 +576,12 @@ void launch_cowarp_fit(const uint8_t* fixed, int fw, int fh, int fd, const uint8
                        hipStream_t s);
 void launch_cowarp_resample(const float* moving, int mw, int mh, int md, int fw, int fh, int fd, const float* map, const int32_t* D, int g,
                             float* out, hipStream_t s);
+
+// kernels_deform.hip: the geometry of a fitted lattice warp (include/unet_deform.h); map and inv: host arrays, read before the return;
+// det, D (pull) and pos may be null
+void launch_deform_jacobian(int sw, int sh, int sd, const float* map, const int32_t* D, int g, float* det, int64_t* info, hipStream_t s);
+void launch_deform_pull(const void* volume, int kind, int sw, int sh, int sd, int tw, int th, int td, const float* map, const float* inv,
+                        const int32_t* D, int g, int iters, void* out, float* pos, int64_t* info, int impl, hipStream_t s);
 
 // kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
 size_t table_scratch_bytes(int n_labels);

@@ -198,7 +198,7 @@ class Atlas:
 
 
 def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissues=5, init=None, step=DEFAULT_STEP, stages=DEFAULT_STAGES,
-               max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT, starts=None, template_moments=None, warp=None):
+               max_iterations=400, max_rounds=None, smooth_rounds=1, impl=IMPL_DEFAULT, starts=None, template_moments=None, warp=None, geometry=None):
     """The atlas's regions on the subject's grid.  subject_tissue: the subject's tissue map (an evaluation's label output), template:
     the template's, atlas: the corrected atlas on the template grid (atlas.prepare_atlas); (D, H, W) device tensors, voxel sizes
     (x, y, z).  search from `init` (centre_init when None), carry, then atlas.grow on the subject grid with the subject tissue as
@@ -212,6 +212,11 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
     back at synchronisation 1, and warp.carry takes carry's place.  The report gains warp = dict(levels int32 {n, 5}, report (the
     rows of the schedule), score_affine, score_warped, max_disp_q8).  None: today's calls, unchanged.
 
+    geometry: a deform.Plan(jacobian, iters, impl), only with `warp`: deform.jacobian runs on the fitted field and
+    the report gains geometry = dict(field int32 {nz, ny, nx, 3} and det float32 on the subject grid (device tensors; det is None
+    when the plan's jacobian is False), g the field's spacing, folded, det_min, det_max, iters, impl): what `to_template` pulls
+    with.  Its info travels in the final readback: no further host synchronisation.  None: nothing of this runs.
+
     Returns (regions uint16 on the subject grid, report) with report = dict(map (m[9], t[3]) float32, iterations, converged, score,
     direct, rescued, left, filled (uint32 {n_tissues} each), rounds, grow_converged); with `starts` also starts = start.report's
     dict, and iterations, converged and score are the best state's.  With `starts` the host also waits once for the subject's
@@ -224,6 +229,11 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
     if warp is not None:
         from . import warp as W
         warp_levels, warp_limit = W._plan(warp, "register.parcellate")
+    if geometry is not None:
+        from . import deform as DF
+        if warp is None:
+            raise UNetError("register.parcellate: geometry needs warp: there is no field without a fit")
+        geo_det, geo_iters, geo_impl = DF._plan(geometry, "register.parcellate")
     if init is None:
         if not (torch.is_tensor(subject_tissue) and torch.is_tensor(template)):
             raise UNetError("register.parcellate: subject_tissue and template must be device tensors")
@@ -245,6 +255,8 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
         field, rows = W.fit(subject_tissue, template, T, m, levels=levels)
         regions, counts = W.carry(subject_tissue, template, atlas, T, m, field, int(levels[-1, 0]))
         affine_hist, max_disp = joint_hist(subject_tissue, template, T, [m]), field.abs().amax()
+        if geometry is not None:
+            det, det_info = DF.jacobian(tuple(subject_tissue.shape), m, field, int(levels[-1, 0]), det=geo_det)
     g = A.grow(subject_tissue, regions, T, list(range(1, T)), flags=A.CLAMP | A.PRESERVE, max_rounds=max_rounds, smooth_rounds=smooth_rounds)
 
     def u32(t):
@@ -267,4 +279,27 @@ def parcellate(subject_tissue, subject_vs, template, template_vs, atlas, n_tissu
         rows_h = rows_h[rows_h[:, 0] >= 0]
         report["warp"] = dict(levels=levels, report=rows_h, score_affine=W.score(u32(affine_hist)[0]), score_warped=int(rows_h[-1, 4]),
                               max_disp_q8=int(max_disp.cpu()))
+    if geometry is not None:
+        d = DF.summary(det_info)
+        report["geometry"] = dict(field=field, g=int(levels[-1, 0]), det=det, folded=d["folded"], det_min=d["det_min"], det_max=d["det_max"],
+                                  iters=geo_iters, impl=geo_impl)
     return regions, report
+
+
+def to_template(volume, report, template_shape, kind=None, iters=None, pos=False):
+    """A subject-grid volume on the template grid, through the inverse of what `parcellate(warp=, geometry=)` found: deform.pull with
+    report["map"] and report["geometry"]'s field.  volume: a (D, H, W) device tensor of the subject's shape, float32 (trilinear) or
+    uint8 / uint16 (labels, tissue maps, regions: nearest); kind: None takes it from the dtype, otherwise deform.KIND_F32 / _U8 /
+    _U16, which the dtype must match; iters: None takes the plan's.  Returns deform.pull's (out, pos, info); no host
+    synchronisation."""
+    from . import deform as DF
+    try:
+        geo, m = report["geometry"], report["map"]
+        field, g = geo["field"], geo["g"]
+        iters = geo["iters"] if iters is None else iters
+        impl = geo["impl"]
+    except (KeyError, TypeError):
+        raise UNetError("register.to_template: report must be parcellate's with warp= and geometry=")
+    if kind is not None and (not torch.is_tensor(volume) or DF._KINDS.get(volume.dtype) != kind):
+        raise UNetError("register.to_template: kind %r does not match the volume's dtype" % (kind,))
+    return DF.pull(volume, template_shape, m, field, g, iters=iters, pos=pos, impl=impl)
