@@ -76,14 +76,6 @@ def _codes(t, name, who, dev=None):
     return (t.data_ptr(), w, h, d)
 
 
-def _out(out, n, dtype, dev, name, who):
-    if out is None:
-        return torch.empty(n, dtype=dtype, device=dev)
-    if not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.is_contiguous() and out.dtype == dtype and out.numel() == n):
-        raise UNetError("coreg.%s: %s must be a contiguous %s device tensor of %d entries" % (who, name, dtype, n))
-    return out
-
-
 def code(image, lo, hi, bins=16, out=None, stream=None):
     """unet_coreg_code on the current stream (or the raw `stream`).  image: a contiguous float32 device tensor; returns uint8 of its
     shape on the device (written into `out` when given): 0 below lo, bins - 1 from the last bin on, `bins` for a NaN.  No host
@@ -91,7 +83,7 @@ def code(image, lo, hi, bins=16, out=None, stream=None):
     if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.numel() > 0):
         raise UNetError("coreg.code: image must be a contiguous float32 device tensor")
     b = _bins(bins, "code")
-    codes = _out(out, image.numel(), torch.uint8, image.device, "out", "code")
+    codes = R._out(out, image.numel(), torch.uint8, image.device, "out", "code", "coreg")
     E.check(E.lib.unet_coreg_code(image.data_ptr(), image.numel(), float(lo), float(hi), b, codes.data_ptr(), E.stream(image, stream)))
     return codes.view(image.shape)
 
@@ -111,7 +103,7 @@ def joint_hist(fixed, moving, bins, maps, stride=1, impl=IMPL_DEFAULT, out=None,
     K = int(flat.shape[0])
     if not 1 <= K <= MAX_MAPS:
         raise UNetError("coreg.joint_hist: K must be in [1, %d], got %d" % (MAX_MAPS, K))
-    hist = _out(out, K * b * (b + 1), torch.uint32, fixed.device, "out", "joint_hist")
+    hist = R._out(out, K * b * (b + 1), torch.uint32, fixed.device, "out", "joint_hist", "coreg")
     E.check(E.lib.unet_coreg_hist(*fg, *mg, b, _floats(flat), K, int(stride), hist.data_ptr(), int(impl), None, 0, E.stream(fixed, stream)))
     return hist.view(K, b, b + 1)
 
@@ -123,7 +115,7 @@ def scores(hist, out=None, stream=None):
             and hist.shape[1] in BINS and hist.shape[2] == hist.shape[1] + 1 and 1 <= hist.shape[0] <= MAX_MAPS):
         raise UNetError("coreg.scores: hist must be a contiguous uint32 {K, bins, bins + 1} device tensor, K in [1, %d]" % MAX_MAPS)
     K, b = int(hist.shape[0]), int(hist.shape[1])
-    res = _out(out, K, torch.int64, hist.device, "out", "scores")
+    res = R._out(out, K, torch.int64, hist.device, "out", "scores", "coreg")
     E.check(E.lib.unet_coreg_score(hist.data_ptr(), K, b, res.data_ptr(), E.stream(hist, stream)))
     return res
 

@@ -59,10 +59,7 @@ def _plan(plan, who):
         levels = list(W.DEFAULT_LEVELS if levels is None else levels)
     except (AttributeError, TypeError):
         raise UNetError("%s: warp must be a cowarp.Plan(levels, limit, impl)" % who)
-    if limit is not None and (isinstance(limit, bool) or int(limit) != limit or limit < 0):
-        raise UNetError("%s: warp.limit must be a non-negative integer or None, got %r" % (who, limit))
-    W.levels_of(levels, 0, None, who)                               # the rows' form; the ranges are the library's to check
-    return levels, limit, int(impl)
+    return W._plan_rows(levels, limit, who) + (int(impl),)
 
 
 def _codes(t, name, who, dev=None):
@@ -80,25 +77,9 @@ def _bins(bins, who):
     return int(bins)
 
 
-def _out(out, n, dtype, dev, who):
-    if out is None:
-        return torch.empty(n, dtype=dtype, device=dev)
-    if not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.is_contiguous() and out.dtype == dtype and out.numel() == n):
-        raise UNetError("cowarp.%s: out must be a contiguous %s device tensor of %d entries" % (who, dtype, n))
-    return out
-
-
-def _g(g, who):
-    if isinstance(g, bool) or g not in SPACINGS:
-        raise UNetError("cowarp.%s: g must be 4, 8 or 16, got %r" % (who, g))
-    return int(g)
-
-
 def _field(D, fixed_shape, g, dev, who):
-    want = W.lattice(tuple(fixed_shape), g) + (3,)
-    if not (torch.is_tensor(D) and D.is_cuda and D.device == dev and D.dtype == torch.int32 and D.is_contiguous() and tuple(D.shape) == want):
-        raise UNetError("cowarp.%s: D must be a contiguous int32 %s tensor on the fixed image's device" % (who, list(want)))
-    return D
+    """D on warp.lattice(fixed_shape, g), g one of SPACINGS, on `dev`"""
+    return W._lattice_field(D, fixed_shape, W._g(g, SPACINGS, who), dev, who, "tensor on the fixed image's device")
 
 
 def scratch_bytes(fixed_shape, bins, levels):
@@ -116,8 +97,8 @@ def hist(fixed, moving, bins, map, D, g, out=None, stream=None):
     mg = _codes(moving, "moving", "hist", fixed.device)
     b = _bins(bins, "hist")
     m = R._map12(map, "cowarp.hist")
-    _field(D, fixed.shape, _g(g, "hist"), fixed.device, "hist")
-    h = _out(out, b * (b + 1), torch.uint32, fixed.device, "hist")
+    _field(D, fixed.shape, g, fixed.device, "cowarp.hist")
+    h = R._out(out, b * (b + 1), torch.uint32, fixed.device, "out", "hist", "cowarp")
     E.check(E.lib.unet_cowarp_hist(*fg, *mg, b, R._floats(m), D.data_ptr(), int(g), h.data_ptr(), E.stream(fixed, stream)))
     return h.view(b, b + 1)
 
@@ -130,7 +111,7 @@ def weights(hist, out=None, stream=None):
             and hist.shape[0] in CR.BINS and hist.shape[1] == hist.shape[0] + 1):
         raise UNetError("cowarp.weights: hist must be a contiguous uint32 {bins, bins + 1} device tensor")
     b = int(hist.shape[0])
-    w = _out(out, b * (b + 1), torch.int16, hist.device, "weights")
+    w = R._out(out, b * (b + 1), torch.int16, hist.device, "out", "weights", "cowarp")
     E.check(E.lib.unet_cowarp_weights(hist.data_ptr(), b, w.data_ptr(), E.stream(hist, stream)))
     return w.view(b, b + 1)
 
@@ -142,7 +123,7 @@ def sweep(fixed, moving, bins, map, D, g, step, limit, impl=IMPL_DEFAULT, scratc
     mg = _codes(moving, "moving", "sweep", fixed.device)
     b = _bins(bins, "sweep")
     m = R._map12(map, "cowarp.sweep")
-    _field(D, fixed.shape, _g(g, "sweep"), fixed.device, "sweep")
+    _field(D, fixed.shape, g, fixed.device, "cowarp.sweep")
     need = scratch_bytes(tuple(fixed.shape), b, [(int(g), 1, 1, 1, 0)])
     scratch = E.scratch(scratch, need, fixed.device)
     info = torch.empty(2, dtype=torch.int64, device=fixed.device)
@@ -179,9 +160,9 @@ def resample(moving, fixed_shape, map, D, g, out=None, stream=None):
         raise UNetError("cowarp.resample: moving must be a contiguous (D, H, W) float32 device tensor")
     fw, fh, fd = W._dims(fixed_shape, "resample")
     m = R._map12(map, "cowarp.resample")
-    _field(D, (fd, fh, fw), _g(g, "resample"), moving.device, "resample")
+    _field(D, (fd, fh, fw), g, moving.device, "cowarp.resample")
     md, mh, mw = (int(v) for v in moving.shape)
-    res = _out(out, fw * fh * fd, torch.float32, moving.device, "resample")
+    res = R._out(out, fw * fh * fd, torch.float32, moving.device, "out", "resample", "cowarp")
     E.check(E.lib.unet_cowarp_resample(moving.data_ptr(), mw, mh, md, fw, fh, fd, R._floats(m), D.data_ptr(), int(g), res.data_ptr(),
                                        E.stream(moving, stream)))
     return res.view(fd, fh, fw)

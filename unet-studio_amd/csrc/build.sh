@@ -35,7 +35,7 @@ for pair in conv_z:kernels_mfma_conv wgrad_z:kernels_mfma_wgrad_z conv_zdma:kern
     esac
 done
 # the co-registration kernels (kernels_coreg.hip), the kernels of the starts (kernels_start.hip) and those of the two lattice warps
-# (kernels_warp.hip, kernels_cowarp.hip) and of their geometry (kernels_deform.hip) must not spill: read every kernel's scratch size from the compiler's resource-usage remarks whenever the file
+# (kernels_warp.hip, kernels_cowarp.hip: each file's own kernels and its five instantiations of lattice_fit.h's) and of their geometry (kernels_deform.hip) must not spill: read every kernel's scratch size from the compiler's resource-usage remarks whenever the file
 # was rebuilt (the remarks stay in build/<file>.remarks: registers, LDS, occupancy)
 for pair in kernels_coreg:10 kernels_start:6 kernels_warp:9 kernels_cowarp:9 kernels_deform:8; do
     f=${pair%%:*}; want=${pair##*:}

@@ -2948,14 +2948,51 @@ static std::string warp_levels_error(const std::string& w, const int* levels, in
     if (rows > UNET_WARP_MAX_ROWS) return w + "levels hold " + std::to_string(rows) + " (level, step) pairs, more than 32";
     return std::string();
 }
-static std::string warp_dims_error(const std::string& w, int sw, int sh, int sd) {
-    if (sw <= 0 || sh <= 0 || sd <= 0) return w + "subject dimensions must be positive";
-    if ((int64_t)sw * sh * sd >= ((int64_t)1 << 31)) return w + "the subject grid must stay below 2^31 voxels";
+// a grid of the warps, the co-registration's warps and their geometry: positive dimensions, below 2^31 voxels
+static std::string grid_dims_error(const std::string& w, const char* name, int a, int b, int c) {
+    if (a <= 0 || b <= 0 || c <= 0) return w + name + " dimensions must be positive";
+    if ((int64_t)a * b * c >= ((int64_t)1 << 31)) return w + "the " + name + " grid must stay below 2^31 voxels";
     return std::string();
+}
+// What a sweep and a fit of unet_warp.h and of unet_cowarp.h take behind their grids, checked once: the ranges are the same (the
+// static_assert of the section below); a header's own are its g and levels rules and the call that sizes its scratch, with its name
+struct LatticeRules {
+    std::string (*g_error)(const std::string&, int);
+    std::string (*levels_error)(const std::string&, const int*, int);
+    size_t (*scratch_bytes)(int, int, int, const int*, int);
+    const char* see;
+};
+static const LatticeRules warp_rules = {warp_g_error, warp_levels_error, warp_scratch_bytes, "unet_warp_scratch_bytes"};
+static std::string lattice_scratch_error(const std::string& w, const LatticeRules& r, int sw, int sh, int sd, const int* levels, int n_levels,
+                                         int impl, const void* scratch, size_t scratch_bytes) {
+    if (impl < UNET_WARP_IMPL_DEFAULT || impl > UNET_WARP_IMPL_VOXEL) return w + "unknown impl " + std::to_string(impl);
+    if (!scratch) return w + "null scratch";
+    if (scratch_bytes < r.scratch_bytes(sw, sh, sd, levels, n_levels)) return w + "scratch too small (see " + r.see + ")";
+    return std::string();
+}
+static std::string lattice_sweep_error(const std::string& w, const LatticeRules& r, int sw, int sh, int sd, const float* map, const int32_t* D,
+                                       int g, int step, int limit, const int64_t* info, int impl, const void* scratch, size_t scratch_bytes) {
+    if (!map) return w + "null map";
+    if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return e;
+    if (std::string e = r.g_error(w, g); !e.empty()) return e;
+    if (step < 1 || step > UNET_WARP_MAX_DISP) return w + "step must be in [1, 32767], got " + std::to_string(step);
+    if (limit < 0) return w + "limit must not be negative, got " + std::to_string(limit);
+    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return e;
+    const int level[5] = {g, 1, 1, 1, 0};
+    return lattice_scratch_error(w, r, sw, sh, sd, level, 1, impl, scratch, scratch_bytes);
+}
+static std::string lattice_fit_error(const std::string& w, const LatticeRules& r, int sw, int sh, int sd, const float* map, const int* levels,
+                                     int n_levels, const int32_t* D_out, const int64_t* report, int impl, const void* scratch,
+                                     size_t scratch_bytes) {
+    if (!map) return w + "null map";
+    if (std::string e = r.levels_error(w, levels, n_levels); !e.empty()) return e;
+    if (std::string e = ptr_error(w, D_out, "D_out", 4); !e.empty()) return e;
+    if (std::string e = ptr_error(w, report, "report", 8); !e.empty()) return e;
+    return lattice_scratch_error(w, r, sw, sh, sd, levels, n_levels, impl, scratch, scratch_bytes);
 }
 int unet_warp_lattice(int sw, int sh, int sd, int g, int* nx, int* ny, int* nz) {
     const std::string w = "unet_warp_lattice: ";
-    if (std::string e = warp_dims_error(w, sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
     if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
     if (!nx || !ny || !nz) return fail(w + "null output");
     *nx = (sw + g - 1) / g + 1;
@@ -2965,7 +3002,7 @@ int unet_warp_lattice(int sw, int sh, int sd, int g, int* nx, int* ny, int* nz) 
 }
 int unet_warp_scratch_bytes(int sw, int sh, int sd, int n_tissues, const int* levels, int n_levels, size_t* bytes) {
     const std::string w = "unet_warp_scratch_bytes: ";
-    if (std::string e = warp_dims_error(w, sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
     if (n_tissues < 2 || n_tissues > UNET_WARP_MAX_TISSUES) return fail(w + "n_tissues must be in [2, 16], got " + std::to_string(n_tissues));
     if (std::string e = warp_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
     if (!bytes) return fail(w + "null output");
@@ -2991,16 +3028,8 @@ int unet_warp_sweep(const void* subject, int sbytes, int sw, int sh, int sd, con
     const std::string w = "unet_warp_sweep: ";
     const std::string e = reg_grids_error("unet_warp_sweep", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
     if (!e.empty()) return fail(e);
-    if (!map) return fail(w + "null map");
-    if (std::string pe = ptr_error(w, D, "D", 4); !pe.empty()) return fail(pe);
-    if (std::string ge = warp_g_error(w, g); !ge.empty()) return fail(ge);
-    if (step < 1 || step > UNET_WARP_MAX_DISP) return fail(w + "step must be in [1, 32767], got " + std::to_string(step));
-    if (limit < 0) return fail(w + "limit must not be negative, got " + std::to_string(limit));
-    if (std::string pe = ptr_error(w, info, "info", 8); !pe.empty()) return fail(pe);
-    if (impl < UNET_WARP_IMPL_DEFAULT || impl > UNET_WARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
-    if (!scratch) return fail(w + "null scratch");
-    const int level[5] = {g, 1, 1, 1, 0};
-    if (scratch_bytes < warp_scratch_bytes(sw, sh, sd, level, 1)) return fail(w + "scratch too small (see unet_warp_scratch_bytes)");
+    const std::string se = lattice_sweep_error(w, warp_rules, sw, sh, sd, map, D, g, step, limit, info, impl, scratch, scratch_bytes);
+    if (!se.empty()) return fail(se);
     return run_on_device_of(D, stream, [&](hipStream_t s) {
         launch_warp_sweep(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, map, D, g, step, limit, info, impl, scratch, s);
     });
@@ -3008,7 +3037,7 @@ int unet_warp_sweep(const void* subject, int sbytes, int sw, int sh, int sd, con
 int unet_warp_refine(const int32_t* D_coarse, int sw, int sh, int sd, int g, int32_t* D_fine, void* stream) {
     const std::string w = "unet_warp_refine: ";
     if (std::string pe = ptr_error(w, D_coarse, "D_coarse", 4); !pe.empty()) return fail(pe);
-    if (std::string e = warp_dims_error(w, sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
     if (g != 8 && g != 16 && g != 32) return fail(w + "g must be 8, 16 or 32, got " + std::to_string(g));
     if (std::string pe = ptr_error(w, D_fine, "D_fine", 4); !pe.empty()) return fail(pe);
     return run_on_device_of(D_fine, stream, [&](hipStream_t s) { launch_warp_refine(D_coarse, sw, sh, sd, g, D_fine, s); });
@@ -3019,13 +3048,8 @@ int unet_warp_fit(const void* subject, int sbytes, int sw, int sh, int sd, const
     const std::string w = "unet_warp_fit: ";
     const std::string e = reg_grids_error("unet_warp_fit", subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues);
     if (!e.empty()) return fail(e);
-    if (!map) return fail(w + "null map");
-    if (std::string le = warp_levels_error(w, levels, n_levels); !le.empty()) return fail(le);
-    if (std::string pe = ptr_error(w, D_out, "D_out", 4); !pe.empty()) return fail(pe);
-    if (std::string pe = ptr_error(w, report, "report", 8); !pe.empty()) return fail(pe);
-    if (impl < UNET_WARP_IMPL_DEFAULT || impl > UNET_WARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
-    if (!scratch) return fail(w + "null scratch");
-    if (scratch_bytes < warp_scratch_bytes(sw, sh, sd, levels, n_levels)) return fail(w + "scratch too small (see unet_warp_scratch_bytes)");
+    const std::string fe = lattice_fit_error(w, warp_rules, sw, sh, sd, map, levels, n_levels, D_out, report, impl, scratch, scratch_bytes);
+    if (!fe.empty()) return fail(fe);
     return run_on_device_of(D_out, stream, [&](hipStream_t s) {   // map and levels are consumed inside the launcher
         launch_warp_fit(subject, sbytes, sw, sh, sd, template_, tbytes, tw, th, td, n_tissues, map, levels, n_levels, D_out, report, impl,
                         scratch, s);
@@ -3061,11 +3085,12 @@ static std::string cowarp_levels_error(const std::string& w, const int* levels, 
     return warp_levels_error(w, levels, n_levels);
 }
 static_assert(UNET_COWARP_MAX_STEP == UNET_WARP_MAX_STEP && UNET_COWARP_MAX_SWEEPS == UNET_WARP_MAX_SWEEPS &&
-              UNET_COWARP_MAX_ROWS == UNET_WARP_MAX_ROWS && UNET_COWARP_MAX_DISP == UNET_WARP_MAX_DISP, "one schedule for both warps");
+              UNET_COWARP_MAX_ROWS == UNET_WARP_MAX_ROWS && UNET_COWARP_MAX_DISP == UNET_WARP_MAX_DISP &&
+              UNET_COWARP_IMPL_DEFAULT == UNET_WARP_IMPL_DEFAULT && UNET_COWARP_IMPL_VOXEL == UNET_WARP_IMPL_VOXEL, "one schedule for both warps");
+static const LatticeRules cowarp_rules = {cowarp_g_error, cowarp_levels_error, cowarp_scratch_bytes, "unet_cowarp_scratch_bytes"};
 int unet_cowarp_scratch_bytes(int fw, int fh, int fd, int bins, const int* levels, int n_levels, size_t* bytes) {
     const std::string w = "unet_cowarp_scratch_bytes: ";
-    if (fw <= 0 || fh <= 0 || fd <= 0) return fail(w + "fixed dimensions must be positive");
-    if ((int64_t)fw * fh * fd >= ((int64_t)1 << 31)) return fail(w + "the fixed grid must stay below 2^31 voxels");
+    if (std::string e = grid_dims_error(w, "fixed", fw, fh, fd); !e.empty()) return fail(e);
     if (!coreg_bins_ok(bins)) return fail(w + "bins must be 8, 16 or 32, got " + std::to_string(bins));
     if (std::string e = cowarp_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
     if (!bytes) return fail(w + "null output");
@@ -3095,16 +3120,8 @@ int unet_cowarp_sweep(const uint8_t* fixed, int fw, int fh, int fd, const uint8_
                       int32_t* D, int g, int step, int limit, int64_t* info, int impl, void* scratch, size_t scratch_bytes, void* stream) {
     const std::string w = "unet_cowarp_sweep: ";
     if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
-    if (!map) return fail(w + "null map");
-    if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
-    if (std::string e = cowarp_g_error(w, g); !e.empty()) return fail(e);
-    if (step < 1 || step > UNET_COWARP_MAX_DISP) return fail(w + "step must be in [1, 32767], got " + std::to_string(step));
-    if (limit < 0) return fail(w + "limit must not be negative, got " + std::to_string(limit));
-    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return fail(e);
-    if (impl < UNET_COWARP_IMPL_DEFAULT || impl > UNET_COWARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
-    if (!scratch) return fail(w + "null scratch");
-    const int level[5] = {g, 1, 1, 1, 0};
-    if (scratch_bytes < cowarp_scratch_bytes(fw, fh, fd, level, 1)) return fail(w + "scratch too small (see unet_cowarp_scratch_bytes)");
+    const std::string se = lattice_sweep_error(w, cowarp_rules, fw, fh, fd, map, D, g, step, limit, info, impl, scratch, scratch_bytes);
+    if (!se.empty()) return fail(se);
     return run_on_device_of(D, stream, [&](hipStream_t s) {
         launch_cowarp_sweep(fixed, fw, fh, fd, moving, mw, mh, md, bins, map, D, g, step, limit, info, impl, scratch, s);
     });
@@ -3114,13 +3131,8 @@ int unet_cowarp_fit(const uint8_t* fixed, int fw, int fh, int fd, const uint8_t*
                     void* stream) {
     const std::string w = "unet_cowarp_fit: ";
     if (std::string e = coreg_grids_error(w, fixed, fw, fh, fd, moving, mw, mh, md, bins); !e.empty()) return fail(e);
-    if (!map) return fail(w + "null map");
-    if (std::string e = cowarp_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
-    if (std::string e = ptr_error(w, D_out, "D_out", 4); !e.empty()) return fail(e);
-    if (std::string e = ptr_error(w, report, "report", 8); !e.empty()) return fail(e);
-    if (impl < UNET_COWARP_IMPL_DEFAULT || impl > UNET_COWARP_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
-    if (!scratch) return fail(w + "null scratch");
-    if (scratch_bytes < cowarp_scratch_bytes(fw, fh, fd, levels, n_levels)) return fail(w + "scratch too small (see unet_cowarp_scratch_bytes)");
+    const std::string fe = lattice_fit_error(w, cowarp_rules, fw, fh, fd, map, levels, n_levels, D_out, report, impl, scratch, scratch_bytes);
+    if (!fe.empty()) return fail(fe);
     return run_on_device_of(D_out, stream, [&](hipStream_t s) {   // map and levels are consumed inside the launcher
         launch_cowarp_fit(fixed, fw, fh, fd, moving, mw, mh, md, bins, map, levels, n_levels, D_out, report, impl, scratch, s);
     });
@@ -3129,10 +3141,8 @@ int unet_cowarp_resample(const float* moving, int mw, int mh, int md, int fw, in
                          float* out, void* stream) {
     const std::string w = "unet_cowarp_resample: ";
     if (std::string e = ptr_error(w, moving, "moving", 4); !e.empty()) return fail(e);
-    if (mw <= 0 || mh <= 0 || md <= 0) return fail(w + "moving dimensions must be positive");
-    if (fw <= 0 || fh <= 0 || fd <= 0) return fail(w + "fixed dimensions must be positive");
-    if ((int64_t)mw * mh * md >= ((int64_t)1 << 31)) return fail(w + "the moving grid must stay below 2^31 voxels");
-    if ((int64_t)fw * fh * fd >= ((int64_t)1 << 31)) return fail(w + "the fixed grid must stay below 2^31 voxels");
+    if (std::string e = grid_dims_error(w, "moving", mw, mh, md); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "fixed", fw, fh, fd); !e.empty()) return fail(e);
     if (!map) return fail(w + "null map");
     if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
     if (std::string e = cowarp_g_error(w, g); !e.empty()) return fail(e);
@@ -3141,18 +3151,13 @@ int unet_cowarp_resample(const float* moving, int mw, int mh, int md, int fw, in
 }
 
 // ---- the geometry of a fitted lattice warp (include/unet_deform.h) ----
-static std::string deform_grid_error(const std::string& w, const char* name, int a, int b, int c) {
-    if (a <= 0 || b <= 0 || c <= 0) return w + name + " dimensions must be positive";
-    if ((int64_t)a * b * c >= ((int64_t)1 << 31)) return w + "the " + name + " grid must stay below 2^31 voxels";
-    return std::string();
-}
 static std::string opt_ptr_error(const std::string& w, const void* p, const char* name, int align) {
     return p ? ptr_error(w, p, name, align) : std::string();
 }
 static_assert(UNET_DEFORM_MAX_DISP == UNET_WARP_MAX_DISP, "a field of either warp");
 int unet_deform_jacobian(int sw, int sh, int sd, const float* map, const int32_t* D, int g, float* det, int64_t* info, void* stream) {
     const std::string w = "unet_deform_jacobian: ";
-    if (std::string e = deform_grid_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
     if (!map) return fail(w + "null map");
     if (std::string e = ptr_error(w, D, "D", 4); !e.empty()) return fail(e);
     if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
@@ -3168,8 +3173,8 @@ int unet_deform_pull(const void* volume, int kind, int sw, int sh, int sd, int t
     if (kind < UNET_DEFORM_KIND_F32 || kind > UNET_DEFORM_KIND_U16) return fail(w + "unknown kind " + std::to_string(kind));
     const int bytes = kind == UNET_DEFORM_KIND_F32 ? 4 : kind == UNET_DEFORM_KIND_U16 ? 2 : 1;
     if (std::string e = ptr_error(w, volume, "volume", bytes); !e.empty()) return fail(e);
-    if (std::string e = deform_grid_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
-    if (std::string e = deform_grid_error(w, "template", tw, th, td); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "subject", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "template", tw, th, td); !e.empty()) return fail(e);
     if (!map) return fail(w + "null map");
     if (!inv) return fail(w + "null inv");
     if (std::string e = opt_ptr_error(w, D, "D", 4); !e.empty()) return fail(e);

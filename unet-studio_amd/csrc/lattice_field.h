@@ -1,8 +1,8 @@
 // What the two lattice warps share (kernels_warp.hip: tissue maps, include/unet_warp.h; kernels_cowarp.hip: intensity codes,
 // include/unet_cowarp.h): the lattice over a grid, the warped position of a voxel under a 12-float map and a Q8 displacement field,
 // and a node's support, admissibility and choice.  Only what a voxel's sample adds to a node's seven sums differs between the two.
-// Device code is all inlined: by the move kernels_warp.hip's hist, vox, refine, row and carry kernels are emitted unchanged, its node and
-// pick kernels with one or two instructions reordered.
+// This is the arithmetic, all inlined device code; the kernels of a sweep and the schedule of a fit built on it are lattice_fit.h's,
+// and the histogram, row, refine, carry and resample kernels of the two files call it directly.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -60,27 +60,10 @@ def _iters(iters, who):
         raise UNetError("%s: iters must be an integer in [0, %d], got %r" % (who, MAX_ITERS, iters))
 
 
-def _g(g, who):
-    if isinstance(g, bool) or g not in SPACINGS:
-        raise UNetError("deform.%s: g must be 4, 8, 16 or 32, got %r" % (who, g))
-    return int(g)
-
-
 def _field(D, subject_shape, g, dev, who):
-    want = W.lattice(tuple(subject_shape), g) + (3,)
-    if not (torch.is_tensor(D) and D.is_cuda and (dev is None or D.device == dev) and D.dtype == torch.int32 and D.is_contiguous()
-            and tuple(D.shape) == want):
-        raise UNetError("deform.%s: D must be a contiguous int32 %s device tensor%s" % (who, list(want), "" if dev is None else
-                                                                                         " on the volume's device"))
-    return D
-
-
-def _out(out, n, dtype, dev, name, who):
-    if out is None:
-        return torch.empty(n, dtype=dtype, device=dev)
-    if not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.is_contiguous() and out.dtype == dtype and out.numel() == n):
-        raise UNetError("deform.%s: %s must be a contiguous %s device tensor of %d entries" % (who, name, dtype, n))
-    return out
+    """D on warp.lattice(subject_shape, g), g one of SPACINGS, and on `dev` unless None"""
+    return W._lattice_field(D, subject_shape, W._g(g, SPACINGS, who), dev, who,
+                            "device tensor" + ("" if dev is None else " on the volume's device"))
 
 
 def jacobian(subject_shape, map, D, g, det=True, stream=None):
@@ -90,10 +73,10 @@ def jacobian(subject_shape, map, D, g, det=True, stream=None):
     of the smallest and the largest det (`summary` decodes them).  No host synchronisation."""
     sw, sh, sd = W._dims(subject_shape, "jacobian")
     m = R._map12(map, "deform.jacobian")
-    _field(D, (sd, sh, sw), _g(g, "jacobian"), None, "jacobian")
+    _field(D, (sd, sh, sw), g, None, "deform.jacobian")
     out = None
     if det is not False and det is not None:
-        out = _out(None if det is True else det, sw * sh * sd, torch.float32, D.device, "det", "jacobian")
+        out = R._out(None if det is True else det, sw * sh * sd, torch.float32, D.device, "det", "jacobian", "deform")
     info = torch.empty(4, dtype=torch.int64, device=D.device)
     E.check(E.lib.unet_deform_jacobian(sw, sh, sd, R._floats(m), D.data_ptr(), int(g), out.data_ptr() if out is not None else None,
                                        info.data_ptr(), E.stream(D, stream)))
@@ -116,11 +99,11 @@ def pull(volume, template_shape, map, D, g, inv=None, iters=8, pos=False, impl=I
     _iters(iters, "deform.pull")
     sd, sh, sw = (int(v) for v in volume.shape)
     if D is not None:
-        _field(D, volume.shape, _g(g, "pull"), volume.device, "pull")
-    res = _out(out, tw * th * td, volume.dtype, volume.device, "out", "pull")
+        _field(D, volume.shape, g, volume.device, "deform.pull")
+    res = R._out(out, tw * th * td, volume.dtype, volume.device, "out", "pull", "deform")
     p = None
     if pos is not False and pos is not None:
-        p = _out(None if pos is True else pos, 3 * tw * th * td, torch.float32, volume.device, "pos", "pull")
+        p = R._out(None if pos is True else pos, 3 * tw * th * td, torch.float32, volume.device, "pos", "pull", "deform")
     info = torch.empty(2, dtype=torch.int64, device=volume.device)
     E.check(E.lib.unet_deform_pull(volume.data_ptr(), _KINDS[volume.dtype], sw, sh, sd, tw, th, td, R._floats(m), R._floats(iv),
                                    D.data_ptr() if D is not None else None, int(g), int(iters), res.data_ptr(),

@@ -88,11 +88,12 @@ def _tissue(t, name, who, dev=None):
     return (t.data_ptr(), t.element_size(), w, h, d)
 
 
-def _out(out, n, dtype, dev, name, who):
+def _out(out, n, dtype, dev, name, who, mod="register"):
+    """the output tensor of `mod`.`who` (coreg, cowarp and deform name themselves): a new one, or the caller's `name`, checked"""
     if out is None:
         return torch.empty(n, dtype=dtype, device=dev)
     if not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.is_contiguous() and out.dtype == dtype and out.numel() == n):
-        raise UNetError("register.%s: %s must be a contiguous %s device tensor of %d entries" % (who, name, dtype, n))
+        raise UNetError("%s.%s: %s must be a contiguous %s device tensor of %d entries" % (mod, who, name, dtype, n))
     return out
 
 

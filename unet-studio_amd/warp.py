@@ -94,15 +94,20 @@ def levels_of(levels, limit, map, who="warp.fit"):
     return np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1, 5))
 
 
+def _plan_rows(levels, limit, who):
+    """(levels, limit) of a warp.Plan or a cowarp.Plan, checked"""
+    if limit is not None and (isinstance(limit, bool) or int(limit) != limit or limit < 0):
+        raise UNetError("%s: warp.limit must be a non-negative integer or None, got %r" % (who, limit))
+    levels_of(levels, 0, None, who)                                 # the rows' form; the ranges are the library's to check
+    return levels, limit
+
+
 def _plan(plan, who):
     try:
         levels, limit = list(plan.levels), plan.limit
     except (AttributeError, TypeError):
         raise UNetError("%s: warp must be a warp.Plan(levels, limit)" % who)
-    if limit is not None and (isinstance(limit, bool) or int(limit) != limit or limit < 0):
-        raise UNetError("%s: warp.limit must be a non-negative integer or None, got %r" % (who, limit))
-    levels_of(levels, 0, None, who)                                 # the rows' form; the ranges are the library's to check
-    return levels, limit
+    return _plan_rows(levels, limit, who)
 
 
 def scratch_bytes(subject_shape, n_tissues, levels):
@@ -112,15 +117,28 @@ def scratch_bytes(subject_shape, n_tissues, levels):
                         int(lv.shape[0]))
 
 
-def _field(D, subject, g, who, name="D"):
+def _g(g, spacings, who):
+    """a lattice spacing of cowarp or deform (`who`: "module.function"); warp's own is the library's to check"""
+    if isinstance(g, bool) or g not in spacings:
+        raise UNetError("%s: g must be %s or %d, got %r" % (who, ", ".join(str(v) for v in spacings[:-1]), spacings[-1], g))
+    return int(g)
+
+
+def _lattice_field(D, shape, g, dev, who, where):
+    """D on lattice(shape, g), and on `dev` unless None; `where`: the words of the message behind the shape"""
+    want = lattice(tuple(shape), g) + (3,)
+    if not (torch.is_tensor(D) and D.is_cuda and (dev is None or D.device == dev) and D.dtype == torch.int32 and D.is_contiguous()
+            and tuple(D.shape) == want):
+        raise UNetError("%s: D must be a contiguous int32 %s %s" % (who, list(want), where))
+    return D
+
+
+def _field(D, subject, g, who):
     try:
-        want = lattice(tuple(subject.shape), g) + (3,)
+        lattice(tuple(subject.shape), g)
     except UNetError as e:
         raise UNetError("warp.%s: %s" % (who, e))
-    if not (torch.is_tensor(D) and D.is_cuda and D.device == subject.device and D.dtype == torch.int32 and D.is_contiguous()
-            and tuple(D.shape) == want):
-        raise UNetError("warp.%s: %s must be a contiguous int32 %s tensor on the subject's device" % (who, name, list(want)))
-    return D
+    return _lattice_field(D, subject.shape, g, subject.device, "warp." + who, "tensor on the subject's device")
 
 
 def _tissues(subject, template, n_tissues, who):
