@@ -202,8 +202,27 @@ int unet_op_scratch_bytes(int cin, int cout, int D, int H, int W, size_t* bytes)
  * dgrad:   0 bf16 MFMA, 1 fp32 MFMA, 2 direct
  * wgrad:   0 first-conv MFMA, 1 bf16 MFMA, 2 fp32 MFMA, 3 register-accumulating small kernels, 4 direct */
 int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]);
+/* The same query for the entries that take two plain sources (c0 + c1 input channels, read as their channel concatenation; c1 = 0: one
+ * source, the query above). */
+int unet_op_conv_choice2(int dtype, int impl, int c0, int c1, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]);
 int unet_op_conv3d_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D,
                        int H, int W, int ks, int stride, void* scratch, void* stream);
+/* The conv entries for a layer with two sources, as a plan runs the convs that read cat(skip, x) without materialising it: x0 [.., c0]
+ * and x1 [.., c1] (c1 = 0: one source, x1 ignored) are read as their channel concatenation; w [cout][c0 + c1][k][k][k].  The family
+ * comes from choose_conv with both sources (unet_op_conv_choice2), scratch is unet_op_scratch_bytes(c0 + c1, cout, D, H, W) bytes.
+ * The one-source entries are these with c1 = 0. */
+int unet_op_conv3d_fwd2(int dtype, int impl, const void* x0, int c0, const void* x1, int c1, const float* w, const float* b, void* y,
+                        int cout, int D, int H, int W, int ks, int stride, void* scratch, void* stream);
+/* The input gradient with a destination per source: d0 [D][H][W][c0] and d1 [D][H][W][c1], each written (acc = 0) or added to (acc = 1);
+ * a NULL destination is left alone (that source needs no gradient), at least one must be given.  transposed = 1: the dgrad of a
+ * conv_trans k2 s2 (w [c0][cout][2][2][2]; D, H, W the coarse grid of d0; ks and stride ignored), one destination only: c1 != 0 is
+ * refused. */
+int unet_op_conv3d_bwd_data2(int dtype, int impl, int transposed, const void* dy, const float* w, void* d0, int c0, int acc0, void* d1,
+                             int c1, int acc1, int cout, int D, int H, int W, int ks, int stride, void* scratch, void* stream);
+/* The weight and bias gradient over both sources, added into dw [cout][c0 + c1][k][k][k] and db; launched politely under UNET_OP_POLITE
+ * like unet_op_conv3d_bwd_weight. */
+int unet_op_conv3d_bwd_weight2(int dtype, int impl, const void* x0, int c0, const void* x1, int c1, const void* dy, float* dw, float* db,
+                               int cout, int D, int H, int W, int ks, int stride, void* scratch, void* stream);
 /* conv3d with the read-side fusion of the engine: the input is seen as act(x*scale[c]+shift[c]) (scale/shift fp32 [cin] or
  * NULL, act 0 none 1 relu 2 leaky_relu(0.01) 3 elu), zero padding applied after it; stats (may be NULL) receives the
  * per-channel {sum, sum of squares} of the stored output, fp32 [cout][2] (what the following norm layer needs). */
@@ -239,6 +258,12 @@ int unet_op_conv3d_fwd_norm(const void* x0, const void* x1, int cin0, int cin1, 
 int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w, void* dx, int accumulate, const void* u, const float* stat,
                                  const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin, int cout, int D, int H,
                                  int W, void* scratch, void* stream);
+/* The same entry with the conv's stride spelled out (transposed = 0: 1 or 2; ignored for a conv_trans): with stride 2, dy lies on the
+ * coarse grid ((D - 1) / 2 + 1, ...) and dx, u on the fine one -- the dgrad of the encoder's stride-2 convs, which as the last writer of a
+ * skip tensor's gradient accumulates and leaves the norm backward's statistics rows. */
+int unet_op_conv3d_bwd_data_norm_strided(int transposed, int stride, const void* dy, const float* w, void* dx, int accumulate, const void* u,
+                                         const float* stat, const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin,
+                                         int cout, int D, int H, int W, void* scratch, void* stream);
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout,
                               int D, int H, int W, int ks, int stride, void* scratch, void* stream);
 int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D,
@@ -247,6 +272,19 @@ int unet_op_convt_bwd_data(int dtype, int impl, const void* dy, const float* w, 
                            int W, void* scratch, void* stream);
 int unet_op_convt_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout,
                              int D, int H, int W, void* scratch, void* stream);
+/* A head -- the conv k1 s1 that writes one of the network's results -- as a plan runs it (Fwd::head; refused where the head kernels do
+ * not take the shape: cout <= 8, cin = 16 * 2^k <= 256).  The source is a view [S][cin] (x, scale, shift, act as for the layer kernels
+ * below), w [cout][cin], b [cout].  Forward: y_cl [S][cout] in the element type and / or y_ncdhw fp32 [cout][S]; either may be NULL, not
+ * both.  Backward, one pass over (source, dy): exactly one of dy_ncdhw (fp32 [cout][S], what unet_backward is given) and dy_cl
+ * ([S][cout], element type) is given; dw [cout][cin] and db [cout] are added to; dx [S][cin] = dL/d(view) is written (acc = 0) or added
+ * to (acc = 1), NULL: not computed.  defer = 1: the kernel leaves its slab rows and the slab sum runs as a launch of its own on the same
+ * stream (a plan runs it on its side stream); the results are the same bits.  scratch: unet_op_scratch_bytes(cin, cout, 1, 1, 1) bytes
+ * cover it for every S (512 slab rows of cin * cout + cout floats). */
+int unet_op_head_fwd(int dtype, const void* x, int cin, const float* scale, const float* shift, int act, const float* w, const float* b,
+                     void* y_cl, float* y_ncdhw, int cout, int64_t S, void* stream);
+int unet_op_head_bwd(int dtype, const void* x, int cin, const float* scale, const float* shift, int act, const float* dy_ncdhw,
+                     const void* dy_cl, const float* w, void* dx, int acc, float* dw, float* db, int cout, int64_t S, int defer,
+                     void* scratch, void* stream);
 /* layout helpers: fp32 NCDHW <-> channels-last element type */
 int unet_op_pack_ndhwc(int dtype, const float* x_ncdhw, void* y_ndhwc, int C, int64_t S, void* stream);
 int unet_op_unpack_ncdhw(int dtype, const void* x_ndhwc, float* y_ncdhw, int C, int64_t S, void* stream);

@@ -138,6 +138,47 @@ def fused_reference(case, seed=0):
     return _frozen(x=d["x"], w=d["w"], b=d["b"], scale=scale, shift=shift, xa=xa, y=oracle_forward(case, xa, d["w"], d["b"]))
 
 
+def merged(case2):
+    """(c0, c1, cout, dims, ks, stride) -> the case of c0 + c1 input channels the oracle computes: the concatenation of two ternary
+    tensors is a ternary tensor, so its results are the two-source layer's and the test only splits them"""
+    c0, c1, cout, dims, ks, st = case2
+    return (c0 + c1, cout, dims, ks, st)
+
+
+@functools.lru_cache(maxsize=None)
+def old_gradient(case, seed=0):
+    """what an accumulating dgrad adds to: integers in [-2, 2], [Cin, D, H, W]"""
+    a = _rng(case, seed + 2000).integers(-2, 3, (case[0], *case[2])).astype(np.float32)
+    a.flags.writeable = False
+    return a
+
+
+def check_accumulate_precondition(ref, old, dt, what=""):
+    """on the reference alone: dx + old is integral and, for the bf16 engine, within the bf16 bound"""
+    a = np.asarray(ref.dx, np.float64) + np.asarray(old, np.float64)
+    bound = BF16_EXACT if dt == "bf16" else F32_EXACT - 1
+    assert np.all(a == np.rint(a)), "%s dx + old: not integral" % what
+    assert np.abs(a).max() <= bound, "%s dx + old: max %g exceeds %g (halve pw for this case in PW_FACTOR)" % (what, np.abs(a).max(), bound)
+
+
+@functools.lru_cache(maxsize=None)
+def head_reference(cin, cout, S, seed=0, plain=False):
+    """exact data for a head: the 1x1x1 conv reads xa = relu(x * scale + shift) (scale in {-1, 1}, shift in {-1, 0, 1}: xa in {0, 1, 2});
+    y, dx = dL/d(view), dw0 + dL/dw and db0 + dL/db by the oracle's 1x1x1 conv on xa; old: what an accumulating dx starts from.
+    plain: the source is read as it is (scale and shift None, xa = x).  Arrays are [C, S, 1, 1]"""
+    case = (cin, cout, (S, 1, 1), 1, 1)
+    d = exact_data(case, seed)
+    rng = _rng(case, seed + 1000)
+    scale = (rng.integers(0, 2, (cin,)) * 2 - 1).astype(np.float32)
+    shift = rng.integers(-1, 2, (cin,)).astype(np.float32)
+    xa = np.maximum(d["x"] * scale[:, None, None, None] + shift[:, None, None, None], 0.0).astype(np.float32)
+    if plain:
+        scale, shift, xa = None, None, d["x"]
+    dw, db = oracle_wgrad(case, xa, d["dy"], d["dw0"], d["db0"])
+    return _frozen(scale=scale, shift=shift, xa=xa, y=oracle_forward(case, xa, d["w"], d["b"]), dx=oracle_dgrad(case, d["dy"], d["w"]),
+                   dw=dw, db=db, old=old_gradient(case, seed), **d)
+
+
 def check_preconditions(ref, dt, what=""):
     """on the reference alone: every value an integer; bf16 engine: max|y|, max|dx| <= 256; fp32 engine: below 2^24; dw / db (fp32
     in both engines): below 2^24"""
@@ -224,6 +265,32 @@ class Guarded:
             nf = torch.nonzero(~torch.isfinite(self.t.float()).flatten()).flatten()
             assert nf.numel() == 0, "%s: %d of %d elements were left NaN / not finite (first at flat index %d, shape %s)" % (
                 what, nf.numel(), self.t.numel(), int(nf[0]), tuple(self.t.shape))
+
+
+class Fenced:
+    """a read-only source inside a larger allocation whose other elements are NaN (`pad` elements on each side, a multiple of 128 so that
+    the view keeps 256-byte alignment): a kernel that reads past either end of the source poisons its result"""
+
+    def __init__(self, t, pad=2048):
+        assert pad % 128 == 0
+        self.raw = torch.full((t.numel() + 2 * pad,), float("nan"), dtype=t.dtype, device=DEV)
+        self.t = self.raw[pad:pad + t.numel()].view(t.shape)
+        self.t.copy_(t)
+        assert self.t.data_ptr() % 256 == 0
+
+    def data_ptr(self):
+        return self.t.data_ptr()
+
+
+def adjacent(t0, t1):
+    """t0 and t1 in ONE allocation, t1 at the next 256-byte boundary behind t0 (as a workspace lays two tensors out) -> the two views"""
+    es = t0.element_size()
+    off = (t0.numel() * es + 255) // 256 * 256 // es
+    raw = torch.zeros((off + t1.numel(),), dtype=t0.dtype, device=DEV)
+    a, b = raw[:t0.numel()].view(t0.shape), raw[off:off + t1.numel()].view(t1.shape)
+    a.copy_(t0)
+    b.copy_(t1)
+    return a, b
 
 
 def poisoned_scratch(cin, cout, D=1, H=1, W=1):

@@ -24,7 +24,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_case_lists_are_the_sections_in_order():
     assert len(CC.CONV_CASES) == 74 and len(set(CC.CONV_CASES)) == 74
     assert len(CC.CONVT_CASES) == 25 and len(set(CC.CONVT_CASES)) == 25
-    for sec in CC.CONV_SECTIONS + CC.CONVT_SECTIONS:
+    assert len(CC.CONV2_CASES) == 28 and len(set(CC.CONV2_CASES)) == 28
+    assert all(len(c) == 6 and c[0] > 0 and c[1] > 0 for c in CC.CONV2_CASES)
+    for sec in CC.CONV_SECTIONS + CC.CONVT_SECTIONS + CC.CONV2_SECTIONS:
         assert set(sec.other) <= set(sec.cases), sec.name
         for d, fam in list(sec.expect.items()) + [kv for o in sec.other.values() for kv in o.items()]:
             assert fam in CC.FAMILIES[d], (sec.name, d, fam)
@@ -141,3 +143,146 @@ def test_bitwise_comparison_rejects_what_the_relative_bound_accepts(case):
         for name, e in errs.items():
             if (case, name) in REL_ACCEPTS:
                 assert 0 < e < 1e-2, "%s: %g" % (name, e)
+
+
+# ---- two sources, split and accumulated destinations, heads ----
+@pytest.mark.parametrize("case2", CC.CONV2_CASES)
+def test_exact_preconditions_two_sources(case2):
+    """the merged case holds every precondition of the one-source recipe, and so does dx + old for the accumulating destinations
+    (integers in [-2, 2]); both halves of the split tensors carry data"""
+    case = X.merged(case2)
+    ref, old = X.reference(case), X.old_gradient(case)
+    for dt in ("bf16", "fp32"):
+        X.check_preconditions(ref, dt, str(case2))
+        X.check_accumulate_precondition(ref, old, dt, str(case2))
+    assert np.all(old == np.rint(old)) and np.abs(old).max() == 2 and old.shape == ref.dx.shape
+    c0 = case2[0]
+    for part in (slice(0, c0), slice(c0, None)):
+        assert np.count_nonzero(ref.x[part]) > 0.5 * ref.x[part].size and np.count_nonzero(ref.dx[part]) > 0.5 * ref.dx[part].size
+        assert np.count_nonzero(ref.dw[:, part] - ref.dw0[:, part]) > 0
+    assert np.count_nonzero(ref.y) > 0.5 * ref.y.size
+
+
+@pytest.mark.parametrize("case", CC.CONVT_ACC_CASES)
+def test_exact_preconditions_convt_accumulate(case):
+    ref, old = X.reference(case), X.old_gradient(case)
+    for dt in ("bf16", "fp32"):
+        X.check_preconditions(ref, dt, str(case))
+        X.check_accumulate_precondition(ref, old, dt, str(case))
+    assert np.count_nonzero(ref.dx) > 0.5 * ref.dx.size and np.count_nonzero(old) > 0.5 * old.size
+
+
+@pytest.mark.parametrize("cin", CC.HEAD_CIN)
+def test_exact_preconditions_heads(cin):
+    for cout in CC.HEAD_COUT:
+        for S in CC.HEAD_VOXELS:
+            r = X.head_reference(cin, cout, S)
+            what = "head %d -> %d, %d voxels" % (cin, cout, S)
+            for dt in ("bf16", "fp32"):
+                X.check_preconditions(r, dt, what)
+                X.check_accumulate_precondition(r, r.old, dt, what)
+            assert r.xa.min() >= 0 and r.xa.max() <= 2 and np.all(r.xa == np.rint(r.xa))
+            assert set(np.unique(r.scale)) <= {-1.0, 1.0} and set(np.unique(r.shift)) <= {-1.0, 0.0, 1.0}
+            if S >= 63:     # (a channel with shift -1 is dead under the relu: a third of dw's columns stay at their start values)
+                assert np.count_nonzero(r.y) > 0.5 * r.y.size and np.count_nonzero(r.dw - r.dw0) > 0.25 * r.dw.size
+                assert np.count_nonzero(r.dx) > 0.25 * r.dx.size
+
+
+@pytest.mark.parametrize("case,plain", [(c, False) for c in CC.HEAD_CAP_CASES] + [(c, True) for c in CC.HEAD_PLAIN_CASES])
+def test_exact_preconditions_heads_past_the_caps_and_plain(case, plain):
+    """the same preconditions where a thread sums many voxels (dw / db are sums over up to 530001 voxels: integers far below 2^24 in
+    any order) and on a plain source; the cap cases exceed both block caps of the launchers with a ragged last pass"""
+    cin, cout, S = case
+    r = X.head_reference(cin, cout, S, plain=plain)
+    what = "head %d -> %d, %d voxels" % (cin, cout, S)
+    for dt in ("bf16", "fp32"):
+        X.check_preconditions(r, dt, what)
+        X.check_accumulate_precondition(r, r.old, dt, what)
+    assert np.count_nonzero(r.y) > 0.5 * r.y.size and np.count_nonzero(r.dx) > 0.25 * r.dx.size
+    if plain:
+        assert r.scale is None and r.shift is None and r.xa is r.x
+        assert np.count_nonzero(r.dw - r.dw0) > 0.5 * r.dw.size     # no dead channel: every column of dw moves
+    else:
+        nchunk = cin // 16
+        assert S * nchunk > 512 * 256 and (S + 63) // 64 * 64 * nchunk > 2048 * 256          # launch_head_bwd / launch_head_fwd
+        assert S % (512 * 256 // nchunk) and S % (2048 * 256 // nchunk) and S % 64
+        assert 2 * S + 4 < X.F32_EXACT      # the largest |partial sum| of dw (xa <= 2, |dy| <= 1) and db
+
+
+def boundary_chunk_swapped(x, c0):
+    """what a conv reads when the 16 channels on either side of the source boundary come from the other source"""
+    out = x.copy()
+    out[c0 - 16:c0], out[c0:c0 + 16] = x[c0:c0 + 16], x[c0 - 16:c0]
+    return out
+
+
+def boundary_moved(x, c0):
+    """what a conv reads when it tests `c >= c0 + 16` for the source and still offsets source 1 by c0: channels [c0, c0 + 16) come from
+    source 0, whose voxel rows are c0 wide -- the first 16 channels of its NEXT voxel (zero behind the last one)"""
+    x0 = np.transpose(x[:c0], (1, 2, 3, 0)).reshape(-1, c0)
+    nxt = np.concatenate([x0[1:], np.zeros((1, c0), x.dtype)])[:, :16]
+    out = x.copy()
+    out[c0:c0 + 16] = nxt.T.reshape(16, *x.shape[1:])
+    return out
+
+
+def at_one_voxel(y, x_wrong, x, w):
+    """the last output voxel (every output channel) with the centre tap's products taken from x_wrong"""
+    out = y.copy()
+    v = tuple(s - 1 for s in y.shape[1:])
+    wc = w[:, :, 1, 1, 1].astype(np.float64)
+    out[(slice(None),) + v] += (wc @ (x_wrong[(slice(None),) + v].astype(np.float64) - x[(slice(None),) + v])).astype(np.float32)
+    return out
+
+
+TEETH2_CASES = [(240, 272, 32, (5, 6, 7), 3, 1), (16, 48, 32, (5, 6, 7), 3, 1), (16, 16, 16, (9, 9, 19), 3, 1)]
+
+
+@pytest.mark.parametrize("case2", TEETH2_CASES)
+def test_bitwise_comparison_rejects_wrong_sources_and_destinations(case2):
+    """assert_exact must reject: the two sources swapped and the source boundary moved by 16 channels, each over the whole volume; the
+    same two confined to the centre tap of one output voxel (one tile edge), where the swap is the smaller one a kernel can make
+    there -- the 16 channels on either side of the boundary exchanged, boundary_chunk_swapped, NOT the two whole sources; an
+    accumulating destination whose old value was ignored or added twice; and the first 16-channel row tile of d1 written into d0's
+    position.
+
+    At c0 + c1 >= 128 the two confined source mutations, on the random data of the random-data tests (N(0,1) activations rounded
+    to bf16, 0.2 N(0,1) filters), must stay under the bound that covers the two-source layers in test_gpu_parity.py.  That is the
+    NETWORK bound, 8e-2 of a tensor's maximum for bf16 logits and gradients, not the 1e-2 of that file's op tests (which the teeth test
+    above uses and which would see both mutants): no op test there runs two sources.  Expected from the data's scale
+    at Cin = 512: 32 (16) wrong channels of one tap give an error of sigma = 0.2 sqrt(2 * 32) = 1.6 (1.1) per output channel, about 2.5
+    sigma at the worst of 32, against max|y| of about 3.5 * 0.2 sqrt(27 * 512) = 82: 5e-2 and 3.5e-2.  The figures are printed."""
+    import torch
+    assert case2 in CC.CONV2_CASES
+    c0, c1 = case2[:2]
+    case = X.merged(case2)
+    ref, old = X.reference(case), X.old_gradient(case)
+    everywhere = {"sources swapped": X.oracle_forward(case, np.concatenate([ref.x[c0:], ref.x[:c0]]), ref.w, ref.b),
+                  "boundary moved": X.oracle_forward(case, boundary_moved(ref.x, c0), ref.w, ref.b)}
+    confined = {"16 channels on either side of the boundary exchanged at one voxel": at_one_voxel(ref.y, boundary_chunk_swapped(ref.x, c0), ref.x, ref.w),
+                "boundary moved at one voxel": at_one_voxel(ref.y, boundary_moved(ref.x, c0), ref.x, ref.w)}
+    for name, wrong in list(everywhere.items()) + list(confined.items()):
+        assert wrong.shape == ref.y.shape and not np.array_equal(wrong, ref.y), name
+        with pytest.raises(AssertionError, match="differ bitwise"):
+            X.assert_exact(wrong, ref.y, name)
+        with pytest.raises(AssertionError, match="differ bitwise"):
+            X.assert_exact(torch.from_numpy(wrong).to(torch.bfloat16), ref.y, name)
+    # destinations
+    d0, d1 = ref.dx[:c0] + old[:c0], ref.dx[c0:]
+    X.assert_exact(d0.copy(), ref.dx[:c0] + old[:c0], "unchanged")
+    wrong0 = {"accumulate ignored": ref.dx[:c0], "old value added twice": ref.dx[:c0] + 2 * old[:c0]}
+    tile = d0.copy()
+    tile[:16] = d1[:16]
+    wrong0["a row tile of d1 in d0's position"] = tile
+    for name, wrong in wrong0.items():
+        for cast in (lambda a: a, lambda a: torch.from_numpy(np.array(a)).to(torch.bfloat16)):
+            with pytest.raises(AssertionError, match="differ bitwise"):
+                X.assert_exact(cast(wrong), d0, name)
+    if c0 + c1 >= 128:
+        x, w, b = real_data(case)
+        y = X.oracle_forward(case, x, w, b)
+        errs = {"16 channels on either side of the boundary exchanged at one voxel": rel(at_one_voxel(y, boundary_chunk_swapped(x, c0), x, w), y),
+                "boundary moved at one voxel": rel(at_one_voxel(y, boundary_moved(x, c0), x, w), y)}
+        print("relative error of the confined mutants on random data, %s: %s (op tests: 1e-2, network tests: 8e-2)" % (case2, errs))
+        for name, e in errs.items():
+            assert 0 < e < 8e-2, "%s: %g" % (name, e)

@@ -1,6 +1,6 @@
 """GPU (-m gpu): a conv and the norm layer next to it, per layer, against a float64 reference of the same layer.
 
-unet_op_conv3d_fwd_norm and unet_op_conv3d_bwd_data_norm (include/unet_hip.h) launch the conv through the functions the executor
+unet_op_conv3d_fwd_norm and unet_op_conv3d_bwd_data_norm (and its sibling with a stride, _strided; include/unet_hip.h) launch the conv through the functions the executor
 launches it through (conv_fwd, conv_dgrad in csrc/engine.cpp) and the norm's own launches through norm_fwd_passes / norm_bwd_passes: on the
 deep levels one split-K launch of kernels_mfma_deep.hip with the norm in the epilogue of the block that draws the last ticket
 (DEEP_FWD_NORM: conv, statistics, running statistics, activated copy; DEEP_BWD_NORM: dgrad, the norm's backward sums, coef,
@@ -316,7 +316,7 @@ def test_conv_norm_forward_against_fp64(case):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # backward: dgrad into the view of a norm layer's tensor u, then that norm's backward
-# (transposed, cin = channels of u / dx, cout = channels of dy, (D, H, W) of u, act, accumulate, norm)
+# (kind: 0 conv k3 s1, 1 conv_trans k2 s2, 2 conv k3 s2; cin = channels of u / dx, cout = channels of dy, (D, H, W) of u, act, accumulate, norm)
 BWD_CASES = [
     # <1,3,1> DEEP_BWD_NORM: conv k3 s1, <= 64 voxels
     (0, 16, 32, (3, 4, 5), 2, 0, "in"),
@@ -334,15 +334,30 @@ BWD_CASES = [
     (0, 32, 32, (8, 8, 8), 2, 0, "in"),
     (0, 64, 64, (16, 16, 16), 1, 1, "bn"),
     (1, 32, 32, (8, 8, 16), 3, 0, "in"),
+    # conv k3 s2 (unet_op_conv3d_bwd_data_norm_strided), the dgrad that writes a skip tensor's gradient last.  k_s2_scatter with the
+    # statistics rows (coarse grid >= 16 wide, >= 4 deep, 32 or 64 dy channels), written <0,KS,false,true> and accumulated
+    # <0,KS,true,true>: KS 2 on the smallest coarse grid it serves, (4, 4, 16) -- 256 voxels, which mfma_dgrad gives to the split-K
+    # scatter kind first: k_s2_scatter runs these two in the UNET_NO_DEEP_KERNELS rerun -- and on (5, 6, 18); KS 1 from odd fine extents
+    (2, 32, 64, (8, 8, 32), 2, 0, "in"),
+    (2, 32, 64, (8, 8, 32), 1, 1, "bn"),
+    (2, 32, 64, (10, 12, 36), 2, 1, "in"),
+    (2, 16, 32, (9, 13, 35), 3, 0, "bn"),
+    (2, 16, 32, (9, 13, 35), 2, 1, "in"),
+    # coarse grid (9, 10, 11): too narrow for k_s2_scatter, above the split-K kernel's 512 voxels -> the halo-tile scatter kind
+    # (k_mfma_conv_p<1,2,0,..,true>) and the norm's separate launches
+    (2, 16, 32, (17, 19, 21), 2, 1, "in"),
+    # coarse grid (4, 5, 6): the split-K scatter kind k_deep_conv<1,2,0,true,DEEP_PLAIN> (a scattering kind has no norm epilogue:
+    # deep_dgrad_outcome), then the norm's separate launches.  (<2,2,0,false,DEEP_BWD_NORM> is the conv_trans kind: the cases above)
+    (2, 16, 32, (7, 9, 11), 1, 0, "bn"),
 ]
 
 
 def bwd_inputs(case):
     tr, cin, cout, (D, H, W), a, acc, norm = case
     seed = 1000 + cin * 7 + cout * 13 + D * 17 + H * 19 + W * 23 + tr
-    fine = (2 * D, 2 * H, 2 * W) if tr else (D, H, W)
+    fine = {0: (D, H, W), 1: (2 * D, 2 * H, 2 * W), 2: ((D - 1) // 2 + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1)}[tr]   # the grid of dy
     dy = grid((*fine, cout), seed + 1, 1 / 8)
-    w = grid((cin, cout, 2, 2, 2) if tr else (cout, cin, 3, 3, 3), seed + 2, 1 / 16)
+    w = grid((cin, cout, 2, 2, 2) if tr == 1 else (cout, cin, 3, 3, 3), seed + 2, 1 / 16)
     u = bf(rnd((D, H, W, cin), seed + 3, 1.0, 0.3))
     old = grid((D, H, W, cin), seed + 4, 1 / 128, 256) if acc else np.zeros((D, H, W, cin))
     gamma = rnd((cin,), seed + 5, 0.2, 1.0).astype(np.float32).astype(np.float64)
@@ -351,10 +366,12 @@ def bwd_inputs(case):
     return dy, w, u, old, gamma, beta
 
 
-def dgrad64(tr, dy, w):
+def dgrad64(tr, dy, w, dims=None):
     d = torch.from_numpy(dy).permute(3, 0, 1, 2)[None]
-    if tr:
+    if tr == 1:
         g = torch.nn.functional.conv3d(d, torch.from_numpy(w), stride=2)
+    elif tr == 2:   # onto the fine grid `dims`: an even extent has one more voxel than 2 * coarse - 1
+        g = torch.nn.functional.conv_transpose3d(d, torch.from_numpy(w), stride=2, padding=1, output_padding=[1 - s % 2 for s in dims])
     else:
         g = torch.nn.functional.conv_transpose3d(d, torch.from_numpy(w), padding=1)
     return g[0].permute(1, 2, 3, 0).numpy()
@@ -395,9 +412,14 @@ def run_bwd(case, dy, w, u, old, stat, gamma):
         coef = nan_like(torch.empty((3 * cin,), dtype=torch.float32, device=DEV))
         dgam = torch.ones((cin,), dtype=torch.float32, device=DEV)
         dbet = torch.ones((cin,), dtype=torch.float32, device=DEV)
-        E.check(E.lib.unet_op_conv3d_bwd_data_norm(tr, dyd.data_ptr(), wd.data_ptr(), dx.data_ptr(), acc, ud.data_ptr(), sd.data_ptr(),
-                                                   gd.data_ptr(), a, coef.data_ptr(), dgam.data_ptr(), dbet.data_ptr(), cin, cout, D, H, W,
-                                                   sc.data_ptr(), stream()))
+        if tr == 2:
+            E.check(E.lib.unet_op_conv3d_bwd_data_norm_strided(0, 2, dyd.data_ptr(), wd.data_ptr(), dx.data_ptr(), acc, ud.data_ptr(),
+                                                               sd.data_ptr(), gd.data_ptr(), a, coef.data_ptr(), dgam.data_ptr(),
+                                                               dbet.data_ptr(), cin, cout, D, H, W, sc.data_ptr(), stream()))
+        else:
+            E.check(E.lib.unet_op_conv3d_bwd_data_norm(tr, dyd.data_ptr(), wd.data_ptr(), dx.data_ptr(), acc, ud.data_ptr(), sd.data_ptr(),
+                                                       gd.data_ptr(), a, coef.data_ptr(), dgam.data_ptr(), dbet.data_ptr(), cin, cout, D, H, W,
+                                                       sc.data_ptr(), stream()))
         torch.cuda.synchronize()
         outs.append({"dx": dx, "coef": coef, "dgamma": dgam, "dbeta": dbet})
     for k in outs[0]:
@@ -405,7 +427,7 @@ def run_bwd(case, dy, w, u, old, stat, gamma):
     return {k: v.float().cpu().numpy().astype(np.float64) for k, v in outs[0].items()}
 
 
-@pytest.mark.parametrize("case", BWD_CASES, ids=lambda c: "%s_%dx%d_%dx%dx%d_act%d_acc%d_%s" % ("convt" if c[0] else "conv", c[1], c[2], *c[3],
+@pytest.mark.parametrize("case", BWD_CASES, ids=lambda c: "%s_%dx%d_%dx%dx%d_act%d_acc%d_%s" % (("conv", "convt", "convs2")[c[0]], c[1], c[2], *c[3],
                                                                                              c[4], c[5], c[6]))
 def test_dgrad_norm_backward_against_fp64(case):
     tr, cin, cout, (D, H, W), a, acc, norm = case
@@ -420,7 +442,7 @@ def test_dgrad_norm_backward_against_fp64(case):
     stat = np.concatenate([mean, rstd, scale, beta - mean * scale]).astype(np.float32).astype(np.float64)
     got = run_bwd(case, dy, w, u, old, stat, gamma)
 
-    gview = bf(dgrad64(tr, dy, w) + old).reshape(V, cin)       # the one rounding before dv: dL/d(view) = bf16(dgrad + old)
+    gview = bf(dgrad64(tr, dy, w, (D, H, W)) + old).reshape(V, cin)       # the one rounding before dv: dL/d(view) = bf16(dgrad + old)
     R = norm_bwd64(gview, uf, gamma, beta, eps, a)
     if a in (1, 2):      # no pre-activation so close to the kink that the kernel's fp32 fma could take the other side of it
         st4 = stat.reshape(4, cin)
@@ -450,11 +472,11 @@ def test_dgrad_norm_backward_against_fp64(case):
     def ratio(wr):
         return max(miss(wr[k], refq[k], bounds[k]) for k in ("du", "m1", "m2", "dgamma", "dbeta"))
     wl = w.copy()
-    if tr:
+    if tr == 1:
         wl[:, 0:32, 0, 0, 0] = 0.0
     else:
         wl[0:32, :, 1, 1, 1] = 0.0
-    gl = bf(dgrad64(tr, dy, wl) + old).reshape(V, cin)
+    gl = bf(dgrad64(tr, dy, wl, (D, H, W)) + old).reshape(V, cin)
     teeth("a lost K range", ratio(bwd_closed(gl * R["ad"], xh, R["c0"], V)))
     if cin > 16:
         p = (np.arange(cin) + 16) % cin

@@ -27,6 +27,36 @@ def test_library_exports_every_declared_symbol():
         assert declared == set(exports)
 
 
+def _ctype_kind(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or hasattr(t, "contents"):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t", ctypes.c_float: "float",
+            ctypes.c_double: "double"}[t]
+
+
+def _c_kind(arg):
+    if "*" in arg or "[" in arg:
+        return "pointer"
+    words = [w for w in re.findall(r"[A-Za-z_][A-Za-z0-9_]*", arg) if w != "const"]
+    assert len(words) == 2 and words[0] in ("int", "int64_t", "size_t", "float", "double"), arg
+    return words[0]
+
+
+def test_ctypes_signatures_match_the_header():
+    """every argument list of include/unet_hip.h against the argtypes the binding sets, kind by kind (pointer, int, int64_t, size_t,
+    float, double): a transposed int / pointer pair, or a missing argument, would otherwise show only as a wrong result on the device"""
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(os.path.join(ROOT, "include", "unet_hip.h")).read(), flags=re.S)
+    decls = re.findall(r"\b(unet_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert {n for n, _ in decls} == set(U.engine.EXPORTS), "a declaration this parser does not read"
+    for name, args in decls:
+        args = [a.strip() for a in args.split(",")]
+        want = [] if args in ([""], ["void"]) else [_c_kind(a) for a in args]
+        fn = getattr(U.engine.lib, name)
+        assert fn.argtypes is not None, name + ": no argtypes"
+        assert [_ctype_kind(t) for t in fn.argtypes] == want, "%s: the binding has %s, the header %s" % (
+            name, [_ctype_kind(t) for t in fn.argtypes], want)
+
+
 def test_plan_matches_reference_parameter_order_default_arch():
     arch = A.default_feature(6)
     p = U.Plan(arch, 1, 6, (128, 128, 128))

@@ -1635,7 +1635,8 @@ int unet_op_scratch_bytes(int cin, int cout, int D, int H, int W, size_t* bytes)
         size_t w = ((size_t)1024 * 1024 + (size_t)1024 * cout) * 4 + 1024;
         if (w > b) b = w;
     }
-    if (cout <= 8 || cin == 1) {   // register-accumulating small wgrads: <= 512 blocks x (weights + bias sums)
+    if (cout <= 8 || cin == 1) {   // register-accumulating small wgrads: <= 512 blocks x (weights + bias sums); covers a head's backward slab
+                                   // (head_bwd_scratch_bytes: the same 512 rows of one tap), which unet_op_head_bwd is given
         size_t w = (size_t)512 * ((size_t)27 * cin * cout + cout) * 4 + 1024;
         if (w > b) b = w;
     }
@@ -1711,37 +1712,54 @@ static FwdRan op_conv_fwd(const ConvChoice& c, bool transposed, int dtype, const
     return conv_fwd(c.fwd, transposed, dtype, g, sd, nsrc, w, wf, wm, b, y, nullptr, part, nf,
                     use_deep && c.mfma_fwd() ? op_deep() : DeepScratch(), s);
 }
-// the input gradient of an entry, into one destination
-static DgradOutcome op_conv_dgrad(Dgrad c, bool transposed, int dtype, const ConvGeom& g, const void* dy, const float* w, const DstGrad& d,
-                                  const DeepNormBwd* nb, float* part, void* scratch, hipStream_t s) {
+// the input gradient of an entry, into the destinations d[0 .. ndst) (one per source of the forward; a null ptr: not wanted)
+static DgradOutcome op_conv_dgrad(Dgrad c, bool transposed, int dtype, const ConvGeom& g, const void* dy, const float* w, const DstGrad* d,
+                                  int ndst, const DeepNormBwd* nb, float* part, void* scratch, hipStream_t s) {
     float *wf, *wd = nullptr;
     const void* wm = nullptr;
     if (c == Dgrad::mfma) wm = op_pack_mfma(w, g, transposed, true, scratch, s);
     else op_pack(w, g.Cin, g.Cout, g.ks * g.ks * g.ks, transposed, scratch, &wf, &wd, s);
-    return conv_dgrad(c, transposed, dtype, g, dy, wm, wd, &d, 1, nb, part, c == Dgrad::mfma ? op_deep() : DeepScratch(), s);
+    return conv_dgrad(c, transposed, dtype, g, dy, wm, wd, d, ndst, nb, part, c == Dgrad::mfma ? op_deep() : DeepScratch(), s);
+}
+// the plain sources of an entry as the op reads them: c0 channels of x0, then c1 of x1 (c1 = 0: one source); returns their number
+static int op_sources(const char* who, SrcDesc sd[2], const void* x0, int c0, const void* x1, int c1) {
+    if (c0 < 1 || c1 < 0) throw std::runtime_error(std::string(who) + ": c0 must be positive and c1 not negative");
+    sd[0].ptr = x0; sd[0].C = c0;
+    if (c1) { sd[1].ptr = x1; sd[1].C = c1; }
+    return c1 ? 2 : 1;
 }
 
-// what the entry points below ask choose_conv for one plain source of cin channels, as integers; launches nothing
-int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]) {
+// what the entry points below ask choose_conv for the plain sources of c0 (+ c1) channels, as integers; launches nothing
+int unet_op_conv_choice2(int dtype, int impl, int c0, int c1, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]) {
     try {
         if (!out) throw std::runtime_error("unet_op_conv_choice: null output");
-        if (cin < 1 || cout < 1 || D < 1 || H < 1 || W < 1) throw std::runtime_error("unet_op_conv_choice: sizes must be positive");
+        if (c0 < 1 || c1 < 0 || cout < 1 || D < 1 || H < 1 || W < 1) throw std::runtime_error("unet_op_conv_choice: sizes must be positive");
+        const int cin = c0 + c1;
         const ConvGeom g = transposed ? op_geom(cin, cout, D, H, W, 2, 2, true) : op_geom(cin, cout, D, H, W, ks, stride, false);
-        SrcDesc sd; sd.C = cin;
-        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, transposed != 0);
+        SrcDesc sd[2];
+        const int nsrc = op_sources("unet_op_conv_choice", sd, nullptr, c0, nullptr, c1);
+        const ConvChoice c = choose_conv(dtype, impl, g, sd, nsrc, false, transposed != 0);
         out[0] = (int)c.fwd; out[1] = (int)c.dgrad; out[2] = (int)c.wgrad;
         return 0;
     } catch (const std::exception& e) { return fail(e.what()); }
 }
+int unet_op_conv_choice(int dtype, int impl, int cin, int cout, int D, int H, int W, int ks, int stride, int transposed, int out[3]) {
+    return unet_op_conv_choice2(dtype, impl, cin, 0, cout, D, H, W, ks, stride, transposed, out);
+}
 
+int unet_op_conv3d_fwd2(int dtype, int impl, const void* x0, int c0, const void* x1, int c1, const float* w, const float* b, void* y,
+                        int cout, int D, int H, int W, int ks, int stride, void* scratch, void* stream) {
+    OP_TRY({
+        SrcDesc sd[2];
+        const int nsrc = op_sources("unet_op_conv3d_fwd2", sd, x0, c0, x1, c1);
+        ConvGeom g = op_geom(c0 + c1, cout, D, H, W, ks, stride, false);
+        const ConvChoice c = choose_conv(dtype, impl, g, sd, nsrc, false, false);
+        op_conv_fwd(c, false, dtype, g, sd, nsrc, w, b, y, nullptr, nullptr, true, scratch, (hipStream_t)stream);
+    })
+}
 int unet_op_conv3d_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D, int H,
                        int W, int ks, int stride, void* scratch, void* stream) {
-    OP_TRY({
-        ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
-        SrcDesc sd; sd.ptr = x; sd.C = cin;
-        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
-        op_conv_fwd(c, false, dtype, g, &sd, 1, w, b, y, nullptr, nullptr, true, scratch, (hipStream_t)stream);
-    })
+    return unet_op_conv3d_fwd2(dtype, impl, x, cin, nullptr, 0, w, b, y, cout, D, H, W, ks, stride, scratch, stream);
 }
 int unet_op_conv3d_fwd_fused(int dtype, int impl, const void* x, const float* scale, const float* shift, int act, const float* w,
                              const float* b, void* y, float* stats, int cin, int cout, int D, int H, int W, int ks, int stride,
@@ -1783,15 +1801,27 @@ int unet_op_conv3d_fwd_packed(int dtype, const void* x, const void* wpacked, con
         launch_mfma_conv_fwd(g, &sd, 1, wpacked, b, y, stats_partials, (hipStream_t)stream);
     })
 }
+// The input gradient as the executor runs it for a layer with one or two sources: a destination per source, written or added to, a
+// null one skipped (that source needs no gradient).
+int unet_op_conv3d_bwd_data2(int dtype, int impl, int transposed, const void* dy, const float* w, void* d0, int c0, int acc0, void* d1,
+                             int c1, int acc1, int cout, int D, int H, int W, int ks, int stride, void* scratch, void* stream) {
+    OP_TRY({
+        const bool tr = transposed != 0;
+        if (tr && c1) throw std::runtime_error("unet_op_conv3d_bwd_data2: a conv_trans has one source");
+        SrcDesc sd[2];
+        const int nsrc = op_sources("unet_op_conv3d_bwd_data2", sd, nullptr, c0, nullptr, c1);
+        if (!d0 && !(nsrc > 1 && d1)) throw std::runtime_error("unet_op_conv3d_bwd_data2: no destination");
+        ConvGeom g = tr ? op_geom(c0, cout, D, H, W, 2, 2, true) : op_geom(c0 + c1, cout, D, H, W, ks, stride, false);
+        DstGrad d[2];
+        d[0].ptr = d0; d[0].C = c0; d[0].accumulate = acc0 ? 1 : 0;
+        if (nsrc > 1) { d[1].ptr = d1; d[1].C = c1; d[1].accumulate = acc1 ? 1 : 0; }
+        const ConvChoice c = choose_conv(dtype, impl, g, sd, nsrc, false, tr);
+        op_conv_dgrad(c.dgrad, tr, dtype, g, dy, w, d, nsrc, nullptr, nullptr, scratch, (hipStream_t)stream);
+    })
+}
 int unet_op_conv3d_bwd_data(int dtype, int impl, const void* dy, const float* w, void* dx, int cin, int cout, int D, int H, int W,
                             int ks, int stride, void* scratch, void* stream) {
-    OP_TRY({
-        ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
-        DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = 0;
-        SrcDesc sd; sd.C = cin;
-        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
-        op_conv_dgrad(c.dgrad, false, dtype, g, dy, w, d, nullptr, nullptr, scratch, (hipStream_t)stream);
-    })
+    return unet_op_conv3d_bwd_data2(dtype, impl, 0, dy, w, dx, cin, 0, nullptr, 0, 0, cout, D, H, W, ks, stride, scratch, stream);
 }
 // A conv k3 and the norm + activation behind it, bf16, as the executor runs that layer (conv_fwd): on the deep levels the split-K kernel
 // with the norm in its epilogue (DEEP_FWD_NORM), else the MFMA conv with its statistics rows and the norm's separate launches.
@@ -1819,32 +1849,44 @@ int unet_op_conv3d_fwd_norm(const void* x0, const void* x1, int cin0, int cin1, 
 // The dgrad of a conv k3 s1 (or of a conv_trans k2 s2: transposed) into the view of a norm layer's tensor u, then that norm's backward
 // as the executor runs it (conv_dgrad): on the deep levels in the split-K kernel's epilogue (DEEP_BWD_NORM), else the dgrad (with the
 // statistics epilogue where the kernel has one) and the norm's separate backward launches.
-int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w, void* dx, int accumulate, const void* u, const float* stat,
-                                 const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin, int cout, int D, int H,
-                                 int W, void* scratch, void* stream) {
+int unet_op_conv3d_bwd_data_norm_strided(int transposed, int stride, const void* dy, const float* w, void* dx, int accumulate, const void* u,
+                                         const float* stat, const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin,
+                                         int cout, int D, int H, int W, void* scratch, void* stream) {
     OP_TRY({
         hipStream_t s = (hipStream_t)stream;
-        ConvGeom g = op_geom(cin, cout, D, H, W, transposed ? 2 : 3, transposed ? 2 : 1, transposed != 0);
+        if (!transposed && stride != 1 && stride != 2) throw std::runtime_error("unet_op_conv3d_bwd_data_norm: stride must be 1 or 2");
+        ConvGeom g = op_geom(cin, cout, D, H, W, transposed ? 2 : 3, transposed ? 2 : stride, transposed != 0);
         SrcDesc sd; sd.C = cin;
         const ConvChoice c = choose_conv(UNET_DTYPE_BF16, UNET_IMPL_AUTO, g, &sd, 1, false, transposed != 0);
         if (c.dgrad != Dgrad::mfma) throw std::runtime_error("unet_op_conv3d_bwd_data_norm: shape not covered by the MFMA kernels");
         float* part = (float*)((char*)scratch + OpScratch(cin, cout).partials);
         DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = accumulate ? 1 : 0;
         const DeepNormBwd nb = {u, stat, gamma, coef, dgamma, dbeta, act};
-        const DgradOutcome o = op_conv_dgrad(c.dgrad, transposed != 0, UNET_DTYPE_BF16, g, dy, w, d, &nb, part, scratch, s);
+        const DgradOutcome o = op_conv_dgrad(c.dgrad, transposed != 0, UNET_DTYPE_BF16, g, dy, w, &d, 1, &nb, part, scratch, s);
         if (!o.norm_done) norm_bwd_passes(UNET_DTYPE_BF16, dx, u, cin, (int64_t)D * H * W, stat, act, gamma, coef, dgamma, dbeta, part, o.rows, false, s);
+    })
+}
+int unet_op_conv3d_bwd_data_norm(int transposed, const void* dy, const float* w, void* dx, int accumulate, const void* u, const float* stat,
+                                 const float* gamma, int act, float* coef, float* dgamma, float* dbeta, int cin, int cout, int D, int H,
+                                 int W, void* scratch, void* stream) {
+    return unet_op_conv3d_bwd_data_norm_strided(transposed, 1, dy, w, dx, accumulate, u, stat, gamma, act, coef, dgamma, dbeta, cin, cout, D, H, W,
+                                                scratch, stream);
+}
+int unet_op_conv3d_bwd_weight2(int dtype, int impl, const void* x0, int c0, const void* x1, int c1, const void* dy, float* dw, float* db,
+                               int cout, int D, int H, int W, int ks, int stride, void* scratch, void* stream) {
+    OP_TRY({
+        SrcDesc sd[2];
+        const int nsrc = op_sources("unet_op_conv3d_bwd_weight2", sd, x0, c0, x1, c1);
+        ConvGeom g = op_geom(c0 + c1, cout, D, H, W, ks, stride, false);
+        const ConvChoice c = choose_conv(dtype, impl, g, sd, nsrc, false, false);
+        // (the direct kernel gets no scratch from this surface: one block range, no slab; polite: UNET_OP_POLITE)
+        conv_wgrad(c.wgrad, false, dtype, g, sd, nsrc, dy, dw, db, c.wgrad == Wgrad::direct ? nullptr : scratch, (hipStream_t)stream, false,
+                   env().op_polite ? 1 : 0, nullptr);
     })
 }
 int unet_op_conv3d_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D,
                               int H, int W, int ks, int stride, void* scratch, void* stream) {
-    OP_TRY({
-        ConvGeom g = op_geom(cin, cout, D, H, W, ks, stride, false);
-        SrcDesc sd; sd.ptr = x; sd.C = cin;
-        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, false);
-        // (the direct kernel gets no scratch from this surface: one block range, no slab; polite: UNET_OP_POLITE)
-        conv_wgrad(c.wgrad, false, dtype, g, &sd, 1, dy, dw, db, c.wgrad == Wgrad::direct ? nullptr : scratch, (hipStream_t)stream, false,
-                   env().op_polite ? 1 : 0, nullptr);
-    })
+    return unet_op_conv3d_bwd_weight2(dtype, impl, x, cin, nullptr, 0, dy, dw, db, cout, D, H, W, ks, stride, scratch, stream);
 }
 int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const float* b, void* y, int cin, int cout, int D, int H,
                       int W, void* scratch, void* stream) {
@@ -1857,13 +1899,7 @@ int unet_op_convt_fwd(int dtype, int impl, const void* x, const float* w, const 
 }
 int unet_op_convt_bwd_data(int dtype, int impl, const void* dy, const float* w, void* dx, int cin, int cout, int D, int H, int W,
                            void* scratch, void* stream) {
-    OP_TRY({
-        ConvGeom g = op_geom(cin, cout, D, H, W, 2, 2, true);
-        DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = 0;
-        SrcDesc sd; sd.C = cin;
-        const ConvChoice c = choose_conv(dtype, impl, g, &sd, 1, false, true);
-        op_conv_dgrad(c.dgrad, true, dtype, g, dy, w, d, nullptr, nullptr, scratch, (hipStream_t)stream);
-    })
+    return unet_op_conv3d_bwd_data2(dtype, impl, 1, dy, w, dx, cin, 0, nullptr, 0, 0, cout, D, H, W, 2, 2, scratch, stream);
 }
 int unet_op_convt_bwd_weight(int dtype, int impl, const void* x, const void* dy, float* dw, float* db, int cin, int cout, int D, int H,
                              int W, void* scratch, void* stream) {
@@ -1892,6 +1928,39 @@ static SrcDesc op_view_src(const void* x, int C, const float* scale, const float
     SrcDesc d;
     d.ptr = x; d.C = C; d.scale = scale; d.shift = shift; d.act = act;
     return d;
+}
+// A head (conv k1 s1 that writes one of the network's results) as a plan runs it: Fwd::head of choose_conv, launch_head_fwd / launch_head_bwd
+// (+ launch_head_bwd_reduce) called as conv_fwd and the executor's backward call them.
+static ConvGeom op_head_geom(const char* who, int dtype, int cin, int cout, int64_t S, SrcDesc* sd) {
+    if (dtype != UNET_DTYPE_F32 && dtype != UNET_DTYPE_BF16) throw std::runtime_error(std::string(who) + ": unknown dtype");
+    if (cin < 1 || cout < 1 || S < 1 || S > INT32_MAX) throw std::runtime_error(std::string(who) + ": sizes must be positive (S below 2^31)");
+    const ConvGeom g = op_geom(cin, cout, (int)S, 1, 1, 1, 1, false);
+    if (choose_conv(dtype, UNET_IMPL_AUTO, g, sd, 1, true, false).fwd != Fwd::head)
+        throw std::runtime_error(std::string(who) + ": shape not covered by the head kernels (Cout <= 8, Cin 16 * 2^k <= 256)");
+    return g;
+}
+int unet_op_head_fwd(int dtype, const void* x, int cin, const float* scale, const float* shift, int act, const float* w, const float* b,
+                     void* y_cl, float* y_ncdhw, int cout, int64_t S, void* stream) {
+    OP_TRY({
+        if (!y_cl && !y_ncdhw) throw std::runtime_error("unet_op_head_fwd: no output");
+        SrcDesc sd = op_view_src(x, cin, scale, shift, act);
+        const ConvGeom g = op_head_geom("unet_op_head_fwd", dtype, cin, cout, S, &sd);
+        launch_head_fwd(dtype, g, sd, w, b, y_cl, y_ncdhw, (hipStream_t)stream);
+    })
+}
+int unet_op_head_bwd(int dtype, const void* x, int cin, const float* scale, const float* shift, int act, const float* dy_ncdhw,
+                     const void* dy_cl, const float* w, void* dx, int acc, float* dw, float* db, int cout, int64_t S, int defer,
+                     void* scratch, void* stream) {
+    OP_TRY({
+        hipStream_t s = (hipStream_t)stream;
+        if ((dy_ncdhw != nullptr) == (dy_cl != nullptr)) throw std::runtime_error("unet_op_head_bwd: exactly one form of dy must be given");
+        if (!dw || !db || !scratch) throw std::runtime_error("unet_op_head_bwd: dw, db and scratch must be given");
+        SrcDesc sd = op_view_src(x, cin, scale, shift, act);
+        const ConvGeom g = op_head_geom("unet_op_head_bwd", dtype, cin, cout, S, &sd);
+        DstGrad d; d.ptr = dx; d.C = cin; d.accumulate = acc ? 1 : 0;
+        launch_head_bwd(dtype, g, sd, dy_ncdhw, dy_cl, w, d, dw, db, scratch, s, defer != 0);
+        if (defer) launch_head_bwd_reduce(g, dw, db, scratch, s);
+    })
 }
 static void op_pool_dims(const char* who, int D, int H, int W) {
     // Graph::build refuses a network in which a tensor's extent becomes zero, so no plan pools an extent of 1

@@ -88,6 +88,11 @@ _sig("unet_comm_broadcast", _i, _vp, _vp, C.c_int64, _i, _vp)
 _sig("unet_comm_join", _i, _vp, _vp)
 _sig("unet_op_scratch_bytes", _i, _i, _i, _i, _i, _i, C.POINTER(_sz))
 _sig("unet_op_conv_choice", _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i))
+_sig("unet_op_conv_choice2", _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i))
+_sig("unet_op_conv3d_fwd2", _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp)
+_sig("unet_op_conv3d_bwd_data2", _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp)
+_sig("unet_op_conv3d_bwd_weight2", _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp)
+_sig("unet_op_conv3d_bwd_data_norm_strided", _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp)
 _sig("unet_op_conv3d_fwd", _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp)
 _sig("unet_op_conv3d_pack", _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp)
 _sig("unet_op_conv3d_fwd_packed", _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp)
@@ -109,6 +114,8 @@ _sig("unet_op_norm_bwd", _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64
 _sig("unet_op_norm_choice", _i, _i, _i, _i64, C.POINTER(_i))
 _sig("unet_op_view", _i, _i, *_view, *_view, _vp, _i64, _vp)
 _sig("unet_op_view_bwd", _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _vp)
+_sig("unet_op_head_fwd", _i, _i, *_view, _vp, _vp, _vp, _vp, _i, _i64, _vp)
+_sig("unet_op_head_bwd", _i, _i, *_view, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _vp)
 _sig("unet_op_apply_view", _i, _i, *_view, _vp, _i64, _vp)
 _sig("unet_op_act_bwd", _i, _i, _vp, _vp, _i, _i64, _vp)
 _sig("unet_op_maxpool_fwd", _i, _i, *_view, _vp, _i, _i, _i, _vp)
@@ -129,6 +136,8 @@ EXPORTS = [
     "unet_op_convt_fwd", "unet_op_convt_bwd_data", "unet_op_convt_bwd_weight", "unet_op_pack_ndhwc", "unet_op_unpack_ncdhw",
     "unet_op_norm_fwd", "unet_op_norm_bwd", "unet_op_norm_choice", "unet_op_view", "unet_op_view_bwd", "unet_op_apply_view", "unet_op_act_bwd",
     "unet_op_maxpool_fwd", "unet_op_maxpool_bwd", "unet_op_upsample_fwd", "unet_op_upsample_bwd", "unet_op_export_view", "unet_op_import_grad",
+    "unet_op_conv_choice2", "unet_op_conv3d_fwd2", "unet_op_conv3d_bwd_data2", "unet_op_conv3d_bwd_weight2", "unet_op_conv3d_bwd_data_norm_strided",
+    "unet_op_head_fwd", "unet_op_head_bwd",
 ]
 
 
