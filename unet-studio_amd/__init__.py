@@ -43,6 +43,7 @@ from . import start  # noqa: F401  (the module: start.EXPORTS the symbols of inc
 from . import warp  # noqa: F401  (the module: warp.EXPORTS the symbols of include/unet_warp.h)
 from . import cowarp  # noqa: F401  (the module: cowarp.EXPORTS the symbols of include/unet_cowarp.h)
 from . import deform  # noqa: F401  (the module: deform.EXPORTS the symbols of include/unet_deform.h)
+from . import bias  # noqa: F401  (the module: bias.EXPORTS the symbols of include/unet_bias.h)
 from .patches import WindowFeed, to_canvas  # noqa: F401
 
 

@@ -3,7 +3,7 @@
 # Objects are compiled in parallel (one hipcc per source) and only when the source or a header is newer.
 set -e
 cd "$(dirname "$0")"
-SRCS="graph.cpp engine.cpp comm.cpp kernels_direct.hip kernels_elem.hip kernels_sgd_pack.hip kernels_mfma_conv.hip kernels_mfma_deep.hip kernels_mfma_conv_z16.hip kernels_mfma_s2.hip kernels_mfma_s2_wgrad.hip kernels_mfma_wgrad.hip kernels_mfma_wgrad_z.hip kernels_mfma_wgrad_zd.hip kernels_augment.hip kernels_mfma_f32.hip kernels_qc.hip kernels_feed.hip kernels_postproc.hip kernels_space.hip kernels_tiles.hip kernels_mirror.hip kernels_ensemble.hip kernels_preproc.hip kernels_components.hip kernels_atlas.hip kernels_register.hip kernels_table.hip kernels_distance.hip kernels_instances.hip kernels_morph.hip kernels_stats.hip kernels_calib.hip kernels_recal.hip kernels_patches.hip kernels_coreg.hip kernels_start.hip kernels_warp.hip kernels_cowarp.hip kernels_deform.hip"
+SRCS="graph.cpp engine.cpp comm.cpp kernels_direct.hip kernels_elem.hip kernels_sgd_pack.hip kernels_mfma_conv.hip kernels_mfma_deep.hip kernels_mfma_conv_z16.hip kernels_mfma_s2.hip kernels_mfma_s2_wgrad.hip kernels_mfma_wgrad.hip kernels_mfma_wgrad_z.hip kernels_mfma_wgrad_zd.hip kernels_augment.hip kernels_mfma_f32.hip kernels_qc.hip kernels_feed.hip kernels_postproc.hip kernels_space.hip kernels_tiles.hip kernels_mirror.hip kernels_ensemble.hip kernels_preproc.hip kernels_components.hip kernels_atlas.hip kernels_register.hip kernels_table.hip kernels_distance.hip kernels_instances.hip kernels_morph.hip kernels_stats.hip kernels_calib.hip kernels_recal.hip kernels_patches.hip kernels_coreg.hip kernels_start.hip kernels_warp.hip kernels_cowarp.hip kernels_deform.hip kernels_bias.hip"
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wno-unused-result"
 mkdir -p build
 newest_hdr=$(ls -t *.h *.hpp ../../include/*.h | head -1)
@@ -35,9 +35,9 @@ for pair in conv_z:kernels_mfma_conv wgrad_z:kernels_mfma_wgrad_z conv_zdma:kern
     esac
 done
 # the co-registration kernels (kernels_coreg.hip), the kernels of the starts (kernels_start.hip) and those of the two lattice warps
-# (kernels_warp.hip, kernels_cowarp.hip: each file's own kernels and its five instantiations of lattice_fit.h's) and of their geometry (kernels_deform.hip) must not spill: read every kernel's scratch size from the compiler's resource-usage remarks whenever the file
+# (kernels_warp.hip, kernels_cowarp.hip: each file's own kernels and its five instantiations of lattice_fit.h's) and of their geometry (kernels_deform.hip) and the inhomogeneity correction's (kernels_bias.hip) must not spill: read every kernel's scratch size from the compiler's resource-usage remarks whenever the file
 # was rebuilt (the remarks stay in build/<file>.remarks: registers, LDS, occupancy)
-for pair in kernels_coreg:10 kernels_start:6 kernels_warp:9 kernels_cowarp:9 kernels_deform:8; do
+for pair in kernels_coreg:10 kernels_start:6 kernels_warp:9 kernels_cowarp:9 kernels_deform:8 kernels_bias:13; do
     f=${pair%%:*}; want=${pair##*:}
     case " $todo " in *" $f.hip "*)
         hipcc $FLAGS --cuda-device-only -c -Rpass-analysis=kernel-resource-usage $f.hip -o build/$f.dev 2> build/$f.remarks

@@ -3258,6 +3258,154 @@ int unet_deform_pull(const void* volume, int kind, int sw, int sh, int sd, int t
     });
 }
 
+// ---- the intensity-inhomogeneity correction (include/unet_bias.h) ----
+// the levels of a fit: n_levels x {g, sweeps, lam}
+static std::string bias_levels_error(const std::string& w, const int* levels, int n_levels) {
+    if (n_levels < 1 || n_levels > UNET_BIAS_MAX_LEVELS) return w + "n_levels must be in [1, 4], got " + std::to_string(n_levels);
+    if (!levels) return w + "null levels";
+    for (int l = 0; l < n_levels; ++l) {
+        const int* v = levels + 3 * l;
+        const std::string lv = w + "level " + std::to_string(l) + ": ";
+        if (std::string e = warp_g_error(lv, v[0]); !e.empty()) return e;
+        if (l && 2 * v[0] != levels[3 * (l - 1)]) return lv + "g must be half the level before's, got " + std::to_string(v[0]);
+        if (v[1] < 1 || v[1] > UNET_BIAS_MAX_SWEEPS) return lv + "sweeps must be in [1, 16], got " + std::to_string(v[1]);
+        if (v[2] < 0 || v[2] > UNET_BIAS_MAX_LAM) return lv + "lam must be in [0, 4096], got " + std::to_string(v[2]);
+    }
+    return std::string();
+}
+// q, the labels, the grid and the classes, as levels, residual and fit take them
+static std::string bias_labelled_error(const std::string& w, const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd,
+                                       const int* classes, int K) {
+    if (std::string e = ptr_error(w, q, "q", 4); !e.empty()) return e;
+    if (!labels) return w + "null labels";
+    if (lbytes != 1 && lbytes != 2) return w + "lbytes must be 1 or 2, got " + std::to_string(lbytes);
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return e;
+    if (K < 1 || K > UNET_BIAS_MAX_CLASSES) return w + "K must be in [1, 16], got " + std::to_string(K);
+    if (!classes) return w + "null classes";
+    for (int k = 0; k < K; ++k) {
+        if (classes[k] < 0 || classes[k] > 65535) return w + "classes must be label values in [0, 65535], got " + std::to_string(classes[k]);
+        for (int j = 0; j < k; ++j)
+            if (classes[j] == classes[k]) return w + "classes must be distinct, got " + std::to_string(classes[k]) + " twice";
+    }
+    return std::string();
+}
+static std::string bias_clip_error(const std::string& w, int clip) {
+    return clip < 0 || clip > UNET_BIAS_MAX ? w + "clip must be in [0, 8192], got " + std::to_string(clip) : std::string();
+}
+static std::string bias_scratch_error(const std::string& w, int sw, int sh, int sd, const int* levels, int n_levels, int impl,
+                                      const void* scratch, size_t scratch_bytes) {
+    if (impl < UNET_BIAS_IMPL_DEFAULT || impl > UNET_BIAS_IMPL_VOXEL) return w + "unknown impl " + std::to_string(impl);
+    if (!scratch) return w + "null scratch";
+    if (scratch_bytes < bias_scratch_bytes(sw, sh, sd, levels, n_levels)) return w + "scratch too small (see unet_bias_scratch_bytes)";
+    return std::string();
+}
+int unet_bias_lattice(int sw, int sh, int sd, int g, int* nx, int* ny, int* nz) {
+    const std::string w = "unet_bias_lattice: ";
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (!nx || !ny || !nz) return fail(w + "null output");
+    *nx = (sw + g - 1) / g + 1;
+    *ny = (sh + g - 1) / g + 1;
+    *nz = (sd + g - 1) / g + 1;
+    return 0;
+}
+int unet_bias_scratch_bytes(int sw, int sh, int sd, const int* levels, int n_levels, size_t* bytes) {
+    const std::string w = "unet_bias_scratch_bytes: ";
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = bias_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
+    if (!bytes) return fail(w + "null output");
+    *bytes = bias_scratch_bytes(sw, sh, sd, levels, n_levels);
+    return 0;
+}
+int unet_bias_logcode(const float* v, int64_t voxels, int32_t* q, void* stream) {
+    const std::string w = "unet_bias_logcode: ";
+    if (std::string e = ptr_error(w, v, "v", 4); !e.empty()) return fail(e);
+    if (voxels <= 0 || voxels >= ((int64_t)1 << 31)) return fail(w + "voxels must be in [1, 2^31), got " + std::to_string(voxels));
+    if (std::string e = ptr_error(w, q, "q", 4); !e.empty()) return fail(e);
+    return run_on_device_of(q, stream, [&](hipStream_t s) { launch_bias_logcode(v, voxels, q, s); });
+}
+int unet_bias_levels(const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd, const int* classes, int K, const int32_t* B,
+                     int g, int64_t* levels_out, void* stream) {
+    const std::string w = "unet_bias_levels: ";
+    if (std::string e = bias_labelled_error(w, q, labels, lbytes, sw, sh, sd, classes, K); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, B, "B", 4); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, levels_out, "levels_out", 8); !e.empty()) return fail(e);
+    return run_on_device_of(levels_out, stream, [&](hipStream_t s) {   // classes is consumed inside the launcher, before this returns
+        launch_bias_levels(q, labels, lbytes, sw, sh, sd, classes, K, B, g, levels_out, s);
+    });
+}
+int unet_bias_residual(const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd, const int* classes, int K,
+                       const int64_t* levels_in, int clip, int16_t* r, void* stream) {
+    const std::string w = "unet_bias_residual: ";
+    if (std::string e = bias_labelled_error(w, q, labels, lbytes, sw, sh, sd, classes, K); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, levels_in, "levels_in", 8); !e.empty()) return fail(e);
+    if (std::string e = bias_clip_error(w, clip); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, r, "r", 16); !e.empty()) return fail(e);
+    return run_on_device_of(r, stream, [&](hipStream_t s) {
+        launch_bias_residual(q, labels, lbytes, sw, sh, sd, classes, K, levels_in, clip, r, s);
+    });
+}
+int unet_bias_sweep(const int16_t* r, int sw, int sh, int sd, int32_t* B, int g, int lam, int64_t* info, int impl, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+    const std::string w = "unet_bias_sweep: ";
+    if (std::string e = ptr_error(w, r, "r", 16); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, B, "B", 4); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (lam < 0 || lam > UNET_BIAS_MAX_LAM) return fail(w + "lam must be in [0, 4096], got " + std::to_string(lam));
+    if (std::string e = ptr_error(w, info, "info", 8); !e.empty()) return fail(e);
+    if (impl < UNET_BIAS_IMPL_DEFAULT || impl > UNET_BIAS_IMPL_VOXEL) return fail(w + "unknown impl " + std::to_string(impl));
+    if (!scratch) return fail(w + "null scratch");
+    if (scratch_bytes < bias_sweep_scratch_bytes(sw, sh, sd, g)) return fail(w + "scratch too small (256 + 16 bytes per node, rounded up to 256)");
+    return run_on_device_of(B, stream, [&](hipStream_t s) { launch_bias_sweep(r, sw, sh, sd, B, g, lam, info, impl, scratch, s); });
+}
+int unet_bias_refine(const int32_t* B_coarse, int sw, int sh, int sd, int g, int32_t* B_fine, void* stream) {
+    const std::string w = "unet_bias_refine: ";
+    if (std::string e = ptr_error(w, B_coarse, "B_coarse", 4); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return fail(e);
+    if (g != 8 && g != 16 && g != 32) return fail(w + "g must be 8, 16 or 32, got " + std::to_string(g));
+    if (std::string e = ptr_error(w, B_fine, "B_fine", 4); !e.empty()) return fail(e);
+    return run_on_device_of(B_fine, stream, [&](hipStream_t s) { launch_bias_refine(B_coarse, sw, sh, sd, g, B_fine, s); });
+}
+int unet_bias_cost(const int16_t* r, int sw, int sh, int sd, const int32_t* B, int g, int64_t* cost, void* stream) {
+    const std::string w = "unet_bias_cost: ";
+    if (std::string e = ptr_error(w, r, "r", 2); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, B, "B", 4); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, cost, "cost", 8); !e.empty()) return fail(e);
+    return run_on_device_of(cost, stream, [&](hipStream_t s) { launch_bias_cost(r, sw, sh, sd, B, g, cost, s); });
+}
+int unet_bias_fit(const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd, const int* classes, int K, int clip,
+                  const int* levels, int n_levels, int outer, int32_t* B_out, int64_t* report, int impl, void* scratch, size_t scratch_bytes,
+                  void* stream) {
+    const std::string w = "unet_bias_fit: ";
+    if (std::string e = bias_labelled_error(w, q, labels, lbytes, sw, sh, sd, classes, K); !e.empty()) return fail(e);
+    if (std::string e = bias_clip_error(w, clip); !e.empty()) return fail(e);
+    if (std::string e = bias_levels_error(w, levels, n_levels); !e.empty()) return fail(e);
+    if (outer < 1 || outer > UNET_BIAS_MAX_OUTER) return fail(w + "outer must be in [1, 8], got " + std::to_string(outer));
+    if (std::string e = ptr_error(w, B_out, "B_out", 4); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, report, "report", 8); !e.empty()) return fail(e);
+    if (std::string e = bias_scratch_error(w, sw, sh, sd, levels, n_levels, impl, scratch, scratch_bytes); !e.empty()) return fail(e);
+    return run_on_device_of(B_out, stream, [&](hipStream_t s) {   // classes and levels are consumed inside the launcher
+        launch_bias_fit(q, labels, lbytes, sw, sh, sd, classes, K, clip, levels, n_levels, outer, B_out, report, impl, scratch, s);
+    });
+}
+static_assert(UNET_BIAS_MAX_LEVELS * UNET_BIAS_MAX_OUTER <= UNET_BIAS_MAX_ROWS, "a row per (level, outer round)");
+int unet_bias_apply(const float* v, int sw, int sh, int sd, const int32_t* B, int g, float* out, float* gain, void* stream) {
+    const std::string w = "unet_bias_apply: ";
+    if (std::string e = opt_ptr_error(w, v, "v", 4); !e.empty()) return fail(e);
+    if (std::string e = grid_dims_error(w, "volume", sw, sh, sd); !e.empty()) return fail(e);
+    if (std::string e = ptr_error(w, B, "B", 4); !e.empty()) return fail(e);
+    if (std::string e = warp_g_error(w, g); !e.empty()) return fail(e);
+    if (std::string e = opt_ptr_error(w, out, "out", 4); !e.empty()) return fail(e);
+    if (std::string e = opt_ptr_error(w, gain, "gain", 4); !e.empty()) return fail(e);
+    if (!out && !gain) return fail(w + "null out and null gain: nothing to form");
+    if (!v != !out) return fail(w + "v and out go together: both or neither");
+    return run_on_device_of(B, stream, [&](hipStream_t s) { launch_bias_apply(v, sw, sh, sd, B, g, out, gain, s); });
+}
+
 // ---- the tables of a label map (include/unet_table.h) ----
 static std::string table_common_error(const std::string& w, int64_t voxels, int n_labels, const int64_t* rows, int impl, const void* scratch,
                                       size_t scratch_bytes) {

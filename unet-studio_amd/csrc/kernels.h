@@ -7,6 +7,7 @@
 
 #include "../../include/unet_atlas.h"
 #include "../../include/unet_augment.h"
+#include "../../include/unet_bias.h"
 #include "../../include/unet_calib.h"
 #include "../../include/unet_recal.h"
 #include "../../include/unet_components.h"
@@ -582,6 +583,24 @@ void launch_cowarp_resample(const float* moving, int mw, int mh, int md, int fw,
 void launch_deform_jacobian(int sw, int sh, int sd, const float* map, const int32_t* D, int g, float* det, int64_t* info, hipStream_t s);
 void launch_deform_pull(const void* volume, int kind, int sw, int sh, int sd, int tw, int th, int td, const float* map, const float* inv,
                         const int32_t* D, int g, int iters, void* out, float* pos, int64_t* info, int impl, hipStream_t s);
+
+// kernels_bias.hip: the intensity-inhomogeneity correction (include/unet_bias.h); classes (K) and levels (n_levels x 3): host arrays,
+// read before the return.  bias_scratch_bytes: the scratch of a fit of these levels; bias_sweep_scratch_bytes: that of one sweep at g
+// (the counters of IMPL_VOXEL alone)
+size_t bias_scratch_bytes(int sw, int sh, int sd, const int* levels, int n_levels);
+size_t bias_sweep_scratch_bytes(int sw, int sh, int sd, int g);
+void launch_bias_logcode(const float* v, int64_t voxels, int32_t* q, hipStream_t s);
+void launch_bias_levels(const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd, const int* classes, int K, const int32_t* B,
+                        int g, int64_t* levels_out, hipStream_t s);
+void launch_bias_residual(const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd, const int* classes, int K,
+                          const int64_t* levels_in, int clip, int16_t* r, hipStream_t s);
+void launch_bias_sweep(const int16_t* r, int sw, int sh, int sd, int32_t* B, int g, int lam, int64_t* info, int impl, void* scratch,
+                       hipStream_t s);
+void launch_bias_refine(const int32_t* coarse, int sw, int sh, int sd, int g, int32_t* fine, hipStream_t s);
+void launch_bias_cost(const int16_t* r, int sw, int sh, int sd, const int32_t* B, int g, int64_t* cost, hipStream_t s);
+void launch_bias_fit(const int32_t* q, const void* labels, int lbytes, int sw, int sh, int sd, const int* classes, int K, int clip,
+                     const int* levels, int n_levels, int outer, int32_t* B_out, int64_t* report, int impl, void* scratch, hipStream_t s);
+void launch_bias_apply(const float* v, int sw, int sh, int sd, const int32_t* B, int g, float* out, float* gain, hipStream_t s);
 
 // kernels_table.hip: the tables of a label map (include/unet_table.h); the running table lives in the scratch
 size_t table_scratch_bytes(int n_labels);
